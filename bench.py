@@ -8,9 +8,15 @@ Metric (BASELINE.json): env-steps/sec (whole job) + SET-actor forward us/step on
 Inputs are resident in HBM when the timed region starts.  Weak scaling: every rank owns its own 8192 envs.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full           # + CPU baseline, per-kernel / roofline figures, ...
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times exactly --steps steps (one region; --regions R > 1 times R regions of --steps steps each
+and reports the median), writes the last timed step's outputs if --dump-outputs is given, and prints the headline.  Everything
+else it can measure -- the CPU baseline, the per-kernel and roofline figures, the other product forms of the SET forward, the
+replay-ingest prices, the learner-ingest region of an N > 1 run -- runs only with --full.
 """
 import argparse
 import json
@@ -147,6 +153,24 @@ def set_executed_flops_per_node():
     return 2 * (3 * layer + head)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, tensors):
+    """{name: device tensor} -> out_dir/<name>.npy, float32 (float64 stays float64); at most DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for name, t in tensors.items():
+        a = t.detach().cpu().numpy()
+        arrays[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -154,14 +178,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--envs-per-morph", type=int, default=1024)
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: CPU baseline (unless --no-cpu-baseline), per-kernel and "
+                         "roofline figures, the other SET product forms, replay-ingest prices, the N > 1 run's learner-ingest region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its actions, observations, rewards, "
+                         "done flags, distances and the SET actor's actions) as DIR/<name>.npy in float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--force-collectives", action="store_true",
                     help="diagnostic: run the N > 1 code path (process group, replay gather, barriers, max-over-ranks) with "
                          "WORLD_SIZE=1 under torch.distributed.run -- what a 1-GPU box can exercise of it")
     ap.add_argument("--set-forward-only", action="store_true",
                     help="internal: time the SET forward alone on this process's settings and print {\"ms_per_forward\": x} "
                          "(the parent bench starts it as a child with SGRL_SET_GEMM=f32 for the exact-f32 comparison)")
-    ap.add_argument("--regions", type=int, default=3, help="timed regions of --steps steps each; the median is reported")
+    ap.add_argument("--regions", type=int, default=1,
+                    help="timed regions of --steps steps each (default 1: exactly --steps timed steps); with more, the median "
+                         "region is reported")
     ap.add_argument("--preroll", type=int, default=200,
                     help="untimed rollout steps run during set-up so that episodes are desynchronised and the timed "
                          "steps see the stationary mix of flight / stance / fallen states (not warm-up of the code)")
@@ -177,7 +209,7 @@ def main():
     cpu_base = None
     if args.set_forward_only:
         args.no_cpu_baseline = True
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_base = cpu_baseline(WALKERS, args.seed)
     import torch
     import torch.distributed as dist
@@ -277,15 +309,18 @@ def main():
     # what `value` / `ms_per_step` report, all samples are listed
     samples = [timed_region() for _ in range(max(1, args.regions))]
     dt = sorted(samples)[len(samples) // 2]
+    if args.dump_outputs and rank == 0:    # the last timed step's results, before anything else steps the environments
+        dump_outputs(args.dump_outputs, {"actions": ro.actions, "obs": env.obs, "reward": env.rew, "done": env.done,
+                                         "dist": env.dist, "policy_actions": ro.policy_actions})
     dt_no_ingest = None
-    if multi:                              # the same region with the learner's ingest switched off: what the ingest costs
+    if multi and args.full:                # the same region with the learner's ingest switched off: what the ingest costs
         state["ingest"] = False
         dt_no_ingest = timed_region()
         state["ingest"] = True
 
     # per-kernel timings with HIP events on the launch stream (rank 0 only; not part of the timed region above)
     extra = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         # the step kernel INSIDE the rollout's flow: one more region of `steps` steps with a HIP event pair around every sgrl_step
         # (on torch's current stream, the stream sgrl_step launches on) -- fresh random actions, the forward between two steps
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]

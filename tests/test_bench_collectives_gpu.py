@@ -30,7 +30,7 @@ def _bench(extra_args, extra_env):
     env = dict(os.environ)
     env.update(extra_env)
     env["SGRL_BENCH_NO_CHILD"] = "1"            # no exact-f32 grand-child: one process per measurement
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "10", "--warmup", "3", "--regions", "3", "--preroll", "60",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "10", "--warmup", "3", "--regions", "3", "--preroll", "60",
            "--no-cpu-baseline"] + extra_args
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]

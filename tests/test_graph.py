@@ -82,18 +82,19 @@ def test_single_limb_graph_dict():
     assert graph.getGraphDict([-1], TRAV, [], device=torch.device("cpu")) == {"parents": [-1]}
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="reference XMLs only exist in the build container")
-def test_xml_readers_on_reference_files(golden):
-    base = "/root/reference/src/environments"
-    for sub in ["3d_hoppers", "3d_walkers", "3d_humanoids", "3d_cheetahs", "zero_shot"]:
-        for f in sorted(os.listdir(os.path.join(base, sub))):
-            if f.endswith(".xml"):
-                p = os.path.join(base, sub, f)
-                g = golden[f[:-4]]
-                assert graph.getGraphStructure(p) == g["parents"]
-                assert graph.getGraphJoints(p) == g["joints"]
-                assert graph.getMotorJoints(p) == g["motors"]
-                assert graph.action_order_for(graph.getGraphJoints(p), graph.getMotorJoints(p)) == g["action_order"]
+def test_xml_readers_on_reference_files(golden, golden_dir):
+    # the reference's 29 MJCF files (src/environments/{3d_hoppers,3d_walkers,3d_humanoids,3d_cheetahs,zero_shot}), stored
+    # under tests/golden/mjcf
+    base = os.path.join(golden_dir, "mjcf")
+    files = sorted(f for f in os.listdir(base) if f.endswith(".xml"))
+    assert [f[:-4] for f in files] == sorted(golden)
+    for f in files:
+        p = os.path.join(base, f)
+        g = golden[f[:-4]]
+        assert graph.getGraphStructure(p) == g["parents"]
+        assert graph.getGraphJoints(p) == g["joints"]
+        assert graph.getMotorJoints(p) == g["motors"]
+        assert graph.action_order_for(graph.getGraphJoints(p), graph.getMotorJoints(p)) == g["action_order"]
 
 
 def test_xml_readers_on_synthetic_mjcf(tmp_path):

@@ -1,6 +1,7 @@
 """Independent checks of the MJCF compile step (sgrl_amd/mjcf.py) -- the one piece BOTH the HIP engine and the CPU oracle
 consume, so that engine-vs-oracle parity cannot see an error in it.  Nothing here pins MuJoCo itself
 (unavailable: DESIGN.md section 2); each check compares the compiler's output with a second, differently derived value."""
+import json
 import math
 import os
 
@@ -11,7 +12,8 @@ from helpers import packed
 from oracle import physics_ref
 from sgrl_amd import mjcf
 
-REF_ENVS = "/root/reference/src/environments"
+# the reference's MJCF files (src/environments), stored as test fixtures
+REF_ENVS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mjcf")
 
 
 # ---- inertia from geoms ---------------------------------------------------------------------------------------
@@ -181,18 +183,16 @@ def test_unknown_attributes_are_refused(tmp_path):
     assert "inertial" in mjcf.audit_mjcf(str(inert))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_ENVS), reason="the reference XMLs exist in the build container only")
 def test_every_attribute_of_every_shipped_xml_is_consumed():
+    # REF_ENVS/shipped.json: every XML under the reference's src/environments (sub-folder/file) -> the stored file with its
+    # contents (the 90 shipped files are 29 distinct ones)
+    with open(os.path.join(REF_ENVS, "shipped.json")) as f:
+        shipped = json.load(f)
     n = 0
-    for sub in sorted(os.listdir(REF_ENVS)):
-        d = os.path.join(REF_ENVS, sub)
-        if not os.path.isdir(d):
-            continue
-        for f in sorted(os.listdir(d)):
-            if f.endswith(".xml"):
-                assert mjcf.audit_mjcf(os.path.join(d, f)) == [], (sub, f)
-                n += 1
-    assert n >= 29
+    for path, name in sorted(shipped.items()):
+        assert mjcf.audit_mjcf(os.path.join(REF_ENVS, name + ".xml")) == [], path
+        n += 1
+    assert n >= 29 and len(set(shipped.values())) == 29
 
 
 # ---- parallel capsule - capsule: two contacts ------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 #!/bin/bash
 # k_env_step of the walker mix with the light dimension sets on their own concurrent dispatch (SGRL_MIX_LIGHT=1) against the one-kernel launch
 for v in 0 1 0 1; do
-  SGRL_MIX_LIGHT=$v SGRL_BENCH_NO_CHILD=1 timeout -k 10 200 python3 bench.py --steps 20 --warmup 3 --regions 3 --no-cpu-baseline 2>/dev/null | python3 -c "
+  SGRL_MIX_LIGHT=$v SGRL_BENCH_NO_CHILD=1 timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 3 --regions 3 --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{\"metric\"'):

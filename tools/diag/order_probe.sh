@@ -1,7 +1,7 @@
 #!/bin/bash
 # k_env_step of the walker mix under three workgroup orders (SGRL_ORDER: 0 costliest dimension set first (default), 1 sets interleaved, 2 lightest first)
 for v in 0 1 2 0 1 2; do
-  SGRL_ORDER=$v SGRL_BENCH_NO_CHILD=1 timeout -k 10 200 python3 bench.py --steps 20 --warmup 3 --regions 3 --no-cpu-baseline 2>/dev/null | python3 -c "
+  SGRL_ORDER=$v SGRL_BENCH_NO_CHILD=1 timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 3 --regions 3 --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{\"metric\"'):

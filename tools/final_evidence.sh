@@ -9,18 +9,18 @@ O=$R/gpurun_out/final
 RAW=/tmp/sgrl_raw
 mkdir -p $O $RAW
 cd $R
-timeout 900 python3 bench.py > $RAW/bench_default.log 2> $RAW/bench_default.err
+timeout 900 python3 bench.py --full > $RAW/bench_default.log 2> $RAW/bench_default.err
 tail -1 $RAW/bench_default.log > $O/${TAG}_bench_default.json
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/stats -o s -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline > $RAW/bench_prof.log 2> $RAW/stats.err
-timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $RAW/fetch -o f -- python3 $R/bench.py --steps 5 --warmup 3 --no-cpu-baseline > $RAW/fetch.log 2>&1
-timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $RAW/write -o w -- python3 $R/bench.py --steps 5 --warmup 3 --no-cpu-baseline > $RAW/write.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/stats -o s -- python3 $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $RAW/bench_prof.log 2> $RAW/stats.err
+timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $RAW/fetch -o f -- python3 $R/bench.py --full --steps 5 --warmup 3 --no-cpu-baseline > $RAW/fetch.log 2>&1
+timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $RAW/write -o w -- python3 $R/bench.py --full --steps 5 --warmup 3 --no-cpu-baseline > $RAW/write.log 2>&1
 cd $R
 grep '^{"metric"' $RAW/bench_prof.log | tail -1 > $RAW/bench_prof.json
 python3 tools/summarize_profiles.py $TAG $RAW/stats $RAW/fetch $RAW/write $RAW/bench_prof.json > $O/summarize.log 2>&1
 python3 tools/set_traffic.py $TAG >> $O/summarize.log 2>&1
 # the default bench again, now quoting the fresh pmc_traffic.json (copied AFTER the profiles/ summaries: same file name)
-timeout 900 python3 bench.py > $RAW/bench_default2.log 2>> $RAW/bench_default.err
+timeout 900 python3 bench.py --full > $RAW/bench_default2.log 2>> $RAW/bench_default.err
 cp profiles/${TAG}_bench.json $O/${TAG}_bench_under_rocprof.json
 cp profiles/${TAG}_kernel_stats.csv profiles/${TAG}_pmc_*_summary.csv profiles/${TAG}_set_traffic.json profiles/pmc_traffic.json $O/ 2>/dev/null
 tail -1 $RAW/bench_default2.log > $O/${TAG}_bench.json

@@ -7,11 +7,11 @@ O=$R/gpurun_out/final
 RAW=/tmp/sgrl_raw
 mkdir -p $O $RAW
 cd $R
-timeout 600 python3 bench.py > $RAW/bench_default.log 2> $RAW/bench_default.err
+timeout 600 python3 bench.py --full > $RAW/bench_default.log 2> $RAW/bench_default.err
 tail -1 $RAW/bench_default.log > $O/${TAG}_bench_default.json
 echo "bench done" 
 cd /tmp && export TMPDIR=/tmp && export SGRL_BENCH_NO_CHILD=1
-B="python3 $R/bench.py --warmup 3 --no-cpu-baseline --regions 1"
+B="python3 $R/bench.py --full --warmup 3 --no-cpu-baseline --regions 1"
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/stats -o s -- $B --steps 20 > $RAW/bench_prof.log 2> $RAW/stats.err
 echo "stats done"
 timeout 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $RAW/fetch -o f -- $B --steps 5 > $RAW/fetch.log 2>&1
@@ -28,7 +28,7 @@ python3 tools/sq_pmc.py $TAG $RAW/sq1 $RAW/sq2 8192 >> $O/summarize.log 2>&1
 python3 tools/set_traffic.py $TAG >> $O/summarize.log 2>&1
 python3 tools/mfma_pmc.py $TAG $RAW/sq3 >> $O/summarize.log 2>&1
 unset SGRL_BENCH_NO_CHILD
-timeout 600 python3 bench.py > $RAW/bench_default2.log 2>> $RAW/bench_default.err      # now quoting the fresh pmc_traffic.json / sq_pmc.json
+timeout 600 python3 bench.py --full > $RAW/bench_default2.log 2>> $RAW/bench_default.err      # now quoting the fresh pmc_traffic.json / sq_pmc.json
 cp profiles/${TAG}_bench.json $O/${TAG}_bench_under_rocprof.json
 cp profiles/${TAG}_kernel_stats.csv profiles/${TAG}_pmc_*_summary.csv profiles/${TAG}_set_traffic.json profiles/${TAG}_set_mfma_pmc.json profiles/pmc_traffic.json profiles/sq_pmc.json $O/ 2>/dev/null
 tail -1 $RAW/bench_default2.log > $O/${TAG}_bench.json

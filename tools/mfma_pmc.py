@@ -17,7 +17,7 @@ for r in csv.DictReader(open(glob.glob(d + "/**/*counter_collection.csv", recurs
              "k_gemm3<10": "k_gemm3 equivariant epilogue (linear4)"}.get(k, k)
     acc[k][r["Counter_Name"]].append(float(r["Counter_Value"]))
 out = {"command": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F16 SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY "
-                  "SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE --kernel-trace -- python3 bench.py --steps 5 --warmup 3 "
+                  "SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE --kernel-trace -- python3 bench.py --full --steps 5 --warmup 3 "
                   "--no-cpu-baseline --regions 1", "build": tag, "kernels": {}}
 for k, c in sorted(acc.items()):
     m = {n: float(np.mean(v)) for n, v in c.items()}

@@ -17,7 +17,7 @@ done
 unset SGRL_GRAPH_UPDATES
 timeout -k 10 300 python tools/diag/update_launch_sources.py > $O/update_launch_sources.txt 2>&1; tail -n 3 $O/update_launch_sources.txt
 timeout -k 10 200 python tools/diag/numpy_surface_probe.py 2>/dev/null | tail -n 1 | tee $O/numpy_surface.txt
-timeout -k 10 400 python bench.py --no-cpu-baseline 2>/dev/null | tail -n 1 > $O/bench.json; python - <<PY
+timeout -k 10 400 python bench.py --full --no-cpu-baseline 2>/dev/null | tail -n 1 > $O/bench.json; python - <<PY
 import json
 j = json.load(open("$O/bench.json"))
 print("bench: %.0f env-steps/s, %.3f ms/step, k_env_step %.3f ms (in rollout %.3f), set fwd %.3f ms" % (j["value"], j["ms_per_step"], j["roofline"]["ms_per_launch"], j["roofline"]["ms_per_launch_in_rollout"], j["set_actor"]["ms_per_forward"]))

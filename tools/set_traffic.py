@@ -12,7 +12,7 @@ for name in ("fetch", "write"):
     for r in csv.DictReader(open("profiles/%s_pmc_%s_size_summary.csv" % (tag, name))):
         tab.setdefault(r["kernel"], {})[name] = (int(r["launches"]), float(r["mean_KB"]))
 fwd = tab["k_embed"]["fetch"][0]
-out = {"command": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE --kernel-trace -- python3 bench.py --steps 5 --warmup 3 --no-cpu-baseline "
+out = {"command": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE --kernel-trace -- python3 bench.py --full --steps 5 --warmup 3 --no-cpu-baseline "
                   "(two passes); per-kernel means x launches, summed over the kernels of one SET forward",
        "forwards": fwd, "nodes": nodes, "per_forward_GB_raw": {}, "per_kernel_MB_per_forward_raw": {}}
 tot = {"fetch": 0.0, "write": 0.0}

@@ -12,7 +12,7 @@ for d in (d1, d2):
 m = {c: float(np.mean(v[len(v) // 2:])) for c, v in acc["k_env_step"].items()}       # second half: stationary episode mix
 n = len(next(iter(acc["k_env_step"].values())))
 cyc = m["GRBM_GUI_ACTIVE"] / 8.0
-out = {"command": "rocprofv3 --pmc <8 SQ counters> --kernel-trace -- python3 bench.py --steps 5 --warmup 3 --no-cpu-baseline (two passes: "
+out = {"command": "rocprofv3 --pmc <8 SQ counters> --kernel-trace -- python3 bench.py --full --steps 5 --warmup 3 --no-cpu-baseline (two passes: "
                   "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES | "
                   "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE)",
        "build": tag, "envs_per_gpu": n_env,

@@ -32,7 +32,7 @@ for i in range(0, len(tr) - groups + 1, groups):
     durs.append(sum(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in chunk) / 1e6)
 half = len(spans) // 2   # the second half of the run is the stationary episode mix (after the pre-roll)
 span_ms = float(np.mean(spans[half:])) if spans else None
-out = {"command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python3 bench.py --steps 5 --warmup 3 --no-cpu-baseline (two separate passes)",
+out = {"command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python3 bench.py --full --steps 5 --warmup 3 --no-cpu-baseline (two separate passes)",
        "envs_per_gpu": json.loads(line)["config"]["envs_per_gpu"], "kernel": "k_env_step (this workload: k_env_step_spec, the walker family's fixed-dimension kernel)",
        "FETCH_SIZE_KB_per_launch_mean": round(means["fetch"][0], 1), "WRITE_SIZE_KB_per_launch_mean": round(means["write"][0], 1),
        "dispatches_per_launch": groups, "dispatches": means["fetch"][1],
