@@ -1,0 +1,107 @@
+/* sgrl_swat.h -- C ABI of the SWAT (structure-aware transformer) actor forward in libsgrl_hip.so.
+ *
+ * Replaces, for inference under torch.no_grad(), the chain
+ *   Agent.select_action                    reference src/agent.py:189-198
+ *   -> StructurePolicy.forward             reference src/StructureActor.py:221-243
+ *   -> TransformerModel.forward            reference src/StructureActor.py:159-170
+ *   -> RepeatTransformerEncoder.forward    reference src/StructureActor.py:77-107
+ *   -> MyTransformerEncoderLayer.forward   reference src/StructureActor.py:52-64
+ *   -> MyMultiheadAttention.forward        reference src/StructureActor.py:36-45
+ * for a whole batch of environments of mixed morphologies in one call (environment blocks per morphology, the nodes of one
+ * environment contiguous, node-major rows).  Every per-node linear layer runs over the nodes of ALL morphologies at once
+ * (exact-f32 matrix instructions, csrc/gemm_f32.h k_gemm2); attention runs per environment over its own limbs, one workgroup
+ * per environment.  The number of launches per forward is fixed (22) whatever the number of morphologies; a forward never
+ * synchronises with the host and can be recorded into a hipGraph.
+ *
+ * Shapes (sgrl_amd/swat_policy.py, the reference's default_args): embedding E = 128, 2 heads of 64, feed-forward 256, 3 layers,
+ * relation features 3, position tables of 15 rows (so at most 15 limbs), `feature` inputs and `out` outputs per limb.
+ */
+#ifndef SGRL_SWAT_H
+#define SGRL_SWAT_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct sgrl_swat sgrl_swat;
+
+/* Parameter table of sgrl_swat_bind_params: one DEVICE address per tensor, contiguous float32 exactly as torch stores it
+ * (nn.Linear weights [out, in] row-major, in_proj_weight already stacked q | k | v).  Global slots first ... */
+enum {
+  SGRL_SWAT_EMB0 = 0,   /* pos_encoder.embeddings.0.weight [15, 42] */
+  SGRL_SWAT_EMB1,       /* pos_encoder.embeddings.1.weight [15, 42] */
+  SGRL_SWAT_EMB2,       /* pos_encoder.embeddings.2.weight [15, 44] */
+  SGRL_SWAT_ENC_W,      /* encoder.weight [128, feature] */
+  SGRL_SWAT_ENC_B,      /* encoder.bias [128] */
+  SGRL_SWAT_REL_W,      /* transformer_encoder.rel_encoder.weight [2, 3] */
+  SGRL_SWAT_REL_B,      /* transformer_encoder.rel_encoder.bias [2] */
+  SGRL_SWAT_DEC_W,      /* decoder.weight [out, 128] or [out, 128 + feature] (cond_decoder) */
+  SGRL_SWAT_DEC_B,      /* decoder.bias [out] */
+  SGRL_SWAT_NGLOBAL
+};
+/* ... then per layer l (slot = SGRL_SWAT_NGLOBAL + l * SGRL_SWAT_NLAYER + k), prefix transformer_encoder.layers.<l>. ... */
+enum {
+  SGRL_SWAT_IN_W = 0,   /* self_attn.in_proj_weight [384, 128] */
+  SGRL_SWAT_IN_B,       /* self_attn.in_proj_bias [384] */
+  SGRL_SWAT_OUT_W,      /* self_attn.out_proj.weight [128, 128] */
+  SGRL_SWAT_OUT_B,      /* self_attn.out_proj.bias [128] */
+  SGRL_SWAT_L1_W,       /* linear1.weight [256, 128] */
+  SGRL_SWAT_L1_B,       /* linear1.bias [256] */
+  SGRL_SWAT_L2_W,       /* linear2.weight [128, 256] */
+  SGRL_SWAT_L2_B,       /* linear2.bias [128] */
+  SGRL_SWAT_N1_W,       /* norm1.weight [128] */
+  SGRL_SWAT_N1_B,       /* norm1.bias [128] */
+  SGRL_SWAT_N2_W,       /* norm2.weight [128] */
+  SGRL_SWAT_N2_B,       /* norm2.bias [128] */
+  SGRL_SWAT_NLAYER
+};
+#define SGRL_SWAT_LAYERS 3
+/* ... then, with transformer_norm only, transformer_encoder.norm.weight [128] and .bias [128] (the final LayerNorm). */
+#define SGRL_SWAT_NW(transformer_norm) (SGRL_SWAT_NGLOBAL + SGRL_SWAT_LAYERS * SGRL_SWAT_NLAYER + ((transformer_norm) ? 2 : 0))
+#define SGRL_SWAT_MAX_LIMBS 15
+
+/* reference StructurePolicy.__init__ (StructureActor.py:179-219) builds the network; here: a handle with no weights and no
+ * batch structure yet.  SGRL_ERR_HIP when no device is visible (there is no CPU fallback). */
+int sgrl_swat_create(sgrl_swat** out);
+void sgrl_swat_destroy(sgrl_swat* s);
+
+/* Bind the network's parameters by address (reference agent.py:155-176 and common/functional.py:7-10 update the same tensors in
+ * place: optimizer steps, soft updates, load_state_dict and in-place broadcasts therefore need no call).  The handle keeps only
+ * the addresses and every forward reads the values behind them; re-bind after anything that MOVES a parameter (module.to(),
+ * re-created tensors).  ptrs: HOST array of n = SGRL_SWAT_NW(transformer_norm) DEVICE addresses in the slot order above, each
+ * 16-byte aligned.  cond_decoder: condition_decoder_on_features (StructureActor.py:146-150, 166-168); transformer_norm: the
+ * final LayerNorm (StructureActor.py:131-134); feature / out: inputs / outputs per limb (41 / 3 for the actor,
+ * 1 <= feature <= 64, 1 <= out <= 8). */
+int sgrl_swat_bind_params(sgrl_swat* s, const void* const* ptrs, int n, int cond_decoder, int transformer_norm, int feature,
+                          int out);
+
+/* Batch structure (StructurePolicy.change_morphology for every morphology at once, reference StructureActor.py:266-273):
+ *   n_morph, morph_L[n_morph] limbs (1 .. 15), morph_count[n_morph] envs per morphology (env blocks in this order),
+ *   trav: HOST int32, per morphology 3*L traversal indices (pre, inlcrs, postlcrs), concatenated, each in [0, 15),
+ *   rel:  HOST float, per morphology L*L*3 relation tensor (graph_dict['relation']), concatenated.
+ * Structures are cached by CONTENT (up to SGRL_SWAT_GRAPH_CACHE): switching back to one seen before swaps pointers, with no
+ * allocation, upload or device synchronisation.  The relation bias itself is computed inside every forward (rel_encoder is
+ * trainable), never cached.  SGRL_ERR_ARG for a morphology of more than SGRL_SWAT_MAX_LIMBS limbs. */
+int sgrl_swat_graph(sgrl_swat* s, int n_morph, const int32_t* morph_L, const int32_t* morph_count, const int32_t* trav,
+                    const float* rel);
+#define SGRL_SWAT_GRAPH_CACHE 64
+
+/* act[e, out*l + j] = max_action * tanh(actor(obs[e, feature*l : feature*l + feature]))[l][j] for the limbs l of env e
+ * (reference StructureActor.py:221-243), act[e, out*L_e : act_ld] = 0 exactly.  obs: DEV float [n_env, obs_ld]; act: DEV float
+ * [n_env, act_ld].  SGRL_ERR_ARG unless obs_ld >= feature * Lmax and act_ld >= out * Lmax.  Asynchronous on `stream`. */
+int sgrl_swat_forward(sgrl_swat* s, const float* obs, int obs_ld, float* act, int act_ld, float max_action, void* stream);
+
+/* Nodes / environments of the current batch structure; launches per forward (constant). */
+int sgrl_swat_num_nodes(const sgrl_swat* s);
+int sgrl_swat_launches(void);
+/* Counter bumped whenever the handle FREES device memory a captured forward may point into (an evicted batch structure, a
+ * regrown workspace): a hipGraph holding forwards of this handle must be captured again once it has changed. */
+int64_t sgrl_swat_generation(const sgrl_swat* s);
+const char* sgrl_swat_last_error(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* SGRL_SWAT_H */

@@ -1,7 +1,7 @@
 """Batched rollout driver: the build's counterpart of the reference's per-env Python loop
 (`for i in range(num_envs_train): change_morphology; select_action; ...; envs.step`, reference trainer.py:173-236
 and the random-action warm-up loop trainer.py:90-138), with the same per-environment semantics but ONE engine
-launch and ONE batched SET forward per time step, plus the replay push as a single gather to the learner rank.
+launch and ONE batched actor forward (SET or SWAT) per time step, plus the replay push as a single gather to the learner rank.
 """
 import ctypes
 
@@ -11,6 +11,7 @@ import torch
 from . import graph as G
 from .replay import DeviceReplayBuffer
 from .set_hip import HipSetActor
+from .swat_hip import HipSwatActor
 from .vec_env import BatchedModularVecEnv
 
 TRAV = ["pre", "inlcrs", "postlcrs"]
@@ -19,8 +20,20 @@ FUSED_RECORD = True      # False (tests, A/B): RoundCollector's bookkeeping as ~
 FUSED_INGEST = True      # False (tests): the learner writes a gathered block morphology by morphology with indexed copies (the CPU path) on the GPU too
 
 
+def hip_actor_class(policy):
+    """The batched HIP forward for `policy`'s type: `SEPolicy` -> `HipSetActor`, `StructurePolicy` (SWAT) -> `HipSwatActor`."""
+    from .set_policy import SEPolicy
+    from .swat_policy import StructurePolicy
+    if isinstance(policy, SEPolicy):
+        return HipSetActor
+    if isinstance(policy, StructurePolicy):
+        return HipSwatActor
+    raise NotImplementedError("the batched rollout has HIP actor forwards for SEPolicy (SET) and StructurePolicy (SWAT) only, "
+                              "not for %s" % type(policy).__name__)
+
+
 class Rollout(object):
-    """Environments of one rank + the shared SET actor."""
+    """Environments of one rank + the shared actor (SET or SWAT)."""
 
     def __init__(self, env_names, envs_per_morph, policy=None, seed=0, device="cuda:0", rank=0, hold_weights=False, **env_kw):
         counts = [envs_per_morph] * len(env_names) if np.isscalar(envs_per_morph) else list(envs_per_morph)
@@ -31,7 +44,7 @@ class Rollout(object):
         self.actor = None
         if policy is not None:
             self.graph_dicts = [G.getGraphDict(m.parents, TRAV, [], device=self.device) for m in self.env.models]
-            self.actor = HipSetActor(policy, device=self.device)
+            self.actor = hip_actor_class(policy)(policy, device=self.device)
             self.actor.configure(self.graph_dicts, counts)
             if hold_weights:      # the owner of the loop says when the policy's parameters change (weights_changed)
                 self.actor.hold_weights(True)
@@ -77,7 +90,7 @@ class Rollout(object):
         return self.actions
 
     def policy_forward(self, obs=None):
-        """One batched SET forward over every environment (replaces n x Agent.select_action, reference agent.py:189-198)."""
+        """One batched actor forward over every environment (replaces n x Agent.select_action, reference agent.py:189-198)."""
         if self.holds_weights and self._weights_fingerprint() != self._weights_seen:
             self.weights_changed()          # the held pack is stale (ADVICE r4): pack again, keep holding
         return self.actor.forward_batch(self.env.obs if obs is None else obs, out=self.policy_actions,

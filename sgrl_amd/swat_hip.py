@@ -1,0 +1,207 @@
+"""Batched HIP forward of the SWAT actor (csrc/swat_actor.hip, C ABI in include/sgrl_swat.h).
+
+`HipSwatActor` binds the parameters of a `StructurePolicy` (swat_policy.py, reference-compatible state_dict) to a handle BY
+ADDRESS: nothing is packed, the library reads the live tensors on every forward, so optimizer steps, soft updates,
+`load_state_dict` and in-place broadcasts need no notification; only a parameter whose storage MOVES (`.to()`, re-created
+tensors) needs a re-bind, which `sync_weights` does by itself.  It has the surface `Rollout` uses on `HipSetActor`
+(`configure`, `forward_batch`, `hold_weights`, `sync_weights`, `n_env`, `max_limbs`).  No CPU fallback: without the MI355X
+every entry point raises `_lib.SgrlError`.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from .set_hip import graph_key
+
+LAYERS = 3
+_LAYER_PARAMS = ("self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight", "self_attn.out_proj.bias",
+                 "linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias", "norm1.weight", "norm1.bias",
+                 "norm2.weight", "norm2.bias")
+
+
+def _config(net):
+    """(feature, out, cond_decoder, transformer_norm, E, hidden) of a swat_policy.TransformerModel."""
+    feature = int(net.encoder.in_features)
+    out = int(net.decoder.out_features)
+    E = int(net.encoder.out_features)
+    hid = int(net.transformer_encoder.layers[0].linear1.out_features)
+    return feature, out, bool(net.condition_decoder), net.transformer_encoder.norm is not None, E, hid
+
+
+def plan_params(net):
+    """[(name, shape)] of `net` (a swat_policy.TransformerModel, e.g. StructurePolicy.actor) in the slot order of
+    sgrl_swat_bind_params (include/sgrl_swat.h): globals, then 12 per layer, then the final norm with transformer_norm.
+    Host only: works on a module on any device."""
+    feature, out, cond, tnorm, E, hid = _config(net)
+    if (E, hid, len(net.transformer_encoder.layers), net.transformer_encoder.nhead) != (128, 256, LAYERS, 2):
+        raise _lib.SgrlError("the HIP SWAT forward is built for E = 128, 2 heads, feed-forward 256, 3 layers")
+    emb = [int(e.weight.shape[1]) for e in net.pos_encoder.embeddings]
+    plan = [("pos_encoder.embeddings.%d.weight" % i, (15, w)) for i, w in enumerate(emb)]
+    plan += [("encoder.weight", (E, feature)), ("encoder.bias", (E,)),
+             ("transformer_encoder.rel_encoder.weight", (2, 3)), ("transformer_encoder.rel_encoder.bias", (2,)),
+             ("decoder.weight", (out, E + feature if cond else E)), ("decoder.bias", (out,))]
+    shapes = {"self_attn.in_proj_weight": (3 * E, E), "self_attn.in_proj_bias": (3 * E,),
+              "self_attn.out_proj.weight": (E, E), "self_attn.out_proj.bias": (E,), "linear1.weight": (hid, E),
+              "linear1.bias": (hid,), "linear2.weight": (E, hid), "linear2.bias": (E,)}
+    for l in range(LAYERS):
+        plan += [("transformer_encoder.layers.%d.%s" % (l, n), shapes.get(n, (E,))) for n in _LAYER_PARAMS]
+    if tnorm:
+        plan += [("transformer_encoder.norm.weight", (E,)), ("transformer_encoder.norm.bias", (E,))]
+    return plan
+
+
+def _bind(L):
+    if getattr(L, "_swat_bound", False):
+        return
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    L.sgrl_swat_create.argtypes = [ctypes.POINTER(vp)]
+    L.sgrl_swat_create.restype = ci
+    L.sgrl_swat_destroy.argtypes = [vp]
+    L.sgrl_swat_destroy.restype = None
+    L.sgrl_swat_bind_params.argtypes = [vp, vp, ci, ci, ci, ci, ci]
+    L.sgrl_swat_bind_params.restype = ci
+    L.sgrl_swat_graph.argtypes = [vp, ci, vp, vp, vp, vp]
+    L.sgrl_swat_graph.restype = ci
+    L.sgrl_swat_forward.argtypes = [vp, vp, ci, vp, ci, ctypes.c_float, vp]
+    L.sgrl_swat_forward.restype = ci
+    L.sgrl_swat_num_nodes.argtypes = [vp]
+    L.sgrl_swat_num_nodes.restype = ci
+    L.sgrl_swat_launches.argtypes = []
+    L.sgrl_swat_launches.restype = ci
+    L.sgrl_swat_generation.argtypes = [vp]
+    L.sgrl_swat_generation.restype = ctypes.c_int64
+    L.sgrl_swat_last_error.argtypes = []
+    L.sgrl_swat_last_error.restype = ctypes.c_char_p
+    L._swat_bound = True
+
+
+def _check(L, rc, what):
+    if rc != 0:
+        raise _lib.SgrlError("%s failed (%d): %s" % (what, rc, L.sgrl_swat_last_error().decode()))
+
+
+class HipSwatActor(object):
+    """HIP forward of the actor network of a `StructurePolicy` (or, with `net=`, any swat_policy.TransformerModel)."""
+
+    def __init__(self, policy, device=None, net=None):
+        if not torch.cuda.is_available():
+            raise _lib.SgrlError("HipSwatActor needs an MI355X (no CPU fallback)")
+        self.L = _lib.lib()
+        _bind(self.L)
+        self.policy = policy
+        self.net = net if net is not None else policy.actor
+        self.device = torch.device(device) if device is not None else next(self.net.parameters()).device
+        if self.device.type != "cuda":
+            raise _lib.SgrlError("the StructurePolicy must live on the GPU for the HIP path")
+        self.feature, self.out_dim, self.cond, self.tnorm = _config(self.net)[:4]
+        self.plan = plan_params(self.net)
+        h = ctypes.c_void_p()
+        _check(self.L, self.L.sgrl_swat_create(ctypes.byref(h)), "sgrl_swat_create")
+        self.h = h
+        self._bound = None
+        self._cfg_key = None
+        self._cfg_info = {}
+        self.n_env = 0
+        self.max_limbs = 0
+        self.num_nodes = 0
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                self.L.sgrl_swat_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    # ---- weights ------------------------------------------------------------------------------------
+    def _params(self):
+        named = dict(self.net.named_parameters())
+        return [named[n] for n, _ in self.plan]
+
+    def sync_weights(self, force=False):
+        """Bind the handle to the parameters' storage (include/sgrl_swat.h sgrl_swat_bind_params).  The VALUES are read by every
+        forward; this binds again only when a parameter's address moved (module.to(), re-created tensors) or with force."""
+        params = self._params()
+        ptrs = tuple(p.data_ptr() for p in params)
+        if not force and ptrs == self._bound:
+            return
+        for (name, shape), p in zip(self.plan, params):
+            if not (p.is_cuda and p.device == self.device and p.dtype == torch.float32 and p.is_contiguous()
+                    and tuple(p.shape) == tuple(shape) and p.data_ptr() % 16 == 0):
+                raise _lib.SgrlError("SWAT parameter %s must be a contiguous, 16-byte aligned float32 %s tensor on %s (got %s %s on %s)"
+                                     % (name, tuple(shape), self.device, p.dtype, tuple(p.shape), p.device))
+        arr = (ctypes.c_void_p * len(ptrs))(*ptrs)
+        _check(self.L, self.L.sgrl_swat_bind_params(self.h, ctypes.cast(arr, ctypes.c_void_p), len(ptrs), int(self.cond),
+                                                    int(self.tnorm), self.feature, self.out_dim), "sgrl_swat_bind_params")
+        self._bound = ptrs
+
+    def hold_weights(self, hold=True):
+        """No-op apart from binding: nothing is packed, every forward reads the live parameters (HipSetActor.hold_weights
+        promises stability so that a packed copy can be reused; there is no copy here)."""
+        self.sync_weights()
+
+    # ---- batch structure ------------------------------------------------------------------------------
+    def configure(self, graphs, counts):
+        """graphs: per-morphology dicts with 'parents', 'traversals' (3 index vectors) and 'relation' [L, L, 3]; counts: envs
+        each.  Structures seen before are switched to without device work (the library caches them by content)."""
+        key = (tuple(graph_key(g) for g in graphs), tuple(int(c) for c in counts))
+        if key == self._cfg_key:
+            return
+        args = self._cfg_info.get(key)
+        if args is None:
+            Ls, trav, rel = [], [], []
+            for g in graphs:
+                t = [np.asarray(v.cpu() if torch.is_tensor(v) else v, dtype=np.int32) for v in g["traversals"]]
+                Ls.append(len(t[0]))
+                trav.append(np.concatenate(t))
+                r = g["relation"]
+                rel.append(np.asarray(r.detach().cpu() if torch.is_tensor(r) else r, dtype=np.float32).reshape(-1))
+            args = (np.asarray(Ls, dtype=np.int32), np.asarray(counts, dtype=np.int32),
+                    np.ascontiguousarray(np.concatenate(trav), dtype=np.int32),
+                    np.ascontiguousarray(np.concatenate(rel), dtype=np.float32))
+            if len(self._cfg_info) >= 64:
+                self._cfg_info.clear()
+            self._cfg_info[key] = args
+        Ls, cnt, trav, rel = args
+        vp = lambda a: ctypes.c_void_p(a.ctypes.data)
+        _check(self.L, self.L.sgrl_swat_graph(self.h, len(Ls), vp(Ls), vp(cnt), vp(trav), vp(rel)), "sgrl_swat_graph")
+        self._cfg_key = key
+        self.n_env = int(cnt.sum())
+        self.max_limbs = int(Ls.max())
+        self.num_nodes = self.L.sgrl_swat_num_nodes(self.h)
+
+    def launches(self):
+        """Kernel launches per forward (constant)."""
+        return int(self.L.sgrl_swat_launches())
+
+    def generation(self):
+        return int(self.L.sgrl_swat_generation(self.h))
+
+    @staticmethod
+    def _ld(t):
+        return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+
+    def forward_batch(self, obs, out=None, act_ld=None):
+        """obs: float32 CUDA [n_env, obs_ld] -> actions float32 [n_env, act_ld] (StructurePolicy.forward for every environment;
+        slots beyond out * L_e of a row are exact zeros)."""
+        assert obs.is_cuda and obs.dtype == torch.float32 and obs.dim() == 2 and obs.stride(1) == 1
+        assert obs.shape[0] == self.n_env
+        assert obs.shape[1] >= self.feature * self.max_limbs, "observation rows narrower than feature * max_limbs"
+        self.sync_weights()
+        act_ld = act_ld or self.out_dim * self.max_limbs
+        assert act_ld >= self.out_dim * self.max_limbs, "action rows narrower than out * max_limbs"
+        if out is None:
+            out = torch.empty((self.n_env, act_ld), dtype=torch.float32, device=self.device)
+        assert out.is_contiguous() and out.shape == (self.n_env, act_ld)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _check(self.L, self.L.sgrl_swat_forward(self.h, ctypes.c_void_p(obs.data_ptr()), self._ld(obs),
+                                                ctypes.c_void_p(out.data_ptr()), int(act_ld),
+                                                ctypes.c_float(float(self.policy.max_action)), stream), "sgrl_swat_forward")
+        return out
+
+    def forward_single(self, state, graph):
+        """StructurePolicy.forward(state [B, feature * L]) for one morphology."""
+        self.configure([graph], [state.shape[0]])
+        return self.forward_batch(state.contiguous().float(), act_ld=self.out_dim * len(graph["parents"]))

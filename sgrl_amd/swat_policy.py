@@ -4,9 +4,10 @@
 `state_dict()` keys of reference src/StructureActor.py:176-273 / src/StructureCritic.py:8-125: a plain transformer over the
 limbs (embedding size 128, 2 heads, 3 layers) with the three traversal-index position embeddings added once and the
 relation bias (PPR, symmetric Laplacian, distance -> one additive bias per head) on the first layer only.  Plain
-differentiable PyTorch -- this baseline has no HIP fast path (the SET model is the one the north star names); outputs are
-pinned to fixtures produced by executing the reference's own modules (tests/golden/swat_forward.npz,
-tools/capture_golden_swat.py).
+differentiable PyTorch; outputs are pinned to fixtures produced by executing the reference's own modules
+(tests/golden/swat_forward.npz, tools/capture_golden_swat.py).  The batched rollout runs the actor's no-grad forward on the HIP
+kernels of swat_hip.HipSwatActor (csrc/swat_actor.hip), which read this module's parameters in place; `forward` itself stays
+PyTorch (the TD3 update back-props through it).
 """
 import copy
 import math

@@ -11,7 +11,9 @@
     `sgrl_get_records` every 50 steps of environments whose episode has lasted at least 50 steps.  Writes
     gpurun_out/policy_states.npz (copied to tests/golden/ by hand).
 
-usage: learn_curve.py [train_seconds=480] [envs_per_morph=64] [seed=3] [hopper|walker]
+usage: learn_curve.py [train_seconds=480] [envs_per_morph=64] [seed=3] [hopper|walker] [set|swat]
+The fifth argument picks the actor and critic type (default set).  With swat the collection runs on the batched HIP SWAT
+forward (sgrl_amd/swat_hip.py), the updates eagerly through td3.Agent (no graphed updates), and only (1) runs.
 """
 import json
 import os
@@ -34,6 +36,9 @@ budget = float(sys.argv[1]) if len(sys.argv) > 1 else 480.0
 per = int(sys.argv[2]) if len(sys.argv) > 2 else 64
 seed = int(sys.argv[3]) if len(sys.argv) > 3 else 3
 family = sys.argv[4] if len(sys.argv) > 4 else "hopper"      # "walker" / "humanoid" / "cheetah" / "cwhh" (config 5): training only
+actor_type = sys.argv[5] if len(sys.argv) > 5 else "set"
+if actor_type not in ("set", "swat"):
+    raise SystemExit("actor type must be set or swat, not %r" % actor_type)
 HOPPERS = ["3d_hopper_3_shin", "3d_hopper_4_lower_shin", "3d_hopper_5_full"]
 
 
@@ -43,7 +48,7 @@ def diag(env):
 
 
 def train():
-    args = default_train_args()
+    args = default_train_args(actor_type=actor_type, critic_type=actor_type)
     held = {"3d_walker_3_left_knee_right_knee", "3d_walker_6_right_foot", "3d_humanoid_7_left_leg", "3d_humanoid_8_right_knee",
             "3d_cheetah_11_leftbkneen_rightffoot", "3d_cheetah_12_tail_leftffoot"}
     if family == "hopper":
@@ -52,7 +57,8 @@ def train():
         names = sorted(n for n in mjcf.list_assets() if n not in held)
     else:
         names = sorted(n for n in mjcf.list_assets() if family in n)
-    tr = DeviceTrainer(names, per, args=args, seed=seed, device="cuda:0", max_buffer_size=400000, graph_updates=True)
+    tr = DeviceTrainer(names, per, args=args, seed=seed, device="cuda:0", max_buffer_size=400000,
+                      graph_updates=actor_type == "set")
     env = tr.ro.env
     curve = []
     t0 = time.time()
@@ -78,7 +84,7 @@ def train():
         if rnd % 5 == 0:
             print("round %d: return %.2f length %.1f iters %d wall %.0f s" % (rnd, s["performance/train_return"],
                   s["performance/train_length"], s["per_morph_iter"], s["wall_s"]), flush=True)
-    out = {"seed": seed, "config": "BASELINE.json config %s (%s) x %d envs" % ({"hopper": "2: 3D_Hopper++", "walker": "3: 3D_Walker++", "humanoid": "4: 3D_Humanoid++", "cwhh": "5: 3D_CWHH++"}.get(family, family), ", ".join(names), per),
+    out = {"seed": seed, "actor_type": actor_type, "config": "BASELINE.json config %s (%s) x %d envs" % ({"hopper": "2: 3D_Hopper++", "walker": "3: 3D_Walker++", "humanoid": "4: 3D_Humanoid++", "cwhh": "5: 3D_CWHH++"}.get(family, family), ", ".join(names), per),
            "schedule": "reference trainer.py:143-286 (per_morph_iter updates per morphology per round, batch %d (agent_batch_size, reference configs/default.py:61), lr 1e-4, expl_noise 0.126)" % tr.batch_size,
            "random_policy": {"train_return_mean": float(np.mean(rand_returns)) if rand_returns else None,
                              "train_length_mean": float(np.mean(rand_lengths)) if rand_lengths else None, "rounds": len(rand_returns)},
@@ -87,7 +93,7 @@ def train():
                        "last5_return": float(np.mean([r["performance/train_return"] for r in curve[-5:]])) if curve else None,
                        "first5_length": float(np.mean([r["performance/train_length"] for r in curve[:5]])) if curve else None,
                        "last5_length": float(np.mean([r["performance/train_length"] for r in curve[-5:]])) if curve else None}}
-    json.dump(out, open(os.path.join(OUT, "learning_curve.json"), "w"), indent=1)
+    json.dump(out, open(os.path.join(OUT, "learning_curve.json" if actor_type == "set" else "learning_curve_%s.json" % actor_type), "w"), indent=1)
     print(json.dumps(out["random_policy"]), json.dumps(out["summary"]), flush=True)
     return tr
 
@@ -145,7 +151,7 @@ def capture(names, driver, policy=None, steps=600, per_morph=8, tag=""):
 
 def main():
     tr = train()
-    if family != "hopper":
+    if family != "hopper" or actor_type != "set":
         return
     torch.save({k: v.detach().cpu() for k, v in tr.agent.actor.state_dict().items()}, os.path.join(OUT, "hopper_actor.pt"))
     A = mjcf.list_assets()
