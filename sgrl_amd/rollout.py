@@ -1,7 +1,7 @@
 """Batched rollout driver: the build's counterpart of the reference's per-env Python loop
 (`for i in range(num_envs_train): change_morphology; select_action; ...; envs.step`, reference trainer.py:173-236
 and the random-action warm-up loop trainer.py:90-138), with the same per-environment semantics but ONE engine
-launch and ONE batched actor forward (SET or SWAT) per time step, plus the replay push as a single gather to the learner rank.
+launch and ONE batched actor forward (SET, SWAT or SMP) per time step, plus the replay push as a single gather to the learner rank.
 """
 import ctypes
 
@@ -11,6 +11,7 @@ import torch
 from . import graph as G
 from .replay import DeviceReplayBuffer
 from .set_hip import HipSetActor
+from .smp_hip import HipSmpActor
 from .swat_hip import HipSwatActor
 from .vec_env import BatchedModularVecEnv
 
@@ -21,19 +22,24 @@ FUSED_INGEST = True      # False (tests): the learner writes a gathered block mo
 
 
 def hip_actor_class(policy):
-    """The batched HIP forward for `policy`'s type: `SEPolicy` -> `HipSetActor`, `StructurePolicy` (SWAT) -> `HipSwatActor`."""
+    """The batched HIP forward for `policy`'s type: `SEPolicy` -> `HipSetActor`, `StructurePolicy` (SWAT) -> `HipSwatActor`,
+    `ActorGraphPolicy` (SMP) in its published mode (td and bu) -> `HipSmpActor`."""
     from .set_policy import SEPolicy
+    from .smp_policy import ActorGraphPolicy
     from .swat_policy import StructurePolicy
     if isinstance(policy, SEPolicy):
         return HipSetActor
     if isinstance(policy, StructurePolicy):
         return HipSwatActor
-    raise NotImplementedError("the batched rollout has HIP actor forwards for SEPolicy (SET) and StructurePolicy (SWAT) only, "
-                              "not for %s" % type(policy).__name__)
+    if isinstance(policy, ActorGraphPolicy) and policy.td and policy.bu:
+        return HipSmpActor
+    raise NotImplementedError("the batched rollout has HIP actor forwards for SEPolicy (SET), StructurePolicy (SWAT) and "
+                              "ActorGraphPolicy (SMP, in the td and bu mode only), not for %s%s"
+                              % (type(policy).__name__, " with td and not bu" if isinstance(policy, ActorGraphPolicy) else ""))
 
 
 class Rollout(object):
-    """Environments of one rank + the shared actor (SET or SWAT)."""
+    """Environments of one rank + the shared actor (SET, SWAT or SMP)."""
 
     def __init__(self, env_names, envs_per_morph, policy=None, seed=0, device="cuda:0", rank=0, hold_weights=False, **env_kw):
         counts = [envs_per_morph] * len(env_names) if np.isscalar(envs_per_morph) else list(envs_per_morph)

@@ -9,9 +9,10 @@ dynamic batching is replaced by what it was a workaround for: the limbs of one t
 call of the shared module -- bottom-up from the deepest level, top-down from the root).  Message passing modes: `bu and td`
 (both ways, the published SMP) and `td` only -- the two the reference's `disable_fold` path can run (without top-down
 messages its forward raises at ModularActor.py:244, `torch.stack` of a list of None).
-Plain differentiable PyTorch -- this baseline has no HIP fast path (the SET model is the one the north star names); outputs
-are pinned to fixtures produced by executing the reference's own modules (tests/golden/smp_forward.npz,
-tools/capture_golden_smp.py).
+Plain differentiable PyTorch: this is what the TD3 updates run through.  Collection in the device loop runs the actor in its
+published mode (`bu and td`) through the batched HIP forward instead (smp_hip.HipSmpActor, csrc/smp_actor.hip; `_Tree` below
+stays the one source of its schedule); the `td`-only ablation and the critic have no HIP path.  Outputs are pinned to fixtures
+produced by executing the reference's own modules (tests/golden/smp_forward.npz, tools/capture_golden_smp.py).
 """
 import torch
 import torch.nn as nn

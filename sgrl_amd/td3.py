@@ -291,7 +291,8 @@ class Agent(nn.Module):
         self.args = args
         atype, ctype = getattr(args, "actor_type", "set"), getattr(args, "critic_type", "set")
         if atype not in ("set", "swat", "smp") or ctype not in ("set", "swat", "smp"):
-            raise NotImplementedError("actor / critic types 'set' (HIP fast path), 'swat' and 'smp' (PyTorch) are built; "
+            raise NotImplementedError("actor / critic types 'set', 'swat' and 'smp' are built (the actors with a batched HIP forward for collection, "
+                                      "smp in its td and bu mode; swat / smp updates in PyTorch); "
                                       "'mlp' is not (SURVEY 8 f4)")
         self.networks = {}
         from .smp_policy import ActorGraphPolicy, CriticGraphPolicy

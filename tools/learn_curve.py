@@ -11,9 +11,10 @@
     `sgrl_get_records` every 50 steps of environments whose episode has lasted at least 50 steps.  Writes
     gpurun_out/policy_states.npz (copied to tests/golden/ by hand).
 
-usage: learn_curve.py [train_seconds=480] [envs_per_morph=64] [seed=3] [hopper|walker] [set|swat]
-The fifth argument picks the actor and critic type (default set).  With swat the collection runs on the batched HIP SWAT
-forward (sgrl_amd/swat_hip.py), the updates eagerly through td3.Agent (no graphed updates), and only (1) runs.
+usage: learn_curve.py [train_seconds=480] [envs_per_morph=64] [seed=3] [hopper|walker] [set|swat|smp]
+The fifth argument picks the actor and critic type (default set).  With swat / smp the collection runs on the batched HIP SWAT /
+SMP forward (sgrl_amd/swat_hip.py, sgrl_amd/smp_hip.py), the updates eagerly through td3.Agent (no graphed updates), and only
+(1) runs.  smp is the published mode (td and bu) with max_children = the largest child count among the chosen morphologies.
 """
 import json
 import os
@@ -37,8 +38,8 @@ per = int(sys.argv[2]) if len(sys.argv) > 2 else 64
 seed = int(sys.argv[3]) if len(sys.argv) > 3 else 3
 family = sys.argv[4] if len(sys.argv) > 4 else "hopper"      # "walker" / "humanoid" / "cheetah" / "cwhh" (config 5): training only
 actor_type = sys.argv[5] if len(sys.argv) > 5 else "set"
-if actor_type not in ("set", "swat"):
-    raise SystemExit("actor type must be set or swat, not %r" % actor_type)
+if actor_type not in ("set", "swat", "smp"):
+    raise SystemExit("actor type must be set, swat or smp, not %r" % actor_type)
 HOPPERS = ["3d_hopper_3_shin", "3d_hopper_4_lower_shin", "3d_hopper_5_full"]
 
 
@@ -57,6 +58,9 @@ def train():
         names = sorted(n for n in mjcf.list_assets() if n not in held)
     else:
         names = sorted(n for n in mjcf.list_assets() if family in n)
+    if actor_type == "smp":         # the defaults (td = bu = False, max_children 3) are SET's: SMP needs both message passes and a slot per child
+        args.td = args.bu = True
+        args.max_children = max(list(mjcf.load_asset(n).parents).count(i) for n in names for i in range(mjcf.load_asset(n).num_limbs))
     tr = DeviceTrainer(names, per, args=args, seed=seed, device="cuda:0", max_buffer_size=400000,
                       graph_updates=actor_type == "set")
     env = tr.ro.env
