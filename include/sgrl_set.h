@@ -167,6 +167,20 @@ int sgrl_set_debug_stop_after(sgrl_set* s, int stage);
  * results to float32 rounding.  Default 2048 (SGRL_SET_SMALL_NODES in the environment); 0 = never; -1 restores the default.
  * Tests use it to run one input through both paths. */
 int sgrl_set_debug_small_nodes(sgrl_set* s, int nodes);
+/* The two-half forward.  Behind the embedding every kernel of the forward is local to an environment, so a batch on the fused
+ * tile-kernel path of 2048 nodes or more is cut at the environment boundary nearest half its nodes (on a multiple of 128 or 64 rows
+ * where one lies within N / 64 of the middle) and its halves run as two chains of the same kernels on the same scratch rows: the
+ * first half on the caller's stream, the second on the handle's side stream, issued one stage behind it and each with all its
+ * kernels on its own stream; both join the caller's stream before the forward returns.  One half's kernel tails, partial last tile
+ * rounds and launch gaps are filled by the other's kernels.  Per row the kernels, their order
+ * and their arithmetic are those of the single pass: the outputs are bit-identical.  Smaller batches, the other product forms, stream
+ * capture and the parity probes (sgrl_set_debug_stop_after) keep the single pass.  In the environment:
+ *   SGRL_SET_SPLIT=0  the single pass everywhere (A/B comparisons);
+ *   SGRL_SET_SPLIT=2  a half's sibling launches (U, the norm2 chain, the head's ng chain) go to the OTHER half's stream, as the
+ *                     single pass sends them to the side stream (measured slower: the halves then wait for each other);
+ *   SGRL_SET_SPLIT=3  as 2, and the second half starts only once the first half's first site kernel is done (slower as well).
+ * sgrl_set_last_split: nodes in the first half of the handle's last forward; 0 = it ran as a single pass. */
+int sgrl_set_last_split(const sgrl_set* s);
 /* Form of the 128 x 128 tile products (reference: plain f32 `F.linear`, subequivariant_attentions.py:90-151 / SEActor.py:82-125).
  * Both forms carry the f32 product on the 16-bit matrix cores and measure the same error against float64 as an f32 FMA chain
  * (tests/test_split_products_gpu.py):

@@ -517,6 +517,7 @@ struct GraphCfg {
   std::vector<int32_t> key_i;   // n_morph | L[] | count[] | trav[]
   std::vector<float> key_f;     // rel[]
   int n_env = 0, N = 0, n_morph = 0, TM = 0, Lmax = 0;
+  int split_env = 0, split_node = 0;   // the environment boundary nearest N / 2 (pick_split): where the two-half forward cuts the batch
   int32_t *d_node_env = nullptr, *d_node_limb = nullptr, *d_node_mnode = nullptr, *d_trav = nullptr;
   int32_t *d_env_off = nullptr, *d_env_L = nullptr, *d_env_relb = nullptr, *d_m_off = nullptr, *d_m_L = nullptr;
   float *d_rel = nullptr, *d_relb = nullptr;
@@ -533,6 +534,8 @@ struct sgrl_set {
   bool have_w = false, have_graph = false;
   // current batch structure (copied out of the cache entry by use_cfg)
   int n_env = 0, N = 0, n_morph = 0, TM = 0, Lmax = 0;
+  int split_env = 0, split_node = 0;   // first environment / node of the second half (two-half forward, run_forward)
+  int last_split = 0;                  // nodes the first half of the last forward held; 0: it ran as a single pass (sgrl_set_last_split)
   int32_t *d_node_env = nullptr, *d_node_limb = nullptr, *d_node_mnode = nullptr, *d_trav = nullptr;
   int32_t *d_env_off = nullptr, *d_env_L = nullptr, *d_env_relb = nullptr, *d_m_off = nullptr, *d_m_L = nullptr;
   float *d_rel = nullptr, *d_relb = nullptr;
@@ -581,6 +584,8 @@ struct sgrl_set {
   // side stream for the GEMM chains that do not depend on each other (their epilogues / tile tails overlap)
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_l3 = nullptr;
+  // two-half forward: the second half's fork / join pair, its start behind the first half and the merge into the caller's stream
+  hipEvent_t ev_fork_b = nullptr, ev_join_b = nullptr, ev_split = nullptr, ev_merge = nullptr;
   std::vector<hipStream_t> side_ok_for;   // caller streams `side` has been measured to overlap (stream_pick.h)
   int side_picks = 0;                     // measurements spent so far (bounded: a caller hopping between streams must not pay forever)
   const float* W(int slot) const { return w + off[slot]; }
@@ -611,6 +616,22 @@ int upload(T** dst, const std::vector<T>& v) {
   return 0;
 }
 
+// Where the two-half forward cuts a batch: the environment boundary whose node prefix sum is nearest N / 2.  Among the boundaries
+// within N / 64 of the middle one on a multiple of 128 rows (the product tiles) or 64 rows (the chain kernels' workgroups) is
+// preferred: the first half then ends on a full tile.  env 0 / node 0: a single environment, nothing to cut.
+void pick_split(const std::vector<int32_t>& env_off, int N, int* env_out, int* node_out) {
+  int best = 0, best_rank = -1;
+  int64_t best_dist = 0;
+  for (size_t e = 1; e < env_off.size(); e++) {
+    const int n = env_off[e];
+    const int64_t dist = std::abs(2 * (int64_t)n - N);        // twice the distance to N / 2
+    const int rank = 2 * dist > N / 16 ? 0 : (n % 128 == 0 ? 3 : n % 64 == 0 ? 2 : 1);
+    if (best_rank < 0 || rank > best_rank || (rank == best_rank && dist < best_dist)) { best = (int)e; best_rank = rank; best_dist = dist; }
+  }
+  *env_out = best;
+  *node_out = best ? env_off[best] : 0;
+}
+
 // point the handle at a cached batch structure; (re)carve the shared workspace for its node count
 int use_cfg(sgrl_set* s, GraphCfg* c) {
   const int64_t N = c->N;
@@ -632,6 +653,7 @@ int use_cfg(sgrl_set* s, GraphCfg* c) {
     s->carved_N = c->N;
   }
   s->n_env = c->n_env; s->N = c->N; s->n_morph = c->n_morph; s->TM = c->TM; s->Lmax = c->Lmax;
+  s->split_env = c->split_env; s->split_node = c->split_node;
   s->d_node_env = c->d_node_env; s->d_node_limb = c->d_node_limb; s->d_node_mnode = c->d_node_mnode; s->d_trav = c->d_trav;
   s->d_env_off = c->d_env_off; s->d_env_L = c->d_env_L; s->d_env_relb = c->d_env_relb; s->d_m_off = c->d_m_off; s->d_m_L = c->d_m_L;
   s->d_rel = c->d_rel; s->d_relb = c->d_relb;
@@ -869,6 +891,7 @@ int launch_chain_ng(hipStream_t st, const float* A, int lda, int K1, const float
 // splitting every k-tile); the epilogue fusions of the big path become the small kernels below.  Scratch: the attention's
 // qkv | vg block (contiguous, 1536 floats per node), idle whenever these run.
 constexpr int kSmallNodesDefault = 2048;
+constexpr int kSplitMinNodes = 2048;    // the two-half forward (run_forward) starts here: the tile-kernel path's own size, whatever the tests set the threshold above to
 int small_nodes() {
   return kSmallNodesDefault;       // (tests move the threshold per handle: sgrl_set_debug_small_nodes)
 }
@@ -994,14 +1017,6 @@ int run_forward(sgrl_set* s, const float* obs, int obs_ld, float* act, int act_l
     s->packed_form = want_words ? SGRL_SET_FORM_F16X3 : SGRL_SET_FORM_BF16X6;
     if (s->hold) (void)hipEventRecord(s->ev_pack, st);
   }
-  // cat = [invariants | ng] is double-buffered in the fused form: norm2 writes the next ng into the OTHER buffer, so that the two
-  // readers of [inv | ng] behind the feed-forward site (linear1 -> linear2 -> norm2 on the side stream, linear3 -> linear4 on the
-  // main one) never wait for each other
-  float* catc = s->cat;
-  float* cato = s->cat2;
-  s->cat_cur = catc;
-  float* ng = catc + 128;
-  int rc = SGRL_OK;
   // back-to-back products as one kernel each: the tile path in its two-piece form on bound (pre-split) weights
   const bool chain = !small && chain_enabled() && gemm_use_split() && g_gemm.form == SGRL_SET_FORM_F16X3;
   // linear3 -> linear4 -> contraction (-> vector-stream update) as ONE kernel exists (chain_f16.h, EPI_EQUIV; tests hold it against
@@ -1012,22 +1027,28 @@ int run_forward(sgrl_set* s, const float* obs, int obs_ld, float* act, int act_l
   // than its two launches (profiles/r4_chain_lab_ffn.txt): not part of the forward; the head folded through linear2_m and the fused
   // residual update are (the A/B switches of rounds 4-5 are gone, their numbers are in LAB_LOG)
   constexpr bool chain_eq = false, head_fold = true, fuse_update = true;
-  float* const scratch = s->qkv;      // small path: [N, 576] Gram triangle / [N, 1024] per-node matrices (spans qkv | vg)
-#define G(...) do { rc = small ? small_gemm(st, __VA_ARGS__) : launch_gemm(st, __VA_ARGS__); if (rc != SGRL_OK) return rc; } while (0)
-  auto gram_gemm = [&](const float* W_, const float* b_, float* C_, int ldc_, int N_) -> int {
-    if (!small) return launch_gemm_gram(st, s->zc, W_, b_, C_, ldc_, N, N_, s->fn);
-    hipLaunchKernelGGL(k_gram576, dim3((N + 3) / 4), dim3(256), 0, st, s->zc, s->d_tri, scratch, s->fn, N);
-    return small_gemm(st, scratch, GK, W_, GK, b_, C_, ldc_, N, N_, GK, EPI_RELU);
+  // Everything behind the embedding is local to an environment (row-wise products and norms, attention per environment), so the
+  // encoder and the head run on any range of whole environments: a Part.  The forward is either one Part (the whole batch) or, on
+  // the fused tile path from kSplitMinNodes nodes on, two halves cut at an environment boundary (pick_split) that walk the same
+  // stages on the same scratch rows, the first half on the caller's stream and the second on the side stream, issued one stage
+  // behind it: each half's kernel tails, partial last tile rounds and launch gaps are filled by the other half's kernels.  A half
+  // keeps ALL its kernels on its own stream, the siblings of the single pass (U, the norm2 chain, the head's ng chain) included:
+  // the other half is the independent work in flight, and no event ties the halves together between the embedding and the end.
+  // Within a half the kernels, their order and their arithmetic are those of the single pass: every row's result is bit-identical.
+  // SGRL_SET_SPLIT=0 keeps the single pass; the forms that measured slower stay selectable (include/sgrl_set.h):
+  // SGRL_SET_SPLIT=2 puts a half's siblings on the OTHER half's stream, SGRL_SET_SPLIT=3 also starts the second half only when the
+  // first half's first site kernel is done.
+  struct Part {
+    int r0, M, e0, ne;                 // first node / nodes / first environment / environments
+    hipStream_t st, sd;                // chain stream, stream of the sibling launches
+    hipEvent_t ev_fork, ev_join;
+    float *catc, *cato;                // the [inv | ng] buffer in use and the other one (whole-batch base pointers)
+    hipEvent_t ev_site0;               // recorded on `st` behind the first site kernel (null: not wanted)
   };
-  // linear4 / linear2_m + equivariant contraction; linear2 + residual + LayerNorm
-  auto equiv_gemm = [&](const float* A_, const float* W_, const float* b_) -> int {
-    if (!small) return launch_gemm_equiv(st, A_, 256, W_, 256, b_, N, 256, s->fn, s->z2, s->mat);
-    const int r = small_gemm(st, A_, 256, W_, 256, b_, scratch, 1024, N, 1024, 256, EPI_ROWDIV, s->fn);
-    if (r != SGRL_OK) return r;
-    hipLaunchKernelGGL(k_zmat_perm, dim3(N), dim3(128), 0, st, s->z2, scratch, s->mat);
-    return SGRL_OK;
-  };
-#define GG(W_, b_, C_, ldc_, N_) do { rc = gram_gemm(W_, b_, C_, ldc_, N_); if (rc != SGRL_OK) return rc; } while (0)
+  // cat = [invariants | ng] is double-buffered in the fused form: norm2 writes the next ng into the OTHER buffer, so that the two
+  // readers of [inv | ng] behind the feed-forward site (linear1 -> linear2 -> norm2 on the side stream, linear3 -> linear4 on the
+  // main one) never wait for each other
+  s->cat_cur = s->cat;
   // proj + gram site: Z (and Z2) = X . [Wp; Wq]^T on the matrix cores (stacked, zero-padded weights), then the packed
   // Gram triangle per node
   auto site_w = [&](int site) -> const float* {   // site 6 (the head, Cpad 144) is last
@@ -1043,146 +1064,215 @@ int run_forward(sgrl_set* s, const float* obs, int obs_ld, float* act, int act_l
     hipLaunchKernelGGL(k_stack_proj, dim3(36), dim3(256), 0, st, s->W(SGRL_SET_GGPROJ), critic ? (const float*)nullptr : s->W(SGRL_SET_GPROJ), 136, OGLD, sw(6));
     s->stack_dirty = false;
   }
-  // projection site: Z (and Z2) = X . [Wp; Wq]^T on the matrix cores (stacked, zero-padded weights), written straight into
-  // the compact rows zc / z2 the Gram GEMM and the equivariant epilogues read
-  auto pg = [&](const float* X, int ldx, int K, int site, float* z2) -> int {
-    if (K % 16 != 0 || (ldx & 3)) return sfail(SGRL_ERR_ARG, "projection: K must be a multiple of 16 and rows 16-byte aligned");
-    if (small) {          // rows 0..29 / 32..61 of the stacked operand: two narrow products (columns 30, 31 hold gdir)
-      int r = small_gemm(st, X, ldx, site_w(site), K, nullptr, s->zc, ZD, N3, 30, K);
-      if (r == SGRL_OK && z2) r = small_gemm(st, X, ldx, site_w(site) + (size_t)32 * K, K, nullptr, z2, ZD, N3, 30, K);
-      return r;
-    }
-    GemmArgs a{X, ldx, site_w(site), K, nullptr, s->zc, ZD, N3, z2 ? 64 : 32, K, EPI_ZSPLIT, nullptr, z2, ZD};
-    if (g_gemm.form == SGRL_SET_FORM_F16X3 && gemm_use_split())      // 128 x 64 tiles, four waves, W pre-split
-      hipLaunchKernelGGL(kProjH, dim3(((a.M + 127) / 128) * ((a.N + 63) / 64)), dim3(256), kProjHLds, st, with_words(a));
-    else
-      GemmKernels<EPI_ZSPLIT>::launch(st, a);
-    return SGRL_OK;
-  };
+  constexpr int kStages = 4 * SGRL_SET_LAYERS + 2, kStop = 1;
+  // one stage of a part: 4 l + (0: U || site A -> qkv, 1: attention, 2: site F, 3: norm2 chain || linear3 -> linear4 -> k_equiv) of
+  // encoder layer l, then the head's (final norm, ng chain || site) and (linear1_m -> linear2_m -> actions).  kStop: a parity probe ends the forward here
+  auto stage = [&](Part& p, int k) -> int {
+    const int N = p.M, N3 = 3 * p.M, lnb = (N + 3) / 4;
+    hipStream_t st = p.st, sd = p.sd;
+    const size_t r = (size_t)p.r0;
+    float *const g = s->g + 384 * r, *const zc = s->zc + 96 * r, *const z2 = s->z2 + 96 * r, *const fn = s->fn + r,
+          *const h256 = s->h256 + 256 * r, *const qkv = s->qkv + 768 * r, *const vg = s->vg + 768 * r, *const g1 = s->g1 + 384 * r,
+          *const mat = s->mat + 96 * r, *const t256 = s->t256 + 256 * r, *const t256b = s->t256b + 256 * r,
+          *const t128a = s->t128a + 128 * r, *const t128b = s->t128b + 128 * r, *const delta = s->delta + 128 * r,
+          *const outg = s->outg + 3 * OGLD * r, *const outng = s->outng + 160 * r, *const cat = s->cat + 256 * r,
+          *const cat2 = s->cat2 + 256 * r;
+    float *const catc = p.catc + 256 * r, *const cato = p.cato + 256 * r, *const ng = catc + 128;
+    const NodeTab ntp{nt.node_env + r, nt.node_limb + r, nt.node_mnode + r, nt.trav, nt.TM};
+    auto fork = [&]() { if (!one_stream && sd != st) { (void)hipEventRecord(p.ev_fork, st); (void)hipStreamWaitEvent(sd, p.ev_fork, 0); } };
+    auto join = [&]() { if (!one_stream && sd != st) { (void)hipEventRecord(p.ev_join, sd); (void)hipStreamWaitEvent(st, p.ev_join, 0); } };
+    int rc = SGRL_OK;
+    float* const scratch = qkv;         // small path: [N, 576] Gram triangle / [N, 1024] per-node matrices (spans qkv | vg)
+#define G(...) do { rc = small ? small_gemm(st, __VA_ARGS__) : launch_gemm(st, __VA_ARGS__); if (rc != SGRL_OK) return rc; } while (0)
+    auto gram_gemm = [&](const float* W_, const float* b_, float* C_, int ldc_, int N_) -> int {
+      if (!small) return launch_gemm_gram(st, zc, W_, b_, C_, ldc_, N, N_, fn);
+      hipLaunchKernelGGL(k_gram576, dim3((N + 3) / 4), dim3(256), 0, st, zc, s->d_tri, scratch, fn, N);
+      return small_gemm(st, scratch, GK, W_, GK, b_, C_, ldc_, N, N_, GK, EPI_RELU);
+    };
+    // linear4 / linear2_m + equivariant contraction; linear2 + residual + LayerNorm
+    auto equiv_gemm = [&](const float* A_, const float* W_, const float* b_) -> int {
+      if (!small) return launch_gemm_equiv(st, A_, 256, W_, 256, b_, N, 256, fn, z2, mat);
+      const int r_ = small_gemm(st, A_, 256, W_, 256, b_, scratch, 1024, N, 1024, 256, EPI_ROWDIV, fn);
+      if (r_ != SGRL_OK) return r_;
+      hipLaunchKernelGGL(k_zmat_perm, dim3(N), dim3(128), 0, st, z2, scratch, mat);
+      return SGRL_OK;
+    };
+#define GG(W_, b_, C_, ldc_, N_) do { rc = gram_gemm(W_, b_, C_, ldc_, N_); if (rc != SGRL_OK) return rc; } while (0)
+    // projection site: Z (and Z2) = X . [Wp; Wq]^T on the matrix cores (stacked, zero-padded weights), written straight into
+    // the compact rows zc / z2 the Gram GEMM and the equivariant epilogues read
+    auto pg = [&](const float* X, int ldx, int K, int site, float* z2_) -> int {
+      if (K % 16 != 0 || (ldx & 3)) return sfail(SGRL_ERR_ARG, "projection: K must be a multiple of 16 and rows 16-byte aligned");
+      if (small) {          // rows 0..29 / 32..61 of the stacked operand: two narrow products (columns 30, 31 hold gdir)
+        int r_ = small_gemm(st, X, ldx, site_w(site), K, nullptr, zc, ZD, N3, 30, K);
+        if (r_ == SGRL_OK && z2_) r_ = small_gemm(st, X, ldx, site_w(site) + (size_t)32 * K, K, nullptr, z2_, ZD, N3, 30, K);
+        return r_;
+      }
+      GemmArgs a{X, ldx, site_w(site), K, nullptr, zc, ZD, N3, z2_ ? 64 : 32, K, EPI_ZSPLIT, nullptr, z2_, ZD};
+      if (g_gemm.form == SGRL_SET_FORM_F16X3 && gemm_use_split())      // 128 x 64 tiles, four waves, W pre-split
+        hipLaunchKernelGGL(kProjH, dim3(((a.M + 127) / 128) * ((a.N + 63) / 64)), dim3(256), kProjHLds, st, with_words(a));
+      else
+        GemmKernels<EPI_ZSPLIT>::launch(st, a);
+      return SGRL_OK;
+    };
 #define PG(...) do { rc = pg(__VA_ARGS__); if (rc != SGRL_OK) return rc; } while (0)
-  const int lnb = (N + 3) / 4;
 #define GS(...) do { rc = small ? small_gemm(sd, __VA_ARGS__) : launch_gemm(sd, __VA_ARGS__); if (rc != SGRL_OK) return rc; } while (0)
-  for (int l = 0; l < SGRL_SET_LAYERS; l++) {
-    // --- attention ---
-    fork();
-    GS(s->g, D, s->WL(l, SGRL_SET_VG_W), D, nullptr, s->vg, 256, N3, 256, D);          // U = g . (Wgo_h Wvg_h)^T, both heads
-    if (chain) {
-      rc = launch_site(st, s->g, D, D, site_w(2 * l), s->zc, nullptr, s->fn, s->WL(l, SGRL_SET_A_LG1_W), s->WL(l, SGRL_SET_A_LG1_B), 256,
-                       s->WL(l, SGRL_SET_A_LG2_W), s->WL(l, SGRL_SET_A_LG2_B), catc, 256, N);
+    const int l = k / 4;
+    if (k < 4 * SGRL_SET_LAYERS && k % 4 == 0) {
+      // --- attention ---
+      fork();
+      GS(g, D, s->WL(l, SGRL_SET_VG_W), D, nullptr, vg, 256, N3, 256, D);          // U = g . (Wgo_h Wvg_h)^T, both heads
+      if (chain) {
+        rc = launch_site(st, g, D, D, site_w(2 * l), zc, nullptr, fn, s->WL(l, SGRL_SET_A_LG1_W), s->WL(l, SGRL_SET_A_LG1_B), 256,
+                         s->WL(l, SGRL_SET_A_LG2_W), s->WL(l, SGRL_SET_A_LG2_B), catc, 256, N);
+        if (rc != SGRL_OK) return rc;
+        if (l == 0 && p.ev_site0) (void)hipEventRecord(p.ev_site0, st);
+      } else {
+        PG(g, D, D, 2 * l, nullptr);
+        GG(s->WL(l, SGRL_SET_A_LG1_W), s->WL(l, SGRL_SET_A_LG1_B), h256, 256, 256);
+        G(h256, 256, s->WL(l, SGRL_SET_A_LG2_W), 256, s->WL(l, SGRL_SET_A_LG2_B), catc, 256, N, 128, 256);
+      }
+      G(catc, 256, s->WL(l, SGRL_SET_QKV_W), 256, s->WL(l, SGRL_SET_QKV_B), qkv, 768, N, 768, 256, EPI_ROWDIV, fn);
+      join();
+    } else if (k < 4 * SGRL_SET_LAYERS && k % 4 == 1) {
+      // (k_attention finds its rows through the environment table: whole-batch base pointers)
+      const EnvTab etp{et.env_off + p.e0, et.env_L + p.e0, et.env_relb + p.e0};
+      hipLaunchKernelGGL(k_attention, dim3(p.ne), dim3(256), 0, st, s->qkv, s->vg, s->gdir, s->d_relb, etp, l == 0 ? 1 : 0,
+                         s->WL(l, SGRL_SET_NGOUT_B), s->WL(l, SGRL_SET_A_GD), s->stop_after == 2 * l ? s->delta : (float*)nullptr,
+                         s->g1, p.catc + 128, 256, s->WL(l, SGRL_SET_N1_W), s->WL(l, SGRL_SET_N1_B));
+      if (s->stop_after == 2 * l) return kStop;      // probe: g1 = attention's vector output, delta = its scalar output
+    } else if (k < 4 * SGRL_SET_LAYERS && k % 4 == 2) {
+      // --- equivariant feed-forward ---
+      if (chain) {
+        rc = launch_site(st, g1, D, D, site_w(2 * l + 1), zc, z2, fn, s->WL(l, SGRL_SET_F_LG1_W), s->WL(l, SGRL_SET_F_LG1_B), 256,
+                         s->WL(l, SGRL_SET_F_LG2_W), s->WL(l, SGRL_SET_F_LG2_B), catc, 256, N);
+        if (rc != SGRL_OK) return rc;
+      } else {
+        PG(g1, D, D, 2 * l + 1, z2);
+        GG(s->WL(l, SGRL_SET_F_LG1_W), s->WL(l, SGRL_SET_F_LG1_B), h256, 256, 256);
+        G(h256, 256, s->WL(l, SGRL_SET_F_LG2_W), 256, s->WL(l, SGRL_SET_F_LG2_B), catc, 256, N, 128, 256);
+      }
+    } else if (k < 4 * SGRL_SET_LAYERS) {
+      fork();
+      if (chain) {
+        // side: linear1 -> ReLU -> linear2 -> / fn -> residual + norm2, the new ng into the other buffer; main: linear3 -> ReLU ->
+        // linear4 -> contraction with z, then the update of the vector stream
+        rc = launch_chain_ln(sd, catc, 256, 256, s->WL(l, SGRL_SET_L1_W), s->WL(l, SGRL_SET_L1_B), s->WL(l, SGRL_SET_L2_W), s->WL(l, SGRL_SET_L2_B),
+                             fn, ng, 256, s->WL(l, SGRL_SET_N2_W), s->WL(l, SGRL_SET_N2_B), N, cato + 128);
+        if (rc == SGRL_OK && chain_eq) {
+          rc = launch_chain_equiv(st, catc, 256, 256, s->WL(l, SGRL_SET_L3_W), s->WL(l, SGRL_SET_L3_B), s->WL(l, SGRL_SET_L4_W), s->WL(l, SGRL_SET_L4_B),
+                                  fn, z2, mat, N, fuse_update ? g : (float*)nullptr, g1, s->WL(l, SGRL_SET_L5_W),
+                                  l == SGRL_SET_LAYERS - 1 ? outg : (float*)nullptr);
+        } else if (rc == SGRL_OK) {
+          rc = launch_gemm(st, catc, 256, s->WL(l, SGRL_SET_L3_W), 256, s->WL(l, SGRL_SET_L3_B), t256, 256, N, 256, 256, EPI_RELU);
+          if (rc == SGRL_OK) rc = equiv_gemm(t256, s->WL(l, SGRL_SET_L4_W), s->WL(l, SGRL_SET_L4_B));
+        }
+        if (rc != SGRL_OK) return rc;
+        if (!(chain_eq && fuse_update))
+          hipLaunchKernelGGL(k_equiv, dim3((N + 7) / 8), dim3(128), 0, st, mat, s->WL(l, SGRL_SET_L5_W), g1, g,
+                             l == SGRL_SET_LAYERS - 1 ? outg : (float*)nullptr, N);
+        join();
+        std::swap(p.catc, p.cato);
+        s->cat_cur = p.catc;
+        if (s->stop_after == 2 * l + 1) return kStop;  // probe: g / ng (= the current cat[:, 128:]) are this layer's outputs
+        return SGRL_OK;
+      }
+      GS(cat, 256, s->WL(l, SGRL_SET_L1_W), 256, s->WL(l, SGRL_SET_L1_B), t256b, 256, N, 256, 256, EPI_RELU);
+      G(cat, 256, s->WL(l, SGRL_SET_L3_W), 256, s->WL(l, SGRL_SET_L3_B), t256, 256, N, 256, 256, EPI_RELU);
+      // linear2 carries the scalar stream's second residual + norm2 in its epilogue (ng rewritten in place): it must not start
+      // before linear3 -- the other reader of cat = [inv | ng] -- is done
+      if (!one_stream) {
+        (void)hipEventRecord(s->ev_l3, st);
+        (void)hipStreamWaitEvent(sd, s->ev_l3, 0);
+      }
+      if (small) {
+        rc = small_gemm(st, t256b, 256, s->WL(l, SGRL_SET_L2_W), 256, s->WL(l, SGRL_SET_L2_B), delta, 128, N, 128, 256, EPI_ROWDIV, fn);
+        if (rc != SGRL_OK) return rc;
+        hipLaunchKernelGGL(k_add_ln, dim3(lnb), dim3(256), 0, st, ng, 256, delta, 128, s->WL(l, SGRL_SET_N2_W),
+                           s->WL(l, SGRL_SET_N2_B), (float*)nullptr, 0, ng, 256, N);
+      } else {
+        rc = launch_gemm_ln(sd, t256b, 256, s->WL(l, SGRL_SET_L2_W), 256, s->WL(l, SGRL_SET_L2_B), N, 256, fn, ng, 256,
+                            s->WL(l, SGRL_SET_N2_W), s->WL(l, SGRL_SET_N2_B));
+        if (rc != SGRL_OK) return rc;
+      }
+      rc = equiv_gemm(t256, s->WL(l, SGRL_SET_L4_W), s->WL(l, SGRL_SET_L4_B));
       if (rc != SGRL_OK) return rc;
+      hipLaunchKernelGGL(k_equiv, dim3((N + 7) / 8), dim3(128), 0, st, mat, s->WL(l, SGRL_SET_L5_W), g1, g,
+                         l == SGRL_SET_LAYERS - 1 ? outg : (float*)nullptr, N);
+      join();
+      if (s->stop_after == 2 * l + 1) return kStop;  // probe: g / ng (= cat[:, 128:]) are this layer's outputs
+    } else if (k == 4 * SGRL_SET_LAYERS) {
+      // final norm -> outng[:, 17:145]; head
+      hipLaunchKernelGGL(k_add_ln, dim3(lnb), dim3(256), 0, st, ng, 256, (const float*)nullptr, 0, s->W(SGRL_SET_FNORM_W),
+                         s->W(SGRL_SET_FNORM_B), (float*)nullptr, 0, outng + ngf, 160, N);
+      float* const hd = chain ? cato : cat2;     // the head's [l2g | l2ng] rows: the buffer the last norm2 did not write
+      fork();
+      if (chain) {
+        rc = launch_chain_ng(sd, outng, 160, 160, s->W(SGRL_SET_L1NG_W), s->W(SGRL_SET_L1NG_B), s->W(SGRL_SET_L2NG_W), s->W(SGRL_SET_L2NG_B),
+                             hd + 128, 256, N);
+        if (rc == SGRL_OK)
+          rc = launch_site(st, outg, OGLD, OGLD, site_w(6), zc, critic ? (float*)nullptr : z2, fn, s->W(SGRL_SET_L1G_W),
+                           s->W(SGRL_SET_L1G_B), 128, s->W(SGRL_SET_L2G_W), s->W(SGRL_SET_L2G_B), hd, 256, N);
+        if (rc != SGRL_OK) return rc;
+      } else {
+        GS(outng, 160, s->W(SGRL_SET_L1NG_W), 160, s->W(SGRL_SET_L1NG_B), t128b, D, N, D, 160, EPI_RELU);
+        GS(t128b, D, s->W(SGRL_SET_L2NG_W), D, s->W(SGRL_SET_L2NG_B), cat2 + 128, 256, N, D, D);
+        PG(outg, OGLD, OGLD, 6, critic ? (float*)nullptr : z2);
+        GG(s->W(SGRL_SET_L1G_W), s->W(SGRL_SET_L1G_B), t128a, D, D);
+        G(t128a, D, s->W(SGRL_SET_L2G_W), D, s->W(SGRL_SET_L2G_B), cat2, 256, N, D, D);
+      }
+      join();
+    } else if (critic) {
+      float* const hd = chain ? cato : cat2;
+      // slots reused by the critic head: DECG = decoder_ng.weight [256], L1M_B = decoder_ng.bias [1]
+      hipLaunchKernelGGL(k_q_head, dim3((N + 3) / 4), dim3(256), 0, st, hd, s->W(SGRL_SET_DECG), s->W(SGRL_SET_L1M_B), fn,
+                         ntp, act, act_ld, N);
     } else {
-      PG(s->g, D, D, 2 * l, nullptr);
-      GG(s->WL(l, SGRL_SET_A_LG1_W), s->WL(l, SGRL_SET_A_LG1_B), s->h256, 256, 256);
-      G(s->h256, 256, s->WL(l, SGRL_SET_A_LG2_W), 256, s->WL(l, SGRL_SET_A_LG2_B), catc, 256, N, 128, 256);
-    }
-    G(catc, 256, s->WL(l, SGRL_SET_QKV_W), 256, s->WL(l, SGRL_SET_QKV_B), s->qkv, 768, N, 768, 256, EPI_ROWDIV, s->fn);
-    join();
-    hipLaunchKernelGGL(k_attention, dim3(s->n_env), dim3(256), 0, st, s->qkv, s->vg, s->gdir, s->d_relb, et, l == 0 ? 1 : 0,
-                       s->WL(l, SGRL_SET_NGOUT_B), s->WL(l, SGRL_SET_A_GD), s->stop_after == 2 * l ? s->delta : (float*)nullptr,
-                       s->g1, ng, 256, s->WL(l, SGRL_SET_N1_W), s->WL(l, SGRL_SET_N1_B));
-    if (s->stop_after == 2 * l) return SGRL_OK;      // probe: g1 = attention's vector output, delta = its scalar output
-    // --- equivariant feed-forward ---
-    if (chain) {
-      rc = launch_site(st, s->g1, D, D, site_w(2 * l + 1), s->zc, s->z2, s->fn, s->WL(l, SGRL_SET_F_LG1_W), s->WL(l, SGRL_SET_F_LG1_B), 256,
-                       s->WL(l, SGRL_SET_F_LG2_W), s->WL(l, SGRL_SET_F_LG2_B), catc, 256, N);
-      if (rc != SGRL_OK) return rc;
-    } else {
-      PG(s->g1, D, D, 2 * l + 1, s->z2);
-      GG(s->WL(l, SGRL_SET_F_LG1_W), s->WL(l, SGRL_SET_F_LG1_B), s->h256, 256, 256);
-      G(s->h256, 256, s->WL(l, SGRL_SET_F_LG2_W), 256, s->WL(l, SGRL_SET_F_LG2_B), catc, 256, N, 128, 256);
-    }
-    fork();
-    if (chain) {
-      // side: linear1 -> ReLU -> linear2 -> / fn -> residual + norm2, the new ng into the other buffer; main: linear3 -> ReLU ->
-      // linear4 -> contraction with z, then the update of the vector stream
-      rc = launch_chain_ln(sd, catc, 256, 256, s->WL(l, SGRL_SET_L1_W), s->WL(l, SGRL_SET_L1_B), s->WL(l, SGRL_SET_L2_W), s->WL(l, SGRL_SET_L2_B),
-                           s->fn, ng, 256, s->WL(l, SGRL_SET_N2_W), s->WL(l, SGRL_SET_N2_B), N, cato + 128);
-      if (rc == SGRL_OK && chain_eq) {
-        rc = launch_chain_equiv(st, catc, 256, 256, s->WL(l, SGRL_SET_L3_W), s->WL(l, SGRL_SET_L3_B), s->WL(l, SGRL_SET_L4_W), s->WL(l, SGRL_SET_L4_B),
-                                s->fn, s->z2, s->mat, N, fuse_update ? s->g : (float*)nullptr, s->g1, s->WL(l, SGRL_SET_L5_W),
-                                l == SGRL_SET_LAYERS - 1 ? s->outg : (float*)nullptr);
-      } else if (rc == SGRL_OK) {
-        rc = launch_gemm(st, catc, 256, s->WL(l, SGRL_SET_L3_W), 256, s->WL(l, SGRL_SET_L3_B), s->t256, 256, N, 256, 256, EPI_RELU);
-        if (rc == SGRL_OK) rc = equiv_gemm(s->t256, s->WL(l, SGRL_SET_L4_W), s->WL(l, SGRL_SET_L4_B));
+      float* const hd = chain ? cato : cat2;
+      const bool folded = !small && s->live && s->l2mf_w && head_fold;
+      if (folded) {
+        // decoder_g folded through linear2_m: the 1024-wide product and its contraction collapse into a 32-wide product
+        G(hd, 256, s->W(SGRL_SET_L1M_W), 256, s->W(SGRL_SET_L1M_B), t256, 256, N, 256, 256, EPI_RELU);
+        G(t256, 256, s->l2mf_w, 256, s->l2mf_b, mat, 32, N, 32, 256, EPI_ROWDIV, fn);
+        hipLaunchKernelGGL(k_head_out2, dim3((N + 3) / 4), dim3(128), 0, st, mat, z2, obs, obs_ld, ntp, act, act_ld, max_action, N);
+      } else if (chain && chain_eq) {
+        rc = launch_chain_equiv(st, hd, 256, 256, s->W(SGRL_SET_L1M_W), s->W(SGRL_SET_L1M_B), s->W(SGRL_SET_L2M_W), s->W(SGRL_SET_L2M_B), fn, z2,
+                                mat, N);
+      } else {
+        G(hd, 256, s->W(SGRL_SET_L1M_W), 256, s->W(SGRL_SET_L1M_B), t256, 256, N, 256, 256, EPI_RELU);
+        rc = equiv_gemm(t256, s->W(SGRL_SET_L2M_W), s->W(SGRL_SET_L2M_B));
       }
       if (rc != SGRL_OK) return rc;
-      if (!(chain_eq && fuse_update))
-        hipLaunchKernelGGL(k_equiv, dim3((N + 7) / 8), dim3(128), 0, st, s->mat, s->WL(l, SGRL_SET_L5_W), s->g1, s->g,
-                           l == SGRL_SET_LAYERS - 1 ? s->outg : (float*)nullptr, N);
-      join();
-      std::swap(catc, cato);
-      ng = catc + 128;
-      s->cat_cur = catc;
-      if (s->stop_after == 2 * l + 1) return SGRL_OK;  // probe: g / ng (= the current cat[:, 128:]) are this layer's outputs
-      continue;
+      if (!folded)
+        hipLaunchKernelGGL(k_head_out, dim3((N + 3) / 4), dim3(128), 0, st, mat, s->W(SGRL_SET_DECG), obs, obs_ld, ntp,
+                           act, act_ld, max_action, N);
     }
-    GS(s->cat, 256, s->WL(l, SGRL_SET_L1_W), 256, s->WL(l, SGRL_SET_L1_B), s->t256b, 256, N, 256, 256, EPI_RELU);
-    G(s->cat, 256, s->WL(l, SGRL_SET_L3_W), 256, s->WL(l, SGRL_SET_L3_B), s->t256, 256, N, 256, 256, EPI_RELU);
-    // linear2 carries the scalar stream's second residual + norm2 in its epilogue (ng rewritten in place): it must not start
-    // before linear3 -- the other reader of cat = [inv | ng] -- is done
-    if (!one_stream) {
-      (void)hipEventRecord(s->ev_l3, st);
-      (void)hipStreamWaitEvent(sd, s->ev_l3, 0);
-    }
-    if (small) {
-      rc = small_gemm(st, s->t256b, 256, s->WL(l, SGRL_SET_L2_W), 256, s->WL(l, SGRL_SET_L2_B), s->delta, 128, N, 128, 256, EPI_ROWDIV, s->fn);
-      if (rc != SGRL_OK) return rc;
-      hipLaunchKernelGGL(k_add_ln, dim3(lnb), dim3(256), 0, st, ng, 256, s->delta, 128, s->WL(l, SGRL_SET_N2_W),
-                         s->WL(l, SGRL_SET_N2_B), (float*)nullptr, 0, ng, 256, N);
-    } else {
-      rc = launch_gemm_ln(sd, s->t256b, 256, s->WL(l, SGRL_SET_L2_W), 256, s->WL(l, SGRL_SET_L2_B), N, 256, s->fn, ng, 256,
-                          s->WL(l, SGRL_SET_N2_W), s->WL(l, SGRL_SET_N2_B));
+    return rc;
+  };
+  static const int split_mode = [] { const char* e = getenv("SGRL_SET_SPLIT"); return e && e[0] >= '0' && e[0] <= '3' ? e[0] - '0' : 1; }();
+  const bool split = split_mode != 0 && chain && !one_stream && s->stop_after < 0 && N >= kSplitMinNodes && s->split_node > 0 && s->split_node < N;
+  s->last_split = split ? s->split_node : 0;
+  if (!split) {
+    Part whole{0, N, 0, s->n_env, st, sd, s->ev_fork, s->ev_join, s->cat, s->cat2, nullptr};
+    for (int k = 0; k < kStages; k++) {
+      const int rc = stage(whole, k);
+      if (rc == kStop) return SGRL_OK;
       if (rc != SGRL_OK) return rc;
     }
-    rc = equiv_gemm(s->t256, s->WL(l, SGRL_SET_L4_W), s->WL(l, SGRL_SET_L4_B));
-    if (rc != SGRL_OK) return rc;
-    hipLaunchKernelGGL(k_equiv, dim3((N + 7) / 8), dim3(128), 0, st, s->mat, s->WL(l, SGRL_SET_L5_W), s->g1, s->g,
-                       l == SGRL_SET_LAYERS - 1 ? s->outg : (float*)nullptr, N);
-    join();
-    if (s->stop_after == 2 * l + 1) return SGRL_OK;  // probe: g / ng (= cat[:, 128:]) are this layer's outputs
-  }
-  // final norm -> outng[:, 17:145]; head
-  hipLaunchKernelGGL(k_add_ln, dim3(lnb), dim3(256), 0, st, ng, 256, (const float*)nullptr, 0, s->W(SGRL_SET_FNORM_W),
-                     s->W(SGRL_SET_FNORM_B), (float*)nullptr, 0, s->outng + ngf, 160, N);
-  float* const hd = chain ? cato : s->cat2;     // the head's [l2g | l2ng] rows: the buffer the last norm2 did not write
-  fork();
-  if (chain) {
-    rc = launch_chain_ng(sd, s->outng, 160, 160, s->W(SGRL_SET_L1NG_W), s->W(SGRL_SET_L1NG_B), s->W(SGRL_SET_L2NG_W), s->W(SGRL_SET_L2NG_B),
-                         hd + 128, 256, N);
-    if (rc == SGRL_OK)
-      rc = launch_site(st, s->outg, OGLD, OGLD, site_w(6), s->zc, critic ? (float*)nullptr : s->z2, s->fn, s->W(SGRL_SET_L1G_W),
-                       s->W(SGRL_SET_L1G_B), 128, s->W(SGRL_SET_L2G_W), s->W(SGRL_SET_L2G_B), hd, 256, N);
-    if (rc != SGRL_OK) return rc;
   } else {
-    GS(s->outng, 160, s->W(SGRL_SET_L1NG_W), 160, s->W(SGRL_SET_L1NG_B), s->t128b, D, N, D, 160, EPI_RELU);
-    GS(s->t128b, D, s->W(SGRL_SET_L2NG_W), D, s->W(SGRL_SET_L2NG_B), s->cat2 + 128, 256, N, D, D);
-    PG(s->outg, OGLD, OGLD, 6, critic ? (float*)nullptr : s->z2);
-    GG(s->W(SGRL_SET_L1G_W), s->W(SGRL_SET_L1G_B), s->t128a, D, D);
-    G(s->t128a, D, s->W(SGRL_SET_L2G_W), D, s->W(SGRL_SET_L2G_B), s->cat2, 256, N, D, D);
-  }
-  join();
-  if (critic) {
-    // slots reused by the critic head: DECG = decoder_ng.weight [256], L1M_B = decoder_ng.bias [1]
-    hipLaunchKernelGGL(k_q_head, dim3((N + 3) / 4), dim3(256), 0, st, hd, s->W(SGRL_SET_DECG), s->W(SGRL_SET_L1M_B), s->fn,
-                       nt, act, act_ld, N);
-  } else {
-    const bool folded = !small && s->live && s->l2mf_w && head_fold;
-    if (folded) {
-      // decoder_g folded through linear2_m: the 1024-wide product and its contraction collapse into a 32-wide product
-      G(hd, 256, s->W(SGRL_SET_L1M_W), 256, s->W(SGRL_SET_L1M_B), s->t256, 256, N, 256, 256, EPI_RELU);
-      G(s->t256, 256, s->l2mf_w, 256, s->l2mf_b, s->mat, 32, N, 32, 256, EPI_ROWDIV, s->fn);
-      hipLaunchKernelGGL(k_head_out2, dim3((N + 3) / 4), dim3(128), 0, st, s->mat, s->z2, obs, obs_ld, nt, act, act_ld, max_action, N);
-    } else if (chain && chain_eq) {
-      rc = launch_chain_equiv(st, hd, 256, 256, s->W(SGRL_SET_L1M_W), s->W(SGRL_SET_L1M_B), s->W(SGRL_SET_L2M_W), s->W(SGRL_SET_L2M_B), s->fn, s->z2,
-                              s->mat, N);
-    } else {
-      G(hd, 256, s->W(SGRL_SET_L1M_W), 256, s->W(SGRL_SET_L1M_B), s->t256, 256, N, 256, 256, EPI_RELU);
-      rc = equiv_gemm(s->t256, s->W(SGRL_SET_L2M_W), s->W(SGRL_SET_L2M_B));
+    const bool head_start = split_mode == 3;
+    Part a{0, s->split_node, 0, s->split_env, st, sd, s->ev_fork, s->ev_join, s->cat, s->cat2, head_start ? s->ev_split : (hipEvent_t) nullptr};
+    Part b{s->split_node, N - s->split_node, s->split_env, s->n_env - s->split_env, sd, st, s->ev_fork_b, s->ev_join_b, s->cat, s->cat2, nullptr};
+    if (split_mode == 1) { a.sd = a.st; b.sd = b.st; }                  // every half on its own stream, siblings included
+    if (!head_start) (void)hipEventRecord(s->ev_split, st);            // the embedding is done: the second half may start
+    for (int k = 0; k <= kStages; k++) {
+      int rc = k < kStages ? stage(a, k) : SGRL_OK;
+      if (rc != SGRL_OK) return rc;
+      if (k == 0) (void)hipStreamWaitEvent(sd, s->ev_split, 0);
+      if (k > 0) rc = stage(b, k - 1);
+      if (rc != SGRL_OK) return rc;
     }
-    if (rc != SGRL_OK) return rc;
-    if (!folded)
-      hipLaunchKernelGGL(k_head_out, dim3((N + 3) / 4), dim3(128), 0, st, s->mat, s->W(SGRL_SET_DECG), obs, obs_ld, nt,
-                         act, act_ld, max_action, N);
+    (void)hipEventRecord(s->ev_merge, sd);
+    (void)hipStreamWaitEvent(st, s->ev_merge, 0);
   }
 #undef GS
 #undef GG
@@ -1234,6 +1324,10 @@ int sgrl_set_create(sgrl_set** out) {
       hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&s->ev_l3, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&s->ev_fork_b, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&s->ev_join_b, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&s->ev_split, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&s->ev_merge, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&s->ev_pack, hipEventDisableTiming) != hipSuccess) {
     delete s;
     *out = nullptr;
@@ -1267,6 +1361,7 @@ void sgrl_set_destroy(sgrl_set* s) {
   if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
   if (s->ev_join) (void)hipEventDestroy(s->ev_join);
   if (s->ev_l3) (void)hipEventDestroy(s->ev_l3);
+  for (hipEvent_t e : {s->ev_fork_b, s->ev_join_b, s->ev_split, s->ev_merge}) if (e) (void)hipEventDestroy(e);
   if (s->ev_pack) (void)hipEventDestroy(s->ev_pack);
   delete s;
 }
@@ -1455,6 +1550,7 @@ int sgrl_set_graph(sgrl_set* s, int n_morph, const int32_t* morph_L, const int32
   c->key_i = std::move(key_i);
   c->key_f.assign(rel, rel + nrel);
   c->n_env = env; c->N = node; c->n_morph = n_morph; c->TM = TM; c->Lmax = Lmax;
+  pick_split(env_off, node, &c->split_env, &c->split_node);
   bool ok = upload(&c->d_node_env, node_env) == 0 && upload(&c->d_node_limb, node_limb) == 0 &&
             upload(&c->d_node_mnode, node_mnode) == 0 && upload(&c->d_trav, travT) == 0 &&
             upload(&c->d_env_off, env_off) == 0 && upload(&c->d_env_L, env_L) == 0 && upload(&c->d_env_relb, env_relb) == 0 &&
@@ -1515,6 +1611,7 @@ int sgrl_set_hold_weights(sgrl_set* s, int hold) {
 int sgrl_set_num_nodes(const sgrl_set* s) { return s ? s->N : SGRL_ERR_ARG; }
 int64_t sgrl_set_workspace_bytes(const sgrl_set* s) { return s ? s->ws_floats * 4 : -1; }
 int64_t sgrl_set_generation(const sgrl_set* s) { return s ? s->generation : -1; }
+int sgrl_set_last_split(const sgrl_set* s) { return s ? s->last_split : SGRL_ERR_ARG; }
 
 int sgrl_set_peek(sgrl_set* s, int which, float* host, int64_t n_floats) {
   if (!s || !host || !s->have_graph) return sfail(SGRL_ERR_ARG, "sgrl_set_peek: bad argument");

@@ -41,6 +41,7 @@ def _bind(L):
     L.sgrl_set_peek.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int64]
     L.sgrl_set_debug_stop_after.argtypes = [vp, ctypes.c_int]
     L.sgrl_set_debug_small_nodes.argtypes = [vp, ctypes.c_int]
+    L.sgrl_set_last_split.argtypes = [vp]
     L.sgrl_set_gemm_form.argtypes = [vp, ctypes.c_int]
     L.sgrl_set_last_error.restype = ctypes.c_char_p
     L.sgrl_set_hold_weights.argtypes = [vp, ctypes.c_int]
@@ -444,6 +445,10 @@ class HipSetActor(object):
     def debug_small_nodes(self, nodes):
         """Batches of at most `nodes` nodes take the small-batch products (include/sgrl_set.h); 0 = never, -1 = default."""
         _check(self.L, self.L.sgrl_set_debug_small_nodes(self.h, int(nodes)), "sgrl_set_debug_small_nodes")
+
+    def last_split(self):
+        """Nodes in the first half of the last forward; 0: it ran as a single pass (include/sgrl_set.h, the two-half forward)."""
+        return int(self.L.sgrl_set_last_split(self.h))
 
     FORM_F16X3, FORM_BF16X6 = 2, 3
 
