@@ -1,4 +1,5 @@
-/* sgrl_swat.h -- C ABI of the SWAT (structure-aware transformer) actor forward in libsgrl_hip.so.
+/* sgrl_swat.h -- C ABI of the SWAT (structure-aware transformer) actor forward, critic forward and TD3 target chain in
+ * libsgrl_hip.so.
  *
  * Replaces, for inference under torch.no_grad(), the chain
  *   Agent.select_action                    reference src/agent.py:189-198
@@ -92,6 +93,43 @@ int sgrl_swat_graph(sgrl_swat* s, int n_morph, const int32_t* morph_L, const int
  * (reference StructureActor.py:221-243), act[e, out*L_e : act_ld] = 0 exactly.  obs: DEV float [n_env, obs_ld]; act: DEV float
  * [n_env, act_ld].  SGRL_ERR_ARG unless obs_ld >= feature * Lmax and act_ld >= out * Lmax.  Asynchronous on `stream`. */
 int sgrl_swat_forward(sgrl_swat* s, const float* obs, int obs_ld, float* act, int act_ld, float max_action, void* stream);
+
+/* ---- critic networks and the TD3 target chain (inference under torch.no_grad(): reference src/agent.py:126-148) -------------
+ * A CRITIC handle is bound with out = 1 and feature = 44 (one TransformerModel of reference src/StructureCritic.py:8-125,
+ * CriticStructurePolicy.critic1 / .critic2).  The input row of limb l of environment e is
+ *   [obs[e, (feature - act_feature) l : ...] | action[e, act_feature l : act_feature l + act_feature]]
+ * (StructureCritic.py:96-112 concatenates them), read from the two buffers where they lie: no concatenated copy is made.
+ * q[e, l] is the decoder output (no tanh), q[e, L_e : q_ld] = 0 exactly.  obs: DEV float [n_env, obs_ld]; action: DEV float
+ * [n_env, act_ld]; q: DEV float [n_env, q_ld].  Same 22 launches as sgrl_swat_forward, asynchronous on `stream`, live
+ * parameters, recordable into a hipGraph.  SGRL_ERR_ARG: a handle not bound as a critic (out != 1), act_feature outside
+ * 1 .. feature - 1, obs_ld < (feature - act_feature) * Lmax, act_ld < act_feature * Lmax, q_ld < Lmax. */
+int sgrl_swat_forward_q(sgrl_swat* s, const float* obs, int obs_ld, const float* action, int act_ld, int act_feature, float* q,
+                        int q_ld, void* stream);
+
+/* Twin critics (CriticStructurePolicy.forward): two handles holding the SAME batch structure (SGRL_ERR_ARG otherwise), one pair
+ * of input buffers, q1 / q2 as sgrl_swat_forward_q of s1 / s2 -- bit for bit.  The two chains run side by side: s1's on
+ * `stream`, s2's on a side stream owned by s1, forked from and joined back into `stream` by events (work queued on `stream`
+ * after the call sees both results).  The side stream is created by the first twin call of a handle: make that call outside
+ * any stream capture. */
+int sgrl_swat_forward_twin(sgrl_swat* s1, sgrl_swat* s2, const float* obs, int obs_ld, const float* action, int act_ld,
+                           int act_feature, float* q1, float* q2, int q_ld, void* stream);
+
+/* The no-grad half of a TD3 update in one call (reference src/agent.py:126-148) over the three TARGET networks, all holding the
+ * same batch structure:
+ *   a'          = clamp(actor_t(next_obs) + clamp(noise, +-noise_clip), +-max_action)      in the actor's tail kernel
+ *   target_q[e, l] = reward[e] + (1 - done[e]) * discount * min(Q1_t, Q2_t)(next_obs, a')[e, l]   in the first critic's tail kernel
+ * with target_q[e, L_e : q_ld] = 0.  noise: DEV float [n_env, noise_ld], laid out like an action row (the caller's N(0,
+ * policy_noise) draw, unclipped); reward, done: DEV float [n_env].  a' and the Q values stay in the handles' workspaces.
+ * SGRL_ERR_ARG as above, and unless the critics' feature = the actor's feature + out. */
+int sgrl_swat_td_target(sgrl_swat* actor_t, sgrl_swat* q1_t, sgrl_swat* q2_t, const float* next_obs, int obs_ld, const float* noise,
+                        int noise_ld, const float* reward, const float* done, float max_action, float noise_clip, float discount,
+                        float* target_q, int q_ld, void* stream);
+
+/* Launches of one sgrl_swat_forward_twin (2 x 22, on two streams) and of one sgrl_swat_td_target (3 x 22). */
+int sgrl_swat_twin_launches(void);
+int sgrl_swat_td_target_launches(void);
+/* Measurements only (process-wide): 0 = the twin's second chain follows the first on the caller's stream; 1 (default) = side stream. */
+int sgrl_swat_debug_twin_streams(int on);
 
 /* Nodes / environments of the current batch structure; launches per forward (constant). */
 int sgrl_swat_num_nodes(const sgrl_swat* s);

@@ -15,6 +15,13 @@
 //                                 padding slots of the action rows
 // Every product is exact f32 (v_mfma_f32_32x32x2_f32 in k_gemm2; the row kernels are plain f32 FMA chains).  The weights are
 // read through the addresses bound by sgrl_swat_bind_params on every forward: nothing is packed, nothing is cached.
+//
+// The same 22 launches serve a CRITIC network (feature = 44, out = 1: sgrl_swat_forward_q): the embedding and the cond_decoder
+// branch of the tail read a limb's input row from two buffers, [obs 41 | action 3], where they lie, and the tail stores the
+// decoder output as it is.  The twin critic (sgrl_swat_forward_twin) is two such chains, the second on the first handle's side
+// stream between a fork and a join event (44 launches); the TD3 target chain (sgrl_swat_td_target, 66 launches) is the target
+// actor's chain, whose tail adds the clipped noise and clamps, followed by the twin, whose first tail waits for the second
+// network's values and stores reward + (1 - done) * discount * min(Q1, Q2).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -60,10 +67,34 @@ struct NodeTab {
   int TM;
 };
 
+// A limb's input row [x0 (F1 values) | x1 (F - F1 values)] read from two row-major buffers where they lie: the actor has F1 = F
+// (observations only), a critic F1 = 41 observation features followed by the limb's 3 action slots
+struct Src {
+  const float* obs; int obs_ld;
+  const float* act; int act_ld;
+  int F1;
+};
+__device__ __forceinline__ float src_at(const Src& s, int F, int env, int limb, int k) {
+  return k < s.F1 ? s.obs[(size_t)env * s.obs_ld + s.F1 * limb + k] : s.act[(size_t)env * s.act_ld + (F - s.F1) * limb + (k - s.F1)];
+}
+
+// what the tail does with the decoder output s of limb l, output j of environment e
+enum { TAIL_ACTION = 0,    // max_action * tanh(s)                                                    (StructureActor.py:221-243)
+       TAIL_TARGET_ACTION, // clamp(max_action * tanh(s) + clamp(noise[e, out l + j], +-noise_clip), +-max_action)   (agent.py:128-134)
+       TAIL_Q,             // s                                                                        (StructureCritic.py:96-112)
+       TAIL_TD_TARGET };   // reward[e] + (1 - done[e]) * discount * min(s, q_other[e, l])             (agent.py:136-148)
+struct TailEpi {
+  int mode;
+  float max_action, noise_clip, discount;
+  const float* noise; int noise_ld;
+  const float* q_other; int q_other_ld;
+  const float* reward; const float* done;
+};
+
 // input embedding + position embedding (StructureActor.py:159-164, 16-30): 8 nodes per 128-thread block, thread = channel; the
 // block's input rows are staged in LDS and every weight is loaded once per block
 constexpr int kEmbedNodes = 8;
-__global__ __launch_bounds__(128) void k_swat_embed(const float* __restrict__ obs, int obs_ld, int F, const float* __restrict__ Wenc,
+__global__ __launch_bounds__(128) void k_swat_embed(Src src, int F, const float* __restrict__ Wenc,
                                                      const float* __restrict__ benc, const float* __restrict__ emb0,
                                                      const float* __restrict__ emb1, const float* __restrict__ emb2, NodeTab nt,
                                                      float* __restrict__ h, int N, float scale) {
@@ -72,7 +103,7 @@ __global__ __launch_bounds__(128) void k_swat_embed(const float* __restrict__ ob
   for (int i = c; i < kEmbedNodes * 64; i += 128) {
     const int r = i / 64, k = i % 64, n = nb + r;
     float v = 0.f;
-    if (n < N && k < F) v = obs[(size_t)nt.node_env[n] * obs_ld + F * nt.node_limb[n] + k];
+    if (n < N && k < F) v = src_at(src, F, nt.node_env[n], nt.node_limb[n], k);
     xs[r][k] = v;
   }
   __syncthreads();
@@ -173,13 +204,14 @@ __global__ __launch_bounds__(256) void k_swat_add_ln(float* __restrict__ h, cons
 }
 
 // last layer's norm2, the final LayerNorm (fw != null), the decoder (StructureActor.py:164-170: over h, or [h | x] with
-// cond_decoder) and max_action * tanh (StructureActor.py:221-243); one wave per node.  The node of limb 0 of every environment
-// also writes the zero padding act[e, out * L_e : act_ld].
+// cond_decoder) and the epilogue of TailEpi (the actor's max_action * tanh, StructureActor.py:221-243, or one of the critic /
+// target forms); one wave per node.  The node of limb 0 of every environment also writes the zero padding
+// act[e, out * L_e : act_ld].
 __global__ __launch_bounds__(256) void k_swat_tail(const float* __restrict__ h, const float* __restrict__ d, const float* __restrict__ n2w,
                                                     const float* __restrict__ n2b, const float* __restrict__ fw, const float* __restrict__ fb,
                                                     const float* __restrict__ Wd, const float* __restrict__ bd, int cond, int F, int O,
-                                                    const float* __restrict__ obs, int obs_ld, NodeTab nt, const int32_t* __restrict__ env_L,
-                                                    float* __restrict__ act, int act_ld, float max_action, int N) {
+                                                    Src src, NodeTab nt, const int32_t* __restrict__ env_L,
+                                                    float* __restrict__ act, int act_ld, TailEpi ep, int N) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= N) return;
   float v0 = h[(size_t)row * E + lane] + d[(size_t)row * E + lane];
@@ -188,14 +220,27 @@ __global__ __launch_bounds__(256) void k_swat_tail(const float* __restrict__ h, 
   if (fw) row_ln(v0, v1, fw, fb, lane);
   const int env = nt.node_env[row], limb = nt.node_limb[row];
   const int ldd = cond ? E + F : E;
-  const float x = (cond && lane < F) ? obs[(size_t)env * obs_ld + F * limb + lane] : 0.f;
+  const float x = (cond && lane < F) ? src_at(src, F, env, limb, lane) : 0.f;
   float* arow = act + (size_t)env * act_ld;
   for (int j = 0; j < O; j++) {
     const float* wr = Wd + (size_t)j * ldd;
     float s = fmaf(v0, wr[lane], v1 * wr[64 + lane]);
     if (cond && lane < F) s = fmaf(x, wr[E + lane], s);
     s = wave_sum(s) + bd[j];
-    if (lane == 0) arow[O * limb + j] = max_action * tanhf(s);
+    if (lane == 0) {
+      float y = s;
+      if (ep.mode <= TAIL_TARGET_ACTION) {
+        y = ep.max_action * tanhf(s);
+        if (ep.mode == TAIL_TARGET_ACTION) {
+          const float nz = fminf(fmaxf(ep.noise[(size_t)env * ep.noise_ld + O * limb + j], -ep.noise_clip), ep.noise_clip);
+          y = fminf(fmaxf(y + nz, -ep.max_action), ep.max_action);
+        }
+      } else if (ep.mode == TAIL_TD_TARGET) {
+        y = fminf(s, ep.q_other[(size_t)env * ep.q_other_ld + O * limb + j]);
+        y = ep.reward[env] + (1.0f - ep.done[env]) * ep.discount * y;
+      }
+      arow[O * limb + j] = y;
+    }
   }
   if (limb == 0)
     for (int k = O * env_L[env] + lane; k < act_ld; k += 64) arow[k] = 0.f;
@@ -240,8 +285,12 @@ struct sgrl_swat {
   std::vector<SwatGraphCfg*> cfgs;
   uint64_t use_clock = 0;
   int64_t generation = 0;
-  float* ws = nullptr;          // workspace: h [N, 128] | qkv [N, 384] | o [N, 128]; grows only
+  float* ws = nullptr;          // workspace: h [N, 128] | qkv [N, 384] | o [N, 128] | out [n_env, out * Lmax]; grows only
   int64_t ws_floats = 0;
+  // twin critic / target chain: the second network's chain runs on `side` of the FIRST handle between ev_fork and ev_join
+  // (created by the first twin call, never under a capture)
+  hipStream_t side = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   const float* W(int slot) const { return p[slot]; }
   const float* WL(int layer, int k) const { return p[SGRL_SWAT_NGLOBAL + layer * SGRL_SWAT_NLAYER + k]; }
 };
@@ -255,10 +304,11 @@ int upload(T** dst, const std::vector<T>& v) {
   return 0;
 }
 
-int64_t ws_floats_for(int64_t N) { return (E + 3 * E + E) * N + 3 * 64; }
+constexpr int kOutMax = 8 * LMAX;     // bind_params: out <= 8
+int64_t ws_floats_for(int64_t N, int64_t n_env) { return (E + 3 * E + E) * N + 3 * 64 + kOutMax * n_env; }
 
 int use_cfg(sgrl_swat* s, SwatGraphCfg* c) {
-  const int64_t need = ws_floats_for(c->N);
+  const int64_t need = ws_floats_for(c->N, c->n_env);
   if (need > s->ws_floats) {
     if (s->ws) { (void)hipFree(s->ws); s->generation++; }      // hipFree waits for the device: no kernel still reads the old block
     s->ws = nullptr; s->ws_floats = 0;
@@ -270,44 +320,144 @@ int use_cfg(sgrl_swat* s, SwatGraphCfg* c) {
   return SGRL_OK;
 }
 
-int run_forward(sgrl_swat* s, const float* obs, int obs_ld, float* act, int act_ld, float max_action, hipStream_t st) {
+// workspace carve-up (16-byte aligned rows for the GEMM's float4 loads): h [N, 128] | qkv [N, 384] | o [N, 128] | out; the
+// out_proj result and the feed-forward hidden layer reuse qkv, linear2's result reuses o; `out` [n_env, out * Lmax] holds what
+// the target chain keeps to itself (the target actor's noisy action, the second critic's values)
+struct Ws { float *h, *qkv, *o, *out; };
+Ws carve(const sgrl_swat* s) {
+  auto al = [](int64_t n) { return (n + 63) & ~int64_t(63); };
+  const int64_t N = s->cur->N;
+  Ws w;
+  w.h = s->ws;
+  w.qkv = w.h + al((int64_t)E * N);
+  w.o = w.qkv + al((int64_t)3 * E * N);
+  w.out = w.o + al((int64_t)E * N);
+  return w;
+}
+NodeTab node_tab(const SwatGraphCfg* c) { return NodeTab{c->d_node_env, c->d_node_limb, c->d_node_mnode, c->d_trav, c->TM}; }
+
+void run_embed(sgrl_swat* s, const Src& src, hipStream_t st) {
   const SwatGraphCfg* c = s->cur;
   const int N = c->N;
-  // workspace carve-up (16-byte aligned rows for the GEMM's float4 loads): h [N, 128] | qkv [N, 384] | o [N, 128];
-  // the out_proj result and the feed-forward hidden layer reuse qkv, linear2's result reuses o
-  auto al = [](int64_t n) { return (n + 63) & ~int64_t(63); };
-  float* h = s->ws;
-  float* qkv = h + al((int64_t)E * N);
-  float* o = qkv + al((int64_t)3 * E * N);
-  NodeTab nt{c->d_node_env, c->d_node_limb, c->d_node_mnode, c->d_trav, c->TM};
+  hipLaunchKernelGGL(k_swat_embed, dim3((N + kEmbedNodes - 1) / kEmbedNodes), dim3(128), 0, st, src, s->F,
+                     s->W(SGRL_SWAT_ENC_W), s->W(SGRL_SWAT_ENC_B), s->W(SGRL_SWAT_EMB0), s->W(SGRL_SWAT_EMB1), s->W(SGRL_SWAT_EMB2),
+                     node_tab(c), carve(s).h, N, sqrtf((float)E));
+}
+
+// layer l up to linear2 (6 launches); its norm2 follows (run_norm2) or is part of the tail (run_tail, last layer)
+void run_layer(sgrl_swat* s, int l, hipStream_t st) {
+  const SwatGraphCfg* c = s->cur;
+  const int N = c->N, rows4 = (N + 3) / 4;
+  const Ws w = carve(s);
   EnvTab et{c->d_env_off, c->d_env_L, c->d_env_rel};
-  hipLaunchKernelGGL(k_swat_embed, dim3((N + kEmbedNodes - 1) / kEmbedNodes), dim3(128), 0, st, obs, obs_ld, s->F,
-                     s->W(SGRL_SWAT_ENC_W), s->W(SGRL_SWAT_ENC_B), s->W(SGRL_SWAT_EMB0), s->W(SGRL_SWAT_EMB1), s->W(SGRL_SWAT_EMB2), nt,
-                     h, N, sqrtf((float)E));
-  const int rows4 = (N + 3) / 4;
-  for (int l = 0; l < SGRL_SWAT_LAYERS; l++) {
-    launch_gemm(st, false, h, E, s->WL(l, SGRL_SWAT_IN_W), s->WL(l, SGRL_SWAT_IN_B), qkv, 3 * E, N, 3 * E, E);
-    hipLaunchKernelGGL(k_swat_attn, dim3(c->n_env), dim3(128), 0, st, qkv, o, et, c->d_rel, s->W(SGRL_SWAT_REL_W),
-                       s->W(SGRL_SWAT_REL_B), l == 0 ? 1 : 0);
-    float* d1 = qkv;
-    launch_gemm(st, false, o, E, s->WL(l, SGRL_SWAT_OUT_W), s->WL(l, SGRL_SWAT_OUT_B), d1, E, N, E, E);
-    hipLaunchKernelGGL(k_swat_add_ln, dim3(rows4), dim3(256), 0, st, h, d1, s->WL(l, SGRL_SWAT_N1_W), s->WL(l, SGRL_SWAT_N1_B), N);
-    float* f = qkv;
-    launch_gemm(st, true, h, E, s->WL(l, SGRL_SWAT_L1_W), s->WL(l, SGRL_SWAT_L1_B), f, FF, N, FF, E);
-    float* d2 = o;
-    launch_gemm(st, false, f, FF, s->WL(l, SGRL_SWAT_L2_W), s->WL(l, SGRL_SWAT_L2_B), d2, E, N, E, FF);
-    if (l + 1 < SGRL_SWAT_LAYERS) {
-      hipLaunchKernelGGL(k_swat_add_ln, dim3(rows4), dim3(256), 0, st, h, d2, s->WL(l, SGRL_SWAT_N2_W), s->WL(l, SGRL_SWAT_N2_B), N);
-    } else {
-      const int fn = SGRL_SWAT_NGLOBAL + SGRL_SWAT_LAYERS * SGRL_SWAT_NLAYER;
-      hipLaunchKernelGGL(k_swat_tail, dim3(rows4), dim3(256), 0, st, h, d2, s->WL(l, SGRL_SWAT_N2_W), s->WL(l, SGRL_SWAT_N2_B),
-                         s->tnorm ? s->p[fn] : (const float*)nullptr, s->tnorm ? s->p[fn + 1] : (const float*)nullptr,
-                         s->W(SGRL_SWAT_DEC_W), s->W(SGRL_SWAT_DEC_B), s->cond ? 1 : 0, s->F, s->O, obs, obs_ld, nt, c->d_env_L,
-                         act, act_ld, max_action, N);
-    }
-  }
+  launch_gemm(st, false, w.h, E, s->WL(l, SGRL_SWAT_IN_W), s->WL(l, SGRL_SWAT_IN_B), w.qkv, 3 * E, N, 3 * E, E);
+  hipLaunchKernelGGL(k_swat_attn, dim3(c->n_env), dim3(128), 0, st, w.qkv, w.o, et, c->d_rel, s->W(SGRL_SWAT_REL_W),
+                     s->W(SGRL_SWAT_REL_B), l == 0 ? 1 : 0);
+  float* d1 = w.qkv;
+  launch_gemm(st, false, w.o, E, s->WL(l, SGRL_SWAT_OUT_W), s->WL(l, SGRL_SWAT_OUT_B), d1, E, N, E, E);
+  hipLaunchKernelGGL(k_swat_add_ln, dim3(rows4), dim3(256), 0, st, w.h, d1, s->WL(l, SGRL_SWAT_N1_W), s->WL(l, SGRL_SWAT_N1_B), N);
+  float* f = w.qkv;
+  launch_gemm(st, true, w.h, E, s->WL(l, SGRL_SWAT_L1_W), s->WL(l, SGRL_SWAT_L1_B), f, FF, N, FF, E);
+  launch_gemm(st, false, f, FF, s->WL(l, SGRL_SWAT_L2_W), s->WL(l, SGRL_SWAT_L2_B), w.o, E, N, E, FF);
+}
+
+void run_norm2(sgrl_swat* s, int l, hipStream_t st) {
+  const int N = s->cur->N;
+  const Ws w = carve(s);
+  hipLaunchKernelGGL(k_swat_add_ln, dim3((N + 3) / 4), dim3(256), 0, st, w.h, w.o, s->WL(l, SGRL_SWAT_N2_W), s->WL(l, SGRL_SWAT_N2_B), N);
+}
+
+void run_tail(sgrl_swat* s, const Src& src, float* out, int out_ld, const TailEpi& ep, hipStream_t st) {
+  const SwatGraphCfg* c = s->cur;
+  const int N = c->N, l = SGRL_SWAT_LAYERS - 1;
+  const Ws w = carve(s);
+  const int fn = SGRL_SWAT_NGLOBAL + SGRL_SWAT_LAYERS * SGRL_SWAT_NLAYER;
+  hipLaunchKernelGGL(k_swat_tail, dim3((N + 3) / 4), dim3(256), 0, st, w.h, w.o, s->WL(l, SGRL_SWAT_N2_W), s->WL(l, SGRL_SWAT_N2_B),
+                     s->tnorm ? s->p[fn] : (const float*)nullptr, s->tnorm ? s->p[fn + 1] : (const float*)nullptr,
+                     s->W(SGRL_SWAT_DEC_W), s->W(SGRL_SWAT_DEC_B), s->cond ? 1 : 0, s->F, s->O, src, node_tab(c), c->d_env_L,
+                     out, out_ld, ep, N);
+}
+
+int launch_status(const char* what) {
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return wfail(SGRL_ERR_HIP, std::string("SWAT forward launch: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return wfail(SGRL_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+  return SGRL_OK;
+}
+
+// one network, one stream: 1 + 3 x 7 launches
+void run_chain(sgrl_swat* s, const Src& src, float* out, int out_ld, const TailEpi& ep, hipStream_t st) {
+  run_embed(s, src, st);
+  for (int l = 0; l < SGRL_SWAT_LAYERS; l++) {
+    run_layer(s, l, st);
+    if (l + 1 < SGRL_SWAT_LAYERS) run_norm2(s, l, st);
+  }
+  run_tail(s, src, out, out_ld, ep, st);
+}
+
+TailEpi epi(int mode) { TailEpi e{}; e.mode = mode; return e; }
+
+bool g_twin_streams = true;     // sgrl_swat_debug_twin_streams
+
+int ensure_side(sgrl_swat* s) {
+  if (s->side) return SGRL_OK;
+  if (hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming) != hipSuccess) {
+    if (s->side) (void)hipStreamDestroy(s->side);
+    if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
+    if (s->ev_join) (void)hipEventDestroy(s->ev_join);
+    s->side = nullptr; s->ev_fork = s->ev_join = nullptr;
+    (void)hipGetLastError();
+    return wfail(SGRL_ERR_HIP, "cannot create the twin critic's side stream (run one twin forward eagerly before capturing one)");
+  }
+  return SGRL_OK;
+}
+
+// Two critics over one pair of input buffers: network 1 on `st`, network 2 on the side stream of handle 1, launches issued layer
+// by layer in turn so that both queues fill together.  The second network's tail always runs on its own stream; the first
+// network's tail runs before the join (plain twin: nothing to wait for) or after it (wait_q2: its epilogue reads network 2's
+// values).  Every kernel of a network gets the arguments of that network's own single forward, so its rows are the same bits.
+int run_twin(sgrl_swat* a, sgrl_swat* b, const Src& src, float* out1, int ld1, const TailEpi& ep1, float* out2, int ld2,
+             const TailEpi& ep2, bool wait_q2, hipStream_t st) {
+  hipStream_t sd = st;
+  if (g_twin_streams) {
+    if (const int rc = ensure_side(a)) return rc;
+    sd = a->side;
+    (void)hipEventRecord(a->ev_fork, st);
+    (void)hipStreamWaitEvent(sd, a->ev_fork, 0);
+  }
+  run_embed(a, src, st);
+  run_embed(b, src, sd);
+  for (int l = 0; l < SGRL_SWAT_LAYERS; l++) {
+    run_layer(a, l, st);
+    run_layer(b, l, sd);
+    if (l + 1 < SGRL_SWAT_LAYERS) { run_norm2(a, l, st); run_norm2(b, l, sd); }
+  }
+  run_tail(b, src, out2, ld2, ep2, sd);
+  if (sd != st) (void)hipEventRecord(a->ev_join, sd);
+  if (!wait_q2) run_tail(a, src, out1, ld1, ep1, st);
+  if (sd != st) (void)hipStreamWaitEvent(st, a->ev_join, 0);
+  if (wait_q2) run_tail(a, src, out1, ld1, ep1, st);
+  return launch_status("SWAT twin critic");
+}
+
+bool same_structure(const sgrl_swat* a, const sgrl_swat* b) {
+  const SwatGraphCfg *x = a->cur, *y = b->cur;
+  return x->key_i == y->key_i && x->key_f.size() == y->key_f.size() &&
+         std::memcmp(x->key_f.data(), y->key_f.data(), sizeof(float) * x->key_f.size()) == 0;
+}
+
+// argument checks of a critic forward: handle `s` bound with out = 1, the limb row = [obs (feature - act_feature) | action]
+int check_critic(const char* fn, const sgrl_swat* s, int obs_ld, int act_ld, int act_feature, int q_ld) {
+  const std::string f(fn);
+  if (!s->have_w || !s->cur) return wfail(SGRL_ERR_ARG, f + ": parameters or batch structure not set");
+  if (s->O != 1) return wfail(SGRL_ERR_ARG, f + ": the handle is not bound as a critic (out = " + std::to_string(s->O) + ", need 1)");
+  if (act_feature < 1 || act_feature > s->F - 1)
+    return wfail(SGRL_ERR_ARG, f + ": act_feature " + std::to_string(act_feature) + " outside [1, feature - 1]");
+  const int Lmax = s->cur->Lmax;
+  if (obs_ld < (s->F - act_feature) * Lmax || act_ld < act_feature * Lmax || q_ld < Lmax)
+    return wfail(SGRL_ERR_ARG, f + ": obs_ld < (feature - act_feature) * Lmax, act_ld < act_feature * Lmax or q_ld < Lmax "
+                                   "(rows too narrow for the largest morphology)");
   return SGRL_OK;
 }
 
@@ -329,6 +479,9 @@ void sgrl_swat_destroy(sgrl_swat* s) {
   if (!s) return;
   for (SwatGraphCfg* c : s->cfgs) { c->release(); delete c; }
   if (s->ws) (void)hipFree(s->ws);
+  if (s->side) (void)hipStreamDestroy(s->side);
+  if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
+  if (s->ev_join) (void)hipEventDestroy(s->ev_join);
   delete s;
 }
 
@@ -430,8 +583,64 @@ int sgrl_swat_forward(sgrl_swat* s, const float* obs, int obs_ld, float* act, in
   if (!s->have_w || !s->cur) return wfail(SGRL_ERR_ARG, "sgrl_swat_forward: parameters or batch structure not set");
   if (obs_ld < s->F * s->cur->Lmax || act_ld < s->O * s->cur->Lmax)
     return wfail(SGRL_ERR_ARG, "sgrl_swat_forward: obs_ld < feature * Lmax or act_ld < out * Lmax (rows too narrow for the largest morphology)");
-  return run_forward(s, obs, obs_ld, act, act_ld, max_action, (hipStream_t)stream);
+  TailEpi ep = epi(TAIL_ACTION);
+  ep.max_action = max_action;
+  run_chain(s, Src{obs, obs_ld, nullptr, 0, s->F}, act, act_ld, ep, (hipStream_t)stream);
+  return launch_status("SWAT forward");
 }
+
+int sgrl_swat_forward_q(sgrl_swat* s, const float* obs, int obs_ld, const float* action, int act_ld, int act_feature, float* q,
+                        int q_ld, void* stream) {
+  if (!s || !obs || !action || !q) return wfail(SGRL_ERR_ARG, "sgrl_swat_forward_q: null argument");
+  if (const int rc = check_critic("sgrl_swat_forward_q", s, obs_ld, act_ld, act_feature, q_ld)) return rc;
+  run_chain(s, Src{obs, obs_ld, action, act_ld, s->F - act_feature}, q, q_ld, epi(TAIL_Q), (hipStream_t)stream);
+  return launch_status("SWAT critic forward");
+}
+
+int sgrl_swat_forward_twin(sgrl_swat* s1, sgrl_swat* s2, const float* obs, int obs_ld, const float* action, int act_ld,
+                           int act_feature, float* q1, float* q2, int q_ld, void* stream) {
+  if (!s1 || !s2 || !obs || !action || !q1 || !q2) return wfail(SGRL_ERR_ARG, "sgrl_swat_forward_twin: null argument");
+  if (s1 == s2 || q1 == q2) return wfail(SGRL_ERR_ARG, "sgrl_swat_forward_twin: the two networks need two handles and two outputs");
+  if (const int rc = check_critic("sgrl_swat_forward_twin", s1, obs_ld, act_ld, act_feature, q_ld)) return rc;
+  if (const int rc = check_critic("sgrl_swat_forward_twin", s2, obs_ld, act_ld, act_feature, q_ld)) return rc;
+  if (s1->F != s2->F) return wfail(SGRL_ERR_ARG, "sgrl_swat_forward_twin: the two critics take different feature counts");
+  if (!same_structure(s1, s2)) return wfail(SGRL_ERR_ARG, "sgrl_swat_forward_twin: the handles hold different batch structures");
+  const Src src{obs, obs_ld, action, act_ld, s1->F - act_feature};
+  return run_twin(s1, s2, src, q1, q_ld, epi(TAIL_Q), q2, q_ld, epi(TAIL_Q), false, (hipStream_t)stream);
+}
+
+int sgrl_swat_td_target(sgrl_swat* actor_t, sgrl_swat* q1_t, sgrl_swat* q2_t, const float* next_obs, int obs_ld, const float* noise,
+                        int noise_ld, const float* reward, const float* done, float max_action, float noise_clip, float discount,
+                        float* target_q, int q_ld, void* stream) {
+  const char* fn = "sgrl_swat_td_target";
+  if (!actor_t || !q1_t || !q2_t || !next_obs || !noise || !reward || !done || !target_q)
+    return wfail(SGRL_ERR_ARG, "sgrl_swat_td_target: null argument");
+  if (actor_t == q1_t || actor_t == q2_t || q1_t == q2_t) return wfail(SGRL_ERR_ARG, "sgrl_swat_td_target: three networks need three handles");
+  if (!actor_t->have_w || !actor_t->cur) return wfail(SGRL_ERR_ARG, "sgrl_swat_td_target: actor parameters or batch structure not set");
+  const int aF = actor_t->F, aO = actor_t->O, Lmax = actor_t->cur->Lmax;
+  const int a_ld = aO * Lmax;                         // the noisy target action stays in the actor handle's workspace
+  if (const int rc = check_critic(fn, q1_t, obs_ld, a_ld, aO, q_ld)) return rc;
+  if (const int rc = check_critic(fn, q2_t, obs_ld, a_ld, aO, q_ld)) return rc;
+  if (q1_t->F != aF + aO || q2_t->F != aF + aO)
+    return wfail(SGRL_ERR_ARG, "sgrl_swat_td_target: the critics must take the actor's feature + out inputs per limb");
+  if (!same_structure(actor_t, q1_t) || !same_structure(actor_t, q2_t))
+    return wfail(SGRL_ERR_ARG, "sgrl_swat_td_target: the handles hold different batch structures");
+  if (obs_ld < aF * Lmax || noise_ld < a_ld)
+    return wfail(SGRL_ERR_ARG, "sgrl_swat_td_target: obs_ld < feature * Lmax or noise_ld < out * Lmax (rows too narrow for the largest morphology)");
+  hipStream_t st = (hipStream_t)stream;
+  float* a_next = carve(actor_t).out;
+  float* q2 = carve(q2_t).out;
+  TailEpi ea = epi(TAIL_TARGET_ACTION);
+  ea.max_action = max_action; ea.noise_clip = noise_clip; ea.noise = noise; ea.noise_ld = noise_ld;
+  run_chain(actor_t, Src{next_obs, obs_ld, nullptr, 0, aF}, a_next, a_ld, ea, st);
+  TailEpi e1 = epi(TAIL_TD_TARGET);
+  e1.discount = discount; e1.q_other = q2; e1.q_other_ld = Lmax; e1.reward = reward; e1.done = done;
+  return run_twin(q1_t, q2_t, Src{next_obs, obs_ld, a_next, a_ld, aF}, target_q, q_ld, e1, q2, Lmax, epi(TAIL_Q), true, st);
+}
+
+int sgrl_swat_twin_launches(void) { return 2 * kLaunches; }
+int sgrl_swat_td_target_launches(void) { return 3 * kLaunches; }
+int sgrl_swat_debug_twin_streams(int on) { g_twin_streams = on != 0; return SGRL_OK; }
 
 int sgrl_swat_num_nodes(const sgrl_swat* s) { return (s && s->cur) ? s->cur->N : SGRL_ERR_ARG; }
 int sgrl_swat_launches(void) { return kLaunches; }

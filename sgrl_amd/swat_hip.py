@@ -1,4 +1,4 @@
-"""Batched HIP forward of the SWAT actor (csrc/swat_actor.hip, C ABI in include/sgrl_swat.h).
+"""Batched HIP forwards of the SWAT actor and critics (csrc/swat_actor.hip, C ABI in include/sgrl_swat.h).
 
 `HipSwatActor` binds the parameters of a `StructurePolicy` (swat_policy.py, reference-compatible state_dict) to a handle BY
 ADDRESS: nothing is packed, the library reads the live tensors on every forward, so optimizer steps, soft updates,
@@ -6,6 +6,10 @@ ADDRESS: nothing is packed, the library reads the live tensors on every forward,
 tensors) needs a re-bind, which `sync_weights` does by itself.  It has the surface `Rollout` uses on `HipSetActor`
 (`configure`, `forward_batch`, `hold_weights`, `sync_weights`, `n_env`, `max_limbs`).  No CPU fallback: without the MI355X
 every entry point raises `_lib.SgrlError`.
+
+`HipSwatCritic` is the same over the two networks of a `CriticStructurePolicy` (per-limb Q values, single or twin, the surface
+of set_hip.HipSetCritic); `HipSwatTargets` runs the no-grad half of a TD3 update -- target actor, clipped noise, twin target
+critics, min and Bellman target (reference src/agent.py:126-148) -- as one library call (`td3.Agent.update_targets`).
 """
 import ctypes
 
@@ -66,6 +70,19 @@ def _bind(L):
     L.sgrl_swat_graph.restype = ci
     L.sgrl_swat_forward.argtypes = [vp, vp, ci, vp, ci, ctypes.c_float, vp]
     L.sgrl_swat_forward.restype = ci
+    cf = ctypes.c_float
+    L.sgrl_swat_forward_q.argtypes = [vp, vp, ci, vp, ci, ci, vp, ci, vp]
+    L.sgrl_swat_forward_q.restype = ci
+    L.sgrl_swat_forward_twin.argtypes = [vp, vp, vp, ci, vp, ci, ci, vp, vp, ci, vp]
+    L.sgrl_swat_forward_twin.restype = ci
+    L.sgrl_swat_td_target.argtypes = [vp, vp, vp, vp, ci, vp, ci, vp, vp, cf, cf, cf, vp, ci, vp]
+    L.sgrl_swat_td_target.restype = ci
+    L.sgrl_swat_twin_launches.argtypes = []
+    L.sgrl_swat_twin_launches.restype = ci
+    L.sgrl_swat_td_target_launches.argtypes = []
+    L.sgrl_swat_td_target_launches.restype = ci
+    L.sgrl_swat_debug_twin_streams.argtypes = [ci]
+    L.sgrl_swat_debug_twin_streams.restype = ci
     L.sgrl_swat_num_nodes.argtypes = [vp]
     L.sgrl_swat_num_nodes.restype = ci
     L.sgrl_swat_launches.argtypes = []
@@ -87,7 +104,7 @@ class HipSwatActor(object):
 
     def __init__(self, policy, device=None, net=None):
         if not torch.cuda.is_available():
-            raise _lib.SgrlError("HipSwatActor needs an MI355X (no CPU fallback)")
+            raise _lib.SgrlError("%s needs an MI355X (no CPU fallback)" % type(self).__name__)
         self.L = _lib.lib()
         _bind(self.L)
         self.policy = policy
@@ -106,6 +123,7 @@ class HipSwatActor(object):
         self.n_env = 0
         self.max_limbs = 0
         self.num_nodes = 0
+        self.act_feature = 0          # per-limb action inputs of a critic network (set by HipSwatCritic)
 
     def __del__(self):
         try:
@@ -201,7 +219,135 @@ class HipSwatActor(object):
                                                 ctypes.c_float(float(self.policy.max_action)), stream), "sgrl_swat_forward")
         return out
 
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def check_rows(self, t, per_limb, what):
+        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == self.n_env, what
+        assert t.shape[1] >= per_limb * self.max_limbs, "%s rows narrower than %d * max_limbs" % (what, per_limb)
+
+    def forward_q(self, obs, action, out=None, q_ld=None):
+        """Critic network (a handle over CriticStructurePolicy.critic1 / .critic2): obs [n_env, obs_ld], action [n_env, act_ld]
+        (out_dim-of-the-actor slots per limb) -> per-limb Q [n_env, q_ld], exact zeros beyond L_e."""
+        act_feature = self.act_feature                # 0 on an actor's handle: the library refuses it
+        self.check_rows(obs, self.feature - act_feature, "observation")
+        self.check_rows(action, act_feature, "action")
+        self.sync_weights()
+        q_ld = q_ld or self.max_limbs
+        assert q_ld >= self.max_limbs
+        if out is None:
+            out = torch.empty((self.n_env, q_ld), dtype=torch.float32, device=self.device)
+        assert out.is_contiguous() and out.shape == (self.n_env, q_ld)
+        _check(self.L, self.L.sgrl_swat_forward_q(self.h, ctypes.c_void_p(obs.data_ptr()), self._ld(obs),
+                                                  ctypes.c_void_p(action.data_ptr()), self._ld(action), act_feature,
+                                                  ctypes.c_void_p(out.data_ptr()), int(q_ld), self._stream()), "sgrl_swat_forward_q")
+        return out
+
     def forward_single(self, state, graph):
         """StructurePolicy.forward(state [B, feature * L]) for one morphology."""
         self.configure([graph], [state.shape[0]])
         return self.forward_batch(state.contiguous().float(), act_ld=self.out_dim * len(graph["parents"]))
+
+
+class HipSwatCritic(object):
+    """Twin critics of a `CriticStructurePolicy` on the HIP path (inference only: the TD3 target values, reference
+    agent.py:136-148): two handles, one per TransformerModel, sharing the batch structure.  Both networks in one call run as
+    sgrl_swat_forward_twin (two chains side by side on two streams); each network's values are those of its own single forward,
+    bit for bit."""
+
+    def __init__(self, critic_module, device=None):
+        if not torch.cuda.is_available():
+            raise _lib.SgrlError("HipSwatCritic needs an MI355X (no CPU fallback)")
+        self.module = critic_module
+        self.q1 = HipSwatActor(critic_module, device=device, net=critic_module.critic1)
+        self.q2 = HipSwatActor(critic_module, device=device, net=critic_module.critic2)
+        self.L, self.device = self.q1.L, self.q1.device
+        self.act_feature = self.q1.act_feature = self.q2.act_feature = int(critic_module.action_dim)
+        self.n_env = self.max_limbs = 0
+        if (self.q1.out_dim, self.q2.out_dim) != (1, 1) or self.q1.feature != int(critic_module.state_dim) + self.act_feature:
+            raise _lib.SgrlError("HipSwatCritic needs critics with one output and state_dim + action_dim inputs per limb")
+
+    def configure(self, graphs, counts):
+        self.q1.configure(graphs, counts)
+        self.q2.configure(graphs, counts)
+        self.n_env, self.max_limbs = self.q1.n_env, self.q1.max_limbs
+
+    def launches(self):
+        """Kernel launches of one twin forward (constant)."""
+        return int(self.L.sgrl_swat_twin_launches())
+
+    def forward_batch(self, obs, action, q_ld=None, which=(1, 2)):
+        """obs [n_env, obs_ld], action [n_env, act_ld] (float32 CUDA) -> tuple of per-limb Q [n_env, q_ld], one per network in
+        `which`; slots beyond L_e of a row are exact zeros."""
+        if not (1 in which and 2 in which):
+            return tuple(h.forward_q(obs, action, q_ld=q_ld) for k, h in ((1, self.q1), (2, self.q2)) if k in which)
+        q1 = self.q1
+        q1.check_rows(obs, q1.feature - self.act_feature, "observation")
+        q1.check_rows(action, self.act_feature, "action")
+        q1.sync_weights()
+        self.q2.sync_weights()
+        q_ld = q_ld or self.max_limbs
+        assert q_ld >= self.max_limbs
+        out = torch.empty((2, self.n_env, q_ld), dtype=torch.float32, device=self.device)
+        vp = ctypes.c_void_p
+        _check(self.L, self.L.sgrl_swat_forward_twin(q1.h, self.q2.h, vp(obs.data_ptr()), q1._ld(obs), vp(action.data_ptr()),
+                                                     q1._ld(action), self.act_feature, vp(out[0].data_ptr()), vp(out[1].data_ptr()),
+                                                     int(q_ld), q1._stream()), "sgrl_swat_forward_twin")
+        return out[0], out[1]
+
+    def forward_single(self, state, action, graph, which=(1, 2)):
+        """CriticStructurePolicy.forward(state [B, 41 L], action [B, 3 L]) for one morphology -> per-limb Q [B, L] each."""
+        B, L = state.shape[0], len(graph["parents"])
+        self.configure([graph], [B])
+        return self.forward_batch(state.contiguous().float(), action.contiguous().float(), q_ld=L, which=which)
+
+
+class HipSwatTargets(object):
+    """The no-grad half of a TD3 update of a SWAT agent (reference src/agent.py:126-148) on the HIP path: the handles of the
+    target actor (`StructurePolicy`) and the twin target critics (`CriticStructurePolicy`), and `target_q` over
+    sgrl_swat_td_target.  The noisy target action and the Q values never leave the library's workspaces."""
+
+    def __init__(self, actor_target, critic_target):
+        if not torch.cuda.is_available():
+            raise _lib.SgrlError("HipSwatTargets needs an MI355X (no CPU fallback)")
+        self.actor = actor_target.hip_handle()        # cached on the modules (dropped when they are pickled / deep-copied)
+        self.critic = critic_target.hip_handle()
+        self.L, self.device = self.actor.L, self.actor.device
+        if self.critic.q1.feature != self.actor.feature + self.actor.out_dim:
+            raise _lib.SgrlError("the target critics must take the target actor's feature + out inputs per limb")
+
+    def configure(self, graphs, counts):
+        self.actor.configure(graphs, counts)
+        self.critic.configure(graphs, counts)
+
+    def launches(self):
+        """Kernel launches of one target chain (constant)."""
+        return int(self.L.sgrl_swat_td_target_launches())
+
+    def target_q(self, next_obs, noise, reward, done, graph, noise_clip, discount, counts=None, out=None, q_ld=None):
+        """reward + (1 - done) * discount * min(Q1_t, Q2_t)(next_obs, clamp(actor_t(next_obs) + clamp(noise, +-noise_clip),
+        +-max_action)) per limb -> float32 [B, q_ld].  next_obs [B, >= 41 Lmax], noise [B, >= 3 Lmax] (the unclipped draw, laid
+        out like an action row), reward / done [B] or [B, 1].  graph: the morphology's graph dict, or a list of them with
+        `counts` environments each (row blocks in that order)."""
+        graphs = graph if isinstance(graph, (list, tuple)) else [graph]
+        self.configure(graphs, counts if counts is not None else [next_obs.shape[0]])
+        a = self.actor
+        a.check_rows(next_obs, a.feature, "observation")
+        a.check_rows(noise, a.out_dim, "noise")
+        reward, done = reward.reshape(-1), done.reshape(-1)
+        for t in (reward, done):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape[0] == a.n_env
+        a.sync_weights()
+        self.critic.q1.sync_weights()
+        self.critic.q2.sync_weights()
+        q_ld = q_ld or a.max_limbs
+        assert q_ld >= a.max_limbs
+        if out is None:
+            out = torch.empty((a.n_env, q_ld), dtype=torch.float32, device=self.device)
+        assert out.is_contiguous() and out.shape == (a.n_env, q_ld)
+        vp, cf = ctypes.c_void_p, ctypes.c_float
+        _check(self.L, self.L.sgrl_swat_td_target(a.h, self.critic.q1.h, self.critic.q2.h, vp(next_obs.data_ptr()), a._ld(next_obs),
+                                                  vp(noise.data_ptr()), a._ld(noise), vp(reward.data_ptr()), vp(done.data_ptr()),
+                                                  cf(float(a.policy.max_action)), cf(float(noise_clip)), cf(float(discount)),
+                                                  vp(out.data_ptr()), int(q_ld), a._stream()), "sgrl_swat_td_target")
+        return out

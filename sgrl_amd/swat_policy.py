@@ -7,7 +7,9 @@ relation bias (PPR, symmetric Laplacian, distance -> one additive bias per head)
 differentiable PyTorch; outputs are pinned to fixtures produced by executing the reference's own modules
 (tests/golden/swat_forward.npz, tools/capture_golden_swat.py).  The batched rollout runs the actor's no-grad forward on the HIP
 kernels of swat_hip.HipSwatActor (csrc/swat_actor.hip), which read this module's parameters in place; `forward` itself stays
-PyTorch (the TD3 update back-props through it).
+PyTorch (the TD3 update back-props through it).  The no-grad target chain of an update (td3.Agent.update_targets) runs on the
+same kernels through `hip_handle()`: the handle a module caches is per-process device state and is dropped whenever the
+module is pickled or deep-copied.
 """
 import copy
 import math
@@ -132,6 +134,19 @@ class StructurePolicy(nn.Module):
         if device is not None:
             self.actor.to(device)
         self.graph = None
+        self._swat_hip = None
+
+    def __getstate__(self):
+        d = self.__dict__.copy()
+        d["_swat_hip"] = None     # per-process device handle: never pickled / deep-copied with the module
+        return d
+
+    def hip_handle(self):
+        """The module's swat_hip.HipSwatActor, created on first use (raises _lib.SgrlError without an MI355X: no fallback)."""
+        if getattr(self, "_swat_hip", None) is None:
+            from .swat_hip import HipSwatActor
+            self._swat_hip = HipSwatActor(self)
+        return self._swat_hip
 
     def clear_buffer(self):
         self.action = None
@@ -164,6 +179,19 @@ class CriticStructurePolicy(nn.Module):
         if device is not None:
             self.to(device)
         self.graph = None
+        self._swat_hip = None
+
+    def __getstate__(self):
+        d = self.__dict__.copy()
+        d["_swat_hip"] = None     # per-process device handles: never pickled / deep-copied with the module
+        return d
+
+    def hip_handle(self):
+        """The module's swat_hip.HipSwatCritic, created on first use (raises _lib.SgrlError without an MI355X: no fallback)."""
+        if getattr(self, "_swat_hip", None) is None:
+            from .swat_hip import HipSwatCritic
+            self._swat_hip = HipSwatCritic(self)
+        return self._swat_hip
 
     def _input(self, state, action):
         B = state.shape[0]

@@ -292,7 +292,7 @@ class Agent(nn.Module):
         atype, ctype = getattr(args, "actor_type", "set"), getattr(args, "critic_type", "set")
         if atype not in ("set", "swat", "smp") or ctype not in ("set", "swat", "smp"):
             raise NotImplementedError("actor / critic types 'set', 'swat' and 'smp' are built (the actors with a batched HIP forward for collection, "
-                                      "smp in its td and bu mode; swat / smp updates in PyTorch); "
+                                      "smp in its td and bu mode; the target chain of a swat update on HIP, the rest of swat / smp updates in PyTorch); "
                                       "'mlp' is not (SURVEY 8 f4)")
         self.networks = {}
         from .smp_policy import ActorGraphPolicy, CriticGraphPolicy
@@ -327,6 +327,25 @@ class Agent(nn.Module):
         self.tot_update_count = 0
         self.target_smoothing_tau = args.agent.target_smoothing_tau
         self.reward_scale = args.agent.reward_scale
+        # SWAT actor AND critic on the GPU: the no-grad target chain of an update runs on the HIP kernels (swat_hip.HipSwatTargets,
+        # created by the first update on a CUDA batch); anything else keeps the PyTorch chain of update_targets
+        self.use_swat_hip = bool(use_hip) and atype == "swat" and ctype == "swat"
+        self._swat_targets = None
+
+    def __getstate__(self):
+        d = self.__dict__.copy()
+        d["_swat_targets"] = None     # per-process device handles: never pickled / deep-copied with the agent
+        return d
+
+    def _hip_targets(self, next_obs):
+        """swat_hip.HipSwatTargets when this update's target chain runs on HIP, else None."""
+        if not (self.use_swat_hip and next_obs.is_cuda and next_obs.dtype == torch.float32 and self.device.type == "cuda"):
+            return None
+        t = self._swat_targets
+        if t is None or t.actor.policy is not self.actor_target or t.critic.module is not self.critic_target:
+            from .swat_hip import HipSwatTargets    # raises SgrlError when the extension is missing (no fallback)
+            t = self._swat_targets = HipSwatTargets(self.actor_target, self.critic_target)
+        return t
 
     @property
     def device(self):
@@ -351,6 +370,11 @@ class Agent(nn.Module):
         with torch.no_grad():
             if noise is None:
                 noise = torch.zeros_like(action_batch).normal_(0, args.policy_noise)
+            hip = self._hip_targets(next_obs_batch)
+            if hip is not None:      # one library call: target actor, noise clip and clamp, twin target critics, min, Bellman target
+                target_Q = hip.target_q(next_obs_batch.contiguous(), noise.contiguous(), reward_batch, done_batch,
+                                        self.actor_target.graph, args.noise_clip, args.discount)
+                return reward_batch, target_Q
             noise = noise.clamp(-args.noise_clip, args.noise_clip)
             next_action = (self.actor_target(next_obs_batch) + noise).clamp(-args.max_action, args.max_action)
             target_Q1, target_Q2 = self.critic_target(next_obs_batch, next_action)    # per-limb values [B, L]
@@ -499,6 +523,8 @@ class GraphedUpdates(object):
             # r6_takeoff_vendor_graphed_*); the vendor path is an A/B arm for EAGER updates, nobody has made its capture sound
             raise RuntimeError("GraphedUpdates replays this library's own training kernels: with SGRL_TRAIN_GEMM=0 (vendor kernels) run the "
                                "updates eagerly (DeviceTrainer(graph_updates=False))")
+        # the workspace stamps below follow the SET handles only: a SWAT agent's graphs record the PyTorch target chain
+        agent.use_swat_hip = False
         for opt in (agent.actor_optimizer, agent.critic_optimizer):
             if opt.state:
                 raise RuntimeError("switch to graphed updates before the first optimizer step (Adam's step counters must be device tensors)")

@@ -1,0 +1,143 @@
+"""Host side of the HIP SWAT critic forward and TD3 target chain (sgrl_amd/swat_hip.py HipSwatCritic / HipSwatTargets,
+include/sgrl_swat.h): the parameter plan of a critic network, the exported symbols and their argument errors, no CPU fallback,
+device handles that never travel with a pickled or deep-copied module, and a CPU agent that stays on PyTorch."""
+import copy
+import ctypes
+import os
+import pickle
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from sgrl_amd import _lib
+from sgrl_amd.set_policy import default_args
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ["sgrl_swat_forward_q", "sgrl_swat_forward_twin", "sgrl_swat_td_target", "sgrl_swat_twin_launches"]
+
+
+def _actor(**over):
+    from sgrl_amd.swat_policy import StructurePolicy
+    return StructurePolicy(41, 3, 32, 1, 1.0, 3, True, False, False, default_args(**over))
+
+
+def _critic(**over):
+    from sgrl_amd.swat_policy import CriticStructurePolicy
+    return CriticStructurePolicy(41, 3, 32, 1, 3, True, False, False, default_args(**over))
+
+
+@pytest.mark.parametrize("tnorm", [1, 0])
+@pytest.mark.parametrize("cond", [0, 1])
+def test_plan_of_a_critic_network(cond, tnorm):
+    from sgrl_amd.swat_hip import plan_params
+    crit = _critic(condition_decoder_on_features=cond, transformer_norm=tnorm)
+    for net in (crit.critic1, crit.critic2):
+        plan = plan_params(net)
+        names = [n for n, _ in plan]
+        params = dict(net.named_parameters())
+        assert len(names) == len(set(names)) and sorted(names) == sorted(params)
+        for n, shape in plan:
+            assert tuple(params[n].shape) == tuple(shape), n
+        shapes = dict(plan)
+        assert shapes["decoder.weight"] == ((1, 172) if cond else (1, 128))
+        assert shapes["encoder.weight"] == (128, 44)
+        assert len(plan) == 9 + 3 * 12 + (2 if tnorm else 0)
+
+
+def _declared(header):
+    text = open(os.path.join(REPO, "include", header)).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return sorted(set(re.findall(r"\b(sgrl_[a-z0-9_]+)\s*\(", text)))
+
+
+def test_library_exports_the_critic_and_target_symbols():
+    so = ctypes.CDLL(_lib.build())
+    names = _declared("sgrl_swat.h")
+    assert set(NEW_SYMBOLS) <= set(names)
+    for n in names:
+        assert hasattr(so, n), n
+
+
+def test_null_handles_are_argument_errors():
+    from sgrl_amd.swat_hip import _bind
+    L = _lib.lib()
+    _bind(L)
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    assert L.sgrl_swat_forward_q(None, p, 41, p, 3, 3, p, 1, None) == -1
+    assert b"sgrl_swat_forward_q" in L.sgrl_swat_last_error()
+    assert L.sgrl_swat_forward_twin(None, None, p, 41, p, 3, 3, p, p, 1, None) == -1
+    assert b"sgrl_swat_forward_twin" in L.sgrl_swat_last_error()
+    assert L.sgrl_swat_td_target(None, None, None, p, 41, p, 3, p, p, 1.0, 0.5, 0.99, p, 1, None) == -1
+    assert b"sgrl_swat_td_target" in L.sgrl_swat_last_error()
+    assert L.sgrl_swat_twin_launches() == 2 * L.sgrl_swat_launches() == 44
+    assert L.sgrl_swat_td_target_launches() == 3 * L.sgrl_swat_launches()
+
+
+def test_no_cpu_fallback_without_a_device():
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is present")
+    from sgrl_amd.swat_hip import HipSwatCritic, HipSwatTargets
+    with pytest.raises(_lib.SgrlError, match="no CPU fallback"):
+        HipSwatCritic(_critic())
+    with pytest.raises(_lib.SgrlError, match="no CPU fallback"):
+        HipSwatTargets(_actor(), _critic())
+    with pytest.raises(_lib.SgrlError, match="no CPU fallback"):
+        _critic().hip_handle()
+
+
+class _StubHandle(object):
+    """Stands for a device handle: refuses to be copied or pickled, as a ctypes pointer does."""
+
+    def __reduce_ex__(self, protocol):
+        raise TypeError("a device handle must not travel with the module")
+
+
+@pytest.mark.parametrize("make", [_actor, _critic])
+def test_cached_handle_is_dropped_by_deepcopy_and_pickle(make):
+    mod = make()
+    assert mod._swat_hip is None
+    keys = list(mod.state_dict().keys())
+    mod._swat_hip = _StubHandle()
+    for other in (copy.deepcopy(mod), pickle.loads(pickle.dumps(mod))):
+        assert other._swat_hip is None
+        assert list(other.state_dict().keys()) == keys
+        for (n, p), (m, q) in zip(mod.state_dict().items(), other.state_dict().items()):
+            assert n == m and torch.equal(p, q)
+    assert isinstance(mod._swat_hip, _StubHandle)          # the original keeps its own
+    assert not any("hip" in k for k in keys)
+
+
+def test_cpu_swat_agent_updates_in_pytorch_and_copies_without_handles():
+    from oracle.formula import synth_obs
+    from sgrl_amd import graph as G, mjcf
+    from sgrl_amd.td3 import Agent, default_train_args
+    m = mjcf.load_asset("3d_walker_5_foot")
+    gd = G.getGraphDict(m.parents, ["pre", "inlcrs", "postlcrs"], [], device=torch.device("cpu"))
+    B, L = 6, m.num_limbs
+    torch.manual_seed(3)
+    batch = {"obs": torch.from_numpy(synth_obs(L, B, 1).astype(np.float32)), "next_obs": torch.from_numpy(synth_obs(L, B, 2).astype(np.float32)),
+             "action": torch.rand(B, 3 * L) * 2 - 1, "reward": torch.randn(B, 1), "done": torch.zeros(B, 1)}
+    noise = torch.randn(B, 3 * L) * 0.4
+    losses = []
+    for use_hip in (True, False):              # on the CPU the flag changes nothing: same numbers from the same seed
+        torch.manual_seed(1)
+        agent = Agent(default_train_args(actor_type="swat", critic_type="swat"), use_hip=use_hip)
+        assert agent.use_swat_hip == use_hip
+        agent.change_morphology(gd)
+        agent.models2train()
+        out = agent.update(batch, 0, noise=noise)
+        assert agent._swat_targets is None and agent.actor_target._swat_hip is None and agent.critic_target._swat_hip is None
+        losses.append((float(out["loss/critic_loss"]), float(out["loss/actor_loss"])))
+        assert all(np.isfinite(v) for v in losses[-1])
+    assert losses[0] == losses[1]
+    agent._swat_targets = _StubHandle()
+    agent.actor.clear_buffer()                 # the last forward's output (a non-leaf tensor) cannot be deep-copied
+    agent.actor_target.clear_buffer()
+    twin = copy.deepcopy(agent)
+    assert twin._swat_targets is None and isinstance(agent._swat_targets, _StubHandle)
+    # mixed types never take the SWAT chain
+    assert not Agent(default_train_args(actor_type="swat", critic_type="set"), use_hip=False).use_swat_hip
+    assert not Agent(default_train_args(actor_type="set", critic_type="set"), use_hip=False).use_swat_hip
