@@ -11,8 +11,11 @@ call of the shared module -- bottom-up from the deepest level, top-down from the
 messages its forward raises at ModularActor.py:244, `torch.stack` of a list of None).
 Plain differentiable PyTorch: this is what the TD3 updates run through.  Collection in the device loop runs the actor in its
 published mode (`bu and td`) through the batched HIP forward instead (smp_hip.HipSmpActor, csrc/smp_actor.hip; `_Tree` below
-stays the one source of its schedule); the `td`-only ablation and the critic have no HIP path.  Outputs are pinned to fixtures
-produced by executing the reference's own modules (tests/golden/smp_forward.npz, tools/capture_golden_smp.py).
+stays the one source of its schedule).  The no-grad target chain of an update (td3.Agent.update_targets: target actor and twin
+target critic, both `bu and td`) runs on the same kernels through `hip_handle()` (smp_hip.HipSmpTargets): the handle a module
+caches is per-process device state and is dropped whenever the module is pickled or deep-copied.  The `td`-only ablation has no
+HIP path.  Outputs are pinned to fixtures produced by executing the reference's own modules (tests/golden/smp_forward.npz,
+tools/capture_golden_smp.py).
 """
 import torch
 import torch.nn as nn
@@ -130,6 +133,20 @@ class _GraphModule(nn.Module):
         self.td, self.bu = td, bu
         self.parents = [-1]
         self._tree = _Tree(self.parents, max_children)
+        self._smp_hip = None
+
+    def __getstate__(self):
+        d = self.__dict__.copy()
+        d["_smp_hip"] = None      # per-process device handle: never pickled / deep-copied with the module
+        return d
+
+    def hip_handle(self):
+        """The module's smp_hip.HipSmpActor / HipSmpCritic, created on first use (raises _lib.SgrlError without an MI355X, and
+        for the td-only mode: no fallback)."""
+        if getattr(self, "_smp_hip", None) is None:
+            from . import smp_hip
+            self._smp_hip = getattr(smp_hip, self._hip_class)(self)
+        return self._smp_hip
 
     def _relist(self, names):
         for n in names:
@@ -181,6 +198,7 @@ class _GraphModule(nn.Module):
 class ActorGraphPolicy(_GraphModule):
     """Drop-in for reference ModularActor.ActorGraphPolicy (constructor of ModularActor.py:102-115)."""
     _lists = ("sNet", "actor")
+    _hip_class = "HipSmpActor"
 
     def __init__(self, state_dim, action_dim, msg_dim, batch_size, max_action, max_children, disable_fold, td, bu,
                  args=None, device=None):
@@ -218,6 +236,7 @@ class CriticGraphPolicy(_GraphModule):
     """Drop-in for reference ModularCritic.CriticGraphPolicy: twin Q values, per-limb outputs summed over the limbs -> [B, 1]
     each (ModularCritic.py:286-290)."""
     _lists = ("sNet", "critic")
+    _hip_class = "HipSmpCritic"
 
     def __init__(self, state_dim, action_dim, msg_dim, batch_size, max_children, disable_fold, td, bu, args=None,
                  device=None):

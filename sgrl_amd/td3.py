@@ -292,8 +292,8 @@ class Agent(nn.Module):
         atype, ctype = getattr(args, "actor_type", "set"), getattr(args, "critic_type", "set")
         if atype not in ("set", "swat", "smp") or ctype not in ("set", "swat", "smp"):
             raise NotImplementedError("actor / critic types 'set', 'swat' and 'smp' are built (the actors with a batched HIP forward for collection, "
-                                      "smp in its td and bu mode; the target chain of a swat update on HIP, the rest of swat / smp updates in PyTorch); "
-                                      "'mlp' is not (SURVEY 8 f4)")
+                                      "smp in its td and bu mode; the target chain of a swat or an smp (td and bu) update on HIP, the rest of swat / "
+                                      "smp updates in PyTorch); 'mlp' is not (SURVEY 8 f4)")
         self.networks = {}
         from .smp_policy import ActorGraphPolicy, CriticGraphPolicy
         from .swat_policy import CriticStructurePolicy, StructurePolicy
@@ -331,16 +331,27 @@ class Agent(nn.Module):
         # created by the first update on a CUDA batch); anything else keeps the PyTorch chain of update_targets
         self.use_swat_hip = bool(use_hip) and atype == "swat" and ctype == "swat"
         self._swat_targets = None
+        # the same for SMP actor AND critic in the published mode (td and bu; smp_hip.HipSmpTargets); the td-only mode stays PyTorch
+        self.use_smp_hip = bool(use_hip) and atype == "smp" and ctype == "smp" and bool(args.td) and bool(args.bu)
+        self._smp_targets = None
 
     def __getstate__(self):
         d = self.__dict__.copy()
         d["_swat_targets"] = None     # per-process device handles: never pickled / deep-copied with the agent
+        d["_smp_targets"] = None
         return d
 
     def _hip_targets(self, next_obs):
-        """swat_hip.HipSwatTargets when this update's target chain runs on HIP, else None."""
-        if not (self.use_swat_hip and next_obs.is_cuda and next_obs.dtype == torch.float32 and self.device.type == "cuda"):
+        """swat_hip.HipSwatTargets / smp_hip.HipSmpTargets when this update's target chain runs on HIP, else None."""
+        if not ((self.use_swat_hip or self.use_smp_hip) and next_obs.is_cuda and next_obs.dtype == torch.float32 and
+                self.device.type == "cuda"):
             return None
+        if self.use_smp_hip:
+            t = self._smp_targets
+            if t is None or t.actor.policy is not self.actor_target or t.critic.module is not self.critic_target:
+                from .smp_hip import HipSmpTargets      # raises SgrlError when the extension is missing (no fallback)
+                t = self._smp_targets = HipSmpTargets(self.actor_target, self.critic_target)
+            return t
         t = self._swat_targets
         if t is None or t.actor.policy is not self.actor_target or t.critic.module is not self.critic_target:
             from .swat_hip import HipSwatTargets    # raises SgrlError when the extension is missing (no fallback)
@@ -523,8 +534,9 @@ class GraphedUpdates(object):
             # r6_takeoff_vendor_graphed_*); the vendor path is an A/B arm for EAGER updates, nobody has made its capture sound
             raise RuntimeError("GraphedUpdates replays this library's own training kernels: with SGRL_TRAIN_GEMM=0 (vendor kernels) run the "
                                "updates eagerly (DeviceTrainer(graph_updates=False))")
-        # the workspace stamps below follow the SET handles only: a SWAT agent's graphs record the PyTorch target chain
+        # the workspace stamps below follow the SET handles only: a SWAT or SMP agent's graphs record the PyTorch target chain
         agent.use_swat_hip = False
+        agent.use_smp_hip = False
         for opt in (agent.actor_optimizer, agent.critic_optimizer):
             if opt.state:
                 raise RuntimeError("switch to graphed updates before the first optimizer step (Adam's step counters must be device tensors)")
