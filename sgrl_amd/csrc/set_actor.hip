@@ -566,7 +566,7 @@ struct sgrl_set {
   bool stack_dirty = true;
   bool stack_critic = false;   // mode the stacked operands were built for
   int stop_after = -1;         // parity probes: leave run_forward after this stage (sgrl_set_debug_stop_after)
-  int small_nodes = -1;        // batches of at most this many nodes take the small-batch products; -1: SGRL_SET_SMALL_NODES / default
+  int small_nodes = -1;        // batches of at most this many nodes take the small-batch products; -1: kSmallNodesDefault
   int gemm_form = 0;           // SGRL_SET_FORM_* of the tile products; 0: SGRL_SET_GEMM / default (sgrl_set_gemm_form)
   // two-piece products: the product matrices of the flat buffer, cut into row-scaled words by k_encode_rows behind every k_pack
   sgrl_gemm::EncMat* d_enc = nullptr;   // [n_enc] (offset, rows, K, first row)
@@ -676,7 +676,7 @@ bool gemm_use_split() {
   static const bool v = [] { const char* e = getenv("SGRL_SET_GEMM"); return !(e && e[0] == 'f'); }();
   return v;
 }
-// Split form of the forward in flight (set by run_forward from its handle): SGRL_SET_FORM_F16X3 = two f16 pieces, three matrix
+// The product context of one forward (built by run_forward from its handle and passed down to every launcher): SGRL_SET_FORM_F16X3 = two f16 pieces, three matrix
 // instructions per product block (default; every operand row pre-scaled by a power of two: float32's range), SGRL_SET_FORM_BF16X6 =
 // three bf16 pieces, six instructions, f32's exponent range (gemm_f32.h).  SGRL_SET_GEMM=bf16x6 makes the latter the default.
 struct GemmCtx {
@@ -685,23 +685,22 @@ struct GemmCtx {
   const float* wsc = nullptr;                                         // inverse row scales of the twin's matrices ...
   const std::vector<std::pair<int64_t, int>>* enc_index = nullptr;    // ... found by a matrix' flat offset
 };
-thread_local GemmCtx g_gemm;
 int gemm_default_form() {
   static const int v = [] { const char* e = getenv("SGRL_SET_GEMM"); return (e && e[0] == 'b') ? SGRL_SET_FORM_BF16X6 : SGRL_SET_FORM_F16X3; }();
   return v;
 }
 // arguments of a two-piece launch: the event counter, and W taken from the pre-split twin of the weight buffer
 // inverse row scales of the product matrix that starts at W (null: W is not a whole matrix of the table -> unscaled words do not exist)
-const float* wsc_of(const float* W) {
-  if (!g_gemm.enc_index) return nullptr;
-  const int64_t off = W - g_gemm.w_base;
-  for (const auto& e : *g_gemm.enc_index) if (e.first == off) return g_gemm.wsc + e.second;
+const float* wsc_of(const GemmCtx& gx, const float* W) {
+  if (!gx.enc_index) return nullptr;
+  const int64_t off = W - gx.w_base;
+  for (const auto& e : *gx.enc_index) if (e.first == off) return gx.wsc + e.second;
   return nullptr;
 }
-GemmArgs with_words(const GemmArgs& a) {
+GemmArgs with_words(const GemmCtx& gx, const GemmArgs& a) {
   GemmArgs b = a;
-  b.W = reinterpret_cast<const float*>(g_gemm.w_words + (a.W - g_gemm.w_base));
-  b.wscale = wsc_of(a.W);
+  b.W = reinterpret_cast<const float*>(gx.w_words + (a.W - gx.w_base));
+  b.wscale = wsc_of(gx, a.W);
   return b;
 }
 template <int F> struct GemmKernels {
@@ -722,12 +721,12 @@ template <int F> struct GemmKernels {
            hipFuncSetAttribute(reinterpret_cast<const void*>(kSplit), hipFuncAttributeMaxDynamicSharedMemorySize, kSplitLds) == hipSuccess &&
            hipFuncSetAttribute(reinterpret_cast<const void*>(kSplitH), hipFuncAttributeMaxDynamicSharedMemorySize, kSplitHLds) == hipSuccess;
   }
-  static void launch(hipStream_t st, const GemmArgs& a) {
+  static void launch(const GemmCtx& gx, hipStream_t st, const GemmArgs& a) {
     const int tiles128 = ((a.M + 127) / 128) * ((a.N + 127) / 128);
     if (a.N <= 64 || (a.K % 32) != 0) {
       hipLaunchKernelGGL(kNarrow, dim3(((a.M + 127) / 128) * ((a.N + 63) / 64)), dim3(256), kNarrowLds, st, a);
     } else if (gemm_use_split()) {
-      if (g_gemm.form == SGRL_SET_FORM_F16X3) hipLaunchKernelGGL(kSplitH, dim3(tiles128), dim3(512), kSplitHLds, st, with_words(a));
+      if (gx.form == SGRL_SET_FORM_F16X3) hipLaunchKernelGGL(kSplitH, dim3(tiles128), dim3(512), kSplitHLds, st, with_words(gx, a));
       else hipLaunchKernelGGL(kSplit, dim3(tiles128), dim3(512), kSplitLds, st, a);
     } else if (tiles128 < 512) {
       hipLaunchKernelGGL(kNarrow, dim3(((a.M + 127) / 128) * ((a.N + 63) / 64)), dim3(256), kNarrowLds, st, a);
@@ -749,12 +748,12 @@ constexpr auto kGemmEquiv = sgrl_gemm::k_gemm3<EPI_ROWDIV | EPI_EQUIV, 4, 2, 1, 
 constexpr auto kGemmEquivH = sgrl_gemm::k_gemm3<EPI_ROWDIV | EPI_EQUIV, 4, 2, 1, 2, 16, 2, false, false, false, 0, false, 2, true, 2>;
 // the equivariant epilogue stages the block's 128 z rows (pitch 100 floats) in the tile's LDS: more than the k-tile stages need
 constexpr int kEquivLds = GemmKernels<0>::kSplitLds > 128 * 100 * 4 ? GemmKernels<0>::kSplitLds : 128 * 100 * 4;
-int launch_gemm_equiv(hipStream_t st, const float* A, int lda, const float* W, int ldw, const float* bias, int M, int K,
+int launch_gemm_equiv(const GemmCtx& gx, hipStream_t st, const float* A, int lda, const float* W, int ldw, const float* bias, int M, int K,
                       const float* rowdiv, const float* zq, float* tout) {
   if (K % 32 != 0 || (lda & 3) || (ldw & 3)) return sfail(SGRL_ERR_ARG, "gemm_equiv: K must be a multiple of 32 and rows 16-byte aligned");
   GemmArgs a{A, lda, W, ldw, bias, nullptr, 0, M, 1024, K, EPI_ROWDIV | EPI_EQUIV, rowdiv, nullptr, 0};
   a.zq = zq; a.tout = tout;
-  if (g_gemm.form == SGRL_SET_FORM_F16X3) hipLaunchKernelGGL(kGemmEquivH, dim3(((M + 127) / 128) * 8), dim3(512), kEquivLds, st, with_words(a));
+  if (gx.form == SGRL_SET_FORM_F16X3) hipLaunchKernelGGL(kGemmEquivH, dim3(((M + 127) / 128) * 8), dim3(512), kEquivLds, st, with_words(gx, a));
   else hipLaunchKernelGGL(kGemmEquiv, dim3(((M + 127) / 128) * 8), dim3(512), kEquivLds, st, a);
   return SGRL_OK;
 }
@@ -762,11 +761,11 @@ int launch_gemm_equiv(hipStream_t st, const float* A, int lda, const float* W, i
 // C[M,N] = relu(G(Z) . W^T + b): the Gram-operand GEMM (A generated from zc [M, 3, 32]; W [N, 576] folded); N = 128 or 256
 constexpr auto kGemmGram = sgrl_gemm::k_gemm3<EPI_RELU, 4, 2, 1, 2, 16, 2, false, false, false, 0, true>;
 constexpr auto kGemmGramH = sgrl_gemm::k_gemm3<EPI_RELU, 4, 2, 1, 2, 16, 2, false, false, false, 0, true, 2, true, 2>;
-int launch_gemm_gram(hipStream_t st, const float* zc, const float* W, const float* bias, float* C, int ldc, int M, int N, float* fn) {
+int launch_gemm_gram(const GemmCtx& gx, hipStream_t st, const float* zc, const float* W, const float* bias, float* C, int ldc, int M, int N, float* fn) {
   if (N % 128 != 0) return sfail(SGRL_ERR_ARG, "gemm_gram: N must be a multiple of 128");
   GemmArgs a{zc, 96, W, GK, bias, C, ldc, M, N, GK, EPI_RELU, nullptr, nullptr, 0};
   a.rowdiv_out = fn;
-  if (g_gemm.form == SGRL_SET_FORM_F16X3) hipLaunchKernelGGL(kGemmGramH, dim3(((M + 127) / 128) * (N / 128)), dim3(512), GemmKernels<0>::kSplitHLds, st, with_words(a));
+  if (gx.form == SGRL_SET_FORM_F16X3) hipLaunchKernelGGL(kGemmGramH, dim3(((M + 127) / 128) * (N / 128)), dim3(512), GemmKernels<0>::kSplitHLds, st, with_words(gx, a));
   else hipLaunchKernelGGL(kGemmGram, dim3(((M + 127) / 128) * (N / 128)), dim3(512), GemmKernels<0>::kSplitLds, st, a);
   return SGRL_OK;
 }
@@ -774,25 +773,25 @@ int launch_gemm_gram(hipStream_t st, const float* zc, const float* W, const floa
 // ln_io[m][:] = LayerNorm(ln_io[m][:] + (A . W^T + b)[m][:] / rowdiv[m]) * ln_w + ln_b   (N = 128, residual stream in place)
 constexpr auto kGemmLn = sgrl_gemm::k_gemm3<EPI_ROWDIV | EPI_LN, 4, 2, 1, 2, 16, 2>;
 constexpr auto kGemmLnH = sgrl_gemm::k_gemm3<EPI_ROWDIV | EPI_LN, 4, 2, 1, 2, 16, 2, false, false, false, 0, false, 2, true, 2>;
-int launch_gemm_ln(hipStream_t st, const float* A, int lda, const float* W, int ldw, const float* bias, int M, int K,
+int launch_gemm_ln(const GemmCtx& gx, hipStream_t st, const float* A, int lda, const float* W, int ldw, const float* bias, int M, int K,
                    const float* rowdiv, float* ln_io, int ln_ld, const float* ln_w, const float* ln_b) {
   if (K % 32 != 0 || (lda & 3) || (ldw & 3)) return sfail(SGRL_ERR_ARG, "gemm_ln: K must be a multiple of 32 and rows 16-byte aligned");
   GemmArgs a{A, lda, W, ldw, bias, nullptr, 0, M, 128, K, EPI_ROWDIV | EPI_LN, rowdiv, nullptr, 0};
   a.ln_io = ln_io; a.ln_ld = ln_ld; a.ln_w = ln_w; a.ln_b = ln_b;
-  if (g_gemm.form == SGRL_SET_FORM_F16X3) hipLaunchKernelGGL(kGemmLnH, dim3((M + 127) / 128), dim3(512), GemmKernels<0>::kSplitHLds, st, with_words(a));
+  if (gx.form == SGRL_SET_FORM_F16X3) hipLaunchKernelGGL(kGemmLnH, dim3((M + 127) / 128), dim3(512), GemmKernels<0>::kSplitHLds, st, with_words(gx, a));
   else hipLaunchKernelGGL(kGemmLn, dim3((M + 127) / 128), dim3(512), GemmKernels<0>::kSplitLds, st, a);
   return SGRL_OK;
 }
 
-int launch_gemm(hipStream_t st, const float* A, int lda, const float* W, int ldw, const float* bias, float* C, int ldc,
+int launch_gemm(const GemmCtx& gx, hipStream_t st, const float* A, int lda, const float* W, int ldw, const float* bias, float* C, int ldc,
                 int M, int N, int K, int flags = 0, const float* rowdiv = nullptr, float* C2 = nullptr, int ldc2 = 0) {
   if (K % 16 != 0 || (lda & 3) || (ldw & 3)) return sfail(SGRL_ERR_ARG, "gemm: K must be a multiple of 16 and rows 16-byte aligned");
   GemmArgs a{A, lda, W, ldw, bias, C, ldc, M, N, K, flags, rowdiv, C2, ldc2};
   switch (flags) {
-    case 0: GemmKernels<0>::launch(st, a); break;
-    case EPI_RELU: GemmKernels<EPI_RELU>::launch(st, a); break;
-    case EPI_ROWDIV: GemmKernels<EPI_ROWDIV>::launch(st, a); break;
-    case EPI_ACC2: GemmKernels<EPI_ACC2>::launch(st, a); break;
+    case 0: GemmKernels<0>::launch(gx, st, a); break;
+    case EPI_RELU: GemmKernels<EPI_RELU>::launch(gx, st, a); break;
+    case EPI_ROWDIV: GemmKernels<EPI_ROWDIV>::launch(gx, st, a); break;
+    case EPI_ACC2: GemmKernels<EPI_ACC2>::launch(gx, st, a); break;
     default: return sfail(SGRL_ERR_ARG, "gemm: unsupported epilogue combination");
   }
   return SGRL_OK;
@@ -822,15 +821,15 @@ bool chain_raise_lds_limits() {
   return hipFuncSetAttribute(reinterpret_cast<const void*>(k_chain<0, 256, EPI_ROWDIV | EPI_EQUIV, 0>), hipFuncAttributeMaxDynamicSharedMemorySize,
                              sgrl_gemm::kChainEqLds) == hipSuccess;
 }
-const unsigned* words_of(const float* W) { return g_gemm.w_words + (W - g_gemm.w_base); }
+const unsigned* words_of(const GemmCtx& gx, const float* W) { return gx.w_words + (W - gx.w_base); }
 // projection site + Gram pair: X [3 M, Kp] -> zc (and z2) -> fn -> relu(G(Z) . W1^T + b1) . W2^T + b2 -> C[:, 0:128]
-int launch_site(hipStream_t st, const float* X, int ldx, int Kp, const float* Wp, float* zc, float* z2, float* fn, const float* W1,
+int launch_site(const GemmCtx& gx, hipStream_t st, const float* X, int ldx, int Kp, const float* Wp, float* zc, float* z2, float* fn, const float* W1,
                 const float* b1, int hid, const float* W2, const float* b2, float* C, int ldc, int M) {
   if (Kp % 16 != 0 || (ldx & 3) || (hid != 256 && hid != 128)) return sfail(SGRL_ERR_ARG, "site: K must be a multiple of 16, rows 16-byte aligned, hidden width 128 or 256");
   ChainArgs a{};
-  a.A = zc; a.W1 = words_of(W1); a.ldw1 = GK; a.b1 = b1; a.W2 = words_of(W2); a.ldw2 = hid; a.b2 = b2; a.C = C; a.ldc = ldc; a.M = M; a.K1 = GK;
-  a.fn_out = fn; a.X = X; a.ldx = ldx; a.Kp = Kp; a.Wp = words_of(Wp); a.zc = zc; a.z2 = z2;
-  a.ws1 = wsc_of(W1); a.ws2 = wsc_of(W2); a.wsp = wsc_of(Wp);
+  a.A = zc; a.W1 = words_of(gx, W1); a.ldw1 = GK; a.b1 = b1; a.W2 = words_of(gx, W2); a.ldw2 = hid; a.b2 = b2; a.C = C; a.ldc = ldc; a.M = M; a.K1 = GK;
+  a.fn_out = fn; a.X = X; a.ldx = ldx; a.Kp = Kp; a.Wp = words_of(gx, Wp); a.zc = zc; a.z2 = z2;
+  a.ws1 = wsc_of(gx, W1); a.ws2 = wsc_of(gx, W2); a.wsp = wsc_of(gx, Wp);
   if (!a.ws1 || !a.ws2 || !a.wsp) return sfail(SGRL_ERR_ARG, "site: a weight operand is not a matrix of the row-scale table");
   const dim3 grid((M + sgrl_gemm::kChainRows - 1) / sgrl_gemm::kChainRows);
   if (hid == 256) {
@@ -843,41 +842,28 @@ int launch_site(hipStream_t st, const float* X, int ldx, int Kp, const float* Wp
   return SGRL_OK;
 }
 // ln_io[m][:] = LayerNorm(ln_io[m][:] + (relu(A . W1^T + b1) . W2^T + b2)[m][:] / rowdiv[m])      (hidden width 256)
-int launch_chain_ln(hipStream_t st, const float* A, int lda, int K1, const float* W1, const float* b1, const float* W2, const float* b2,
+int launch_chain_ln(const GemmCtx& gx, hipStream_t st, const float* A, int lda, int K1, const float* W1, const float* b1, const float* W2, const float* b2,
                     const float* rowdiv, float* ln_io, int ln_ld, const float* ln_w, const float* ln_b, int M, float* ln_out = nullptr) {
   if (K1 % 16 != 0 || (lda & 3)) return sfail(SGRL_ERR_ARG, "chain: K must be a multiple of 16 and rows 16-byte aligned");
   ChainArgs a{};
-  a.A = A; a.lda = lda; a.W1 = words_of(W1); a.ldw1 = K1; a.b1 = b1; a.W2 = words_of(W2); a.ldw2 = 256; a.b2 = b2; a.M = M; a.K1 = K1;
+  a.A = A; a.lda = lda; a.W1 = words_of(gx, W1); a.ldw1 = K1; a.b1 = b1; a.W2 = words_of(gx, W2); a.ldw2 = 256; a.b2 = b2; a.M = M; a.K1 = K1;
   a.rowdiv = rowdiv; a.ln_io = ln_io; a.ln_ld = ln_ld; a.ln_w = ln_w; a.ln_b = ln_b; a.ln_out = ln_out;
-  a.ws1 = wsc_of(W1); a.ws2 = wsc_of(W2);
+  a.ws1 = wsc_of(gx, W1); a.ws2 = wsc_of(gx, W2);
   if (!a.ws1 || !a.ws2) return sfail(SGRL_ERR_ARG, "chain: a weight operand is not a matrix of the row-scale table");
   hipLaunchKernelGGL(kChainLn, dim3((M + sgrl_gemm::kChainRows - 1) / sgrl_gemm::kChainRows), dim3(512), sgrl_gemm::kChainLds, st, a);
   return SGRL_OK;
 }
-// tout[m][s][c] = sum_q zq[m][s][q] * ((relu(A . W1^T + b1) . W2^T + b2)[m][c * 32 + q] / rowdiv[m])      (hidden width 256, N = 1024)
-constexpr auto kChainEq = k_chain<0, 256, EPI_ROWDIV | EPI_EQUIV, 0>;   // linear3 -> ReLU -> linear4 -> contraction (and the head's linear1_m -> linear2_m)
-int launch_chain_equiv(hipStream_t st, const float* A, int lda, int K1, const float* W1, const float* b1, const float* W2, const float* b2,
-                       const float* rowdiv, const float* zq, float* tout, int M, float* g = nullptr, const float* g1 = nullptr,
-                       const float* W5 = nullptr, float* outg = nullptr) {
-  if (K1 % 16 != 0 || (lda & 3)) return sfail(SGRL_ERR_ARG, "chain: K must be a multiple of 16 and rows 16-byte aligned");
-  ChainArgs a{};
-  a.A = A; a.lda = lda; a.W1 = words_of(W1); a.ldw1 = K1; a.b1 = b1; a.W2 = words_of(W2); a.ldw2 = 256; a.b2 = b2; a.M = M; a.K1 = K1;
-  a.rowdiv = rowdiv; a.zq = zq; a.tout = tout; a.ws1 = wsc_of(W1); a.ws2 = wsc_of(W2);
-  if (!a.ws1 || !a.ws2) return sfail(SGRL_ERR_ARG, "chain: a weight operand is not a matrix of the row-scale table");
-  if (g) {               // the vector stream's update in the same kernel
-    a.g = g; a.g1 = g1; a.W5 = words_of(W5); a.ws5 = wsc_of(W5); a.outg = outg; a.outg_ld = OGLD;
-    if (!a.ws5) return sfail(SGRL_ERR_ARG, "chain: linear5 is not a matrix of the row-scale table");
-  }
-  hipLaunchKernelGGL(kChainEq, dim3((M + sgrl_gemm::kChainRows - 1) / sgrl_gemm::kChainRows), dim3(512), sgrl_gemm::kChainEqLds, st, a);
-  return SGRL_OK;
-}
+// linear3 -> ReLU -> linear4 -> contraction with z as ONE kernel: tout[m][s][c] = sum_q zq[m][s][q] * ((relu(A . W1^T + b1) . W2^T + b2)[m][c * 32 + q] / rowdiv[m]).
+// Not part of the forward: a 64-row workgroup streams linear4's words out of L2 twice as often as the 128-row tiles do -- 151 us against the 135 us
+// of the two launches (profiles/r4_chain_lab_ffn.txt).  Kept for sgrl_set_debug_chain kind 3 (held against float64 by the tests) and tools/chain_lab.hip.
+constexpr auto kChainEq = k_chain<0, 256, EPI_ROWDIV | EPI_EQUIV, 0>;
 // C[:, 0:128] = relu(A . W1^T + b1) . W2^T + b2      (hidden width 128)
-int launch_chain_ng(hipStream_t st, const float* A, int lda, int K1, const float* W1, const float* b1, const float* W2, const float* b2,
+int launch_chain_ng(const GemmCtx& gx, hipStream_t st, const float* A, int lda, int K1, const float* W1, const float* b1, const float* W2, const float* b2,
                     float* C, int ldc, int M) {
   if (K1 % 16 != 0 || (lda & 3)) return sfail(SGRL_ERR_ARG, "chain: K must be a multiple of 16 and rows 16-byte aligned");
   ChainArgs a{};
-  a.A = A; a.lda = lda; a.W1 = words_of(W1); a.ldw1 = K1; a.b1 = b1; a.W2 = words_of(W2); a.ldw2 = 128; a.b2 = b2; a.C = C; a.ldc = ldc; a.M = M;
-  a.K1 = K1; a.ws1 = wsc_of(W1); a.ws2 = wsc_of(W2);
+  a.A = A; a.lda = lda; a.W1 = words_of(gx, W1); a.ldw1 = K1; a.b1 = b1; a.W2 = words_of(gx, W2); a.ldw2 = 128; a.b2 = b2; a.C = C; a.ldc = ldc; a.M = M;
+  a.K1 = K1; a.ws1 = wsc_of(gx, W1); a.ws2 = wsc_of(gx, W2);
   if (!a.ws1 || !a.ws2) return sfail(SGRL_ERR_ARG, "chain: a weight operand is not a matrix of the row-scale table");
   hipLaunchKernelGGL(kChainNg, dim3((M + sgrl_gemm::kChainRows - 1) / sgrl_gemm::kChainRows), dim3(512), sgrl_gemm::kChainLds, st, a);
   return SGRL_OK;
@@ -890,11 +876,8 @@ int launch_chain_ng(hipStream_t st, const float* A, int lda, int K1, const float
 // kernels of the training path instead (train_gemm.hip, include/sgrl_train.h: exact-float32 matrix instruction, four waves
 // splitting every k-tile); the epilogue fusions of the big path become the small kernels below.  Scratch: the attention's
 // qkv | vg block (contiguous, 1536 floats per node), idle whenever these run.
-constexpr int kSmallNodesDefault = 2048;
+constexpr int kSmallNodesDefault = 2048;   // (tests move the threshold per handle: sgrl_set_debug_small_nodes)
 constexpr int kSplitMinNodes = 2048;    // the two-half forward (run_forward) starts here: the tile-kernel path's own size, whatever the tests set the threshold above to
-int small_nodes() {
-  return kSmallNodesDefault;       // (tests move the threshold per handle: sgrl_set_debug_small_nodes)
-}
 
 // A[n][0:576] = blocked lower triangle of Z'Z (order of the folded weights), fn[n] = ||Z'Z||_F + 1; one wave per node
 __global__ __launch_bounds__(256) void k_gram576(const float* __restrict__ zc, const unsigned short* __restrict__ tri,
@@ -950,37 +933,309 @@ int small_gemm(hipStream_t st, const float* A, int lda, const float* W, int ldw,
   return rc == SGRL_OK ? rc : small_fail();
 }
 
-// critic = false: actions[e, 0:3L] = max_action * tanh(actor(obs)).  critic = true: `action` holds the per-limb action
-// slots that complete the critic's input rows and `act` receives the per-limb Q values (row stride act_ld).
-int run_forward(sgrl_set* s, const float* obs, int obs_ld, float* act, int act_ld, float max_action, hipStream_t st,
-                bool critic = false, const float* action = nullptr, int action_ld = 0) {
-  const int N = s->N, N3 = 3 * s->N;
-  const int ngf = critic ? 20 : 17;
-  g_gemm.form = s->gemm_form ? s->gemm_form : gemm_default_form();
-  if (!s->live || !s->wwords) g_gemm.form = SGRL_SET_FORM_BF16X6;   // the two-piece form takes W pre-split by k_pack (bound parameters)
+// Everything behind the embedding is local to an environment (row-wise products and norms, attention per environment), so the
+// encoder and the head run on any range of whole environments: a Part.  The forward is either one Part (the whole batch) or, on
+// the fused tile path from kSplitMinNodes nodes on, two halves cut at an environment boundary (pick_split) that walk the same
+// stages on the same scratch rows, the first half on the caller's stream and the second on the side stream, issued one stage
+// behind it: each half's kernel tails, partial last tile rounds and launch gaps are filled by the other half's kernels.  A half
+// keeps ALL its kernels on its own stream, the siblings of the single pass (U, the norm2 chain, the head's ng chain) included:
+// the other half is the independent work in flight, and no event ties the halves together between the embedding and the end.
+// Within a half the kernels, their order and their arithmetic are those of the single pass: every row's result is bit-identical.
+// SGRL_SET_SPLIT=0 keeps the single pass; the forms that measured slower stay selectable (include/sgrl_set.h):
+// SGRL_SET_SPLIT=2 puts a half's siblings on the OTHER half's stream, SGRL_SET_SPLIT=3 also starts the second half only when the
+// first half's first site kernel is done.
+struct Part {
+  int r0, M, e0, ne;                 // first node / nodes / first environment / environments
+  hipStream_t st, sd;                // chain stream, stream of the sibling launches
+  hipEvent_t ev_fork, ev_join;
+  hipEvent_t ev_site0;               // recorded on `st` behind the first site kernel (null: not wanted)
+  // the part's rows of the workspace.  cat = [invariants | ng] is double-buffered in the fused form: norm2 writes the next ng into the
+  // OTHER buffer (catc <-> cato per layer), so that the two readers of [inv | ng] behind the feed-forward site (linear1 -> linear2 ->
+  // norm2 on the side stream, linear3 -> linear4 on the main one) never wait for each other; the unfused forms stay on catc = cat
+  float *catc, *cato, *g, *zc, *z2, *fn, *h256, *qkv, *vg, *g1, *mat, *t256, *t256b, *t128a, *t128b, *delta, *outg, *outng;
+  NodeTab nt;
+};
+
+// One stage of a part: 4 l + (0: U || site A -> qkv, 1: attention, 2: site F, 3: norm2 chain || linear3 -> linear4 -> k_equiv) of
+// encoder layer l, then the head's (final norm, ng chain || site) and (linear1_m -> linear2_m -> actions).  kStop: a parity probe ends the forward here
+constexpr int kStages = 4 * SGRL_SET_LAYERS + 2, kStop = 1;
+
+// One forward: the handle, the call's arguments, the product context and the path taken.  critic = false: actions[e, 0:3L] = max_action *
+// tanh(actor(obs)).  critic = true: `action` holds the per-limb action slots that complete the critic's input rows and `act` receives the
+// per-limb Q values (row stride act_ld).
+struct Forward {
+  sgrl_set* s;
+  const float* obs; int obs_ld; float* act; int act_ld; float max_action;
+  bool critic; const float* action; int action_ld;
+  hipStream_t st, sd;                // the caller's stream, the side stream (one_stream: the caller's again)
+  bool capturing, one_stream;
+  bool small, chain;                 // small-batch products | tile kernels with back-to-back products as one kernel each (neither: one launch per product)
+  int ngf;
+  GemmCtx gx;
+  NodeTab nt;
+  EnvTab et;
+
+  // Independent GEMM chains go to the side stream: fork() makes it wait for everything issued so far on the part's stream, join()
+  // makes that stream wait for it.  The chains' store-heavy epilogues and partial last tile waves overlap each other.
+  void fork(const Part& p) const { if (!one_stream && p.sd != p.st) { (void)hipEventRecord(p.ev_fork, p.st); (void)hipStreamWaitEvent(p.sd, p.ev_fork, 0); } }
+  void join(const Part& p) const { if (!one_stream && p.sd != p.st) { (void)hipEventRecord(p.ev_join, p.sd); (void)hipStreamWaitEvent(p.st, p.ev_join, 0); } }
+
+  Part part(int r0, int M, int e0, int ne, hipStream_t pst, hipStream_t psd, hipEvent_t ev_fork, hipEvent_t ev_join, hipEvent_t ev_site0) const {
+    const size_t r = (size_t)r0;
+    Part p{r0, M, e0, ne, pst, psd, ev_fork, ev_join, ev_site0};
+    p.catc = s->cat + 256 * r; p.cato = s->cat2 + 256 * r; p.g = s->g + 384 * r; p.zc = s->zc + 96 * r; p.z2 = s->z2 + 96 * r; p.fn = s->fn + r;
+    p.h256 = s->h256 + 256 * r; p.qkv = s->qkv + 768 * r; p.vg = s->vg + 768 * r; p.g1 = s->g1 + 384 * r; p.mat = s->mat + 96 * r;
+    p.t256 = s->t256 + 256 * r; p.t256b = s->t256b + 256 * r; p.t128a = s->t128a + 128 * r; p.t128b = s->t128b + 128 * r;
+    p.delta = s->delta + 128 * r; p.outg = s->outg + 3 * OGLD * r; p.outng = s->outng + 160 * r;
+    p.nt = NodeTab{nt.node_env + r, nt.node_limb + r, nt.node_mnode + r, nt.trav, nt.TM};
+    return p;
+  }
+  // stacked projection operand of a site (site 6, the head, Cpad 144, is last)
+  const float* site_w(int site) const { return s->live ? s->site_ptr[site] : s->wstack + (size_t)site * 64 * 128; }
+
+  // ---- products: small-batch kernels or tile kernels ---------------------------------------------------------------------
+  int gemm(hipStream_t q, const float* A, int lda, const float* W, int ldw, const float* bias, float* C, int ldc, int M, int N, int K,
+           int flags = 0, const float* rowdiv = nullptr) const {
+    return small ? small_gemm(q, A, lda, W, ldw, bias, C, ldc, M, N, K, flags, rowdiv) : launch_gemm(gx, q, A, lda, W, ldw, bias, C, ldc, M, N, K, flags, rowdiv);
+  }
+  // C = relu(G(Z) . W^T + b), fn = ||Z'Z||_F + 1.  Small path: the Gram triangle [M, 576] goes through the scratch rows (qkv | vg)
+  int gram_gemm(const Part& p, const float* W, const float* b, float* C, int ldc, int Nout) const {
+    if (!small) return launch_gemm_gram(gx, p.st, p.zc, W, b, C, ldc, p.M, Nout, p.fn);
+    hipLaunchKernelGGL(k_gram576, dim3((p.M + 3) / 4), dim3(256), 0, p.st, p.zc, s->d_tri, p.qkv, p.fn, p.M);
+    return small_gemm(p.st, p.qkv, GK, W, GK, b, C, ldc, p.M, Nout, GK, EPI_RELU);
+  }
+  // linear4 / linear2_m + equivariant contraction -> mat.  Small path: the [M, 1024] per-node matrices go through the scratch rows
+  int equiv_gemm(const Part& p, const float* A, const float* W, const float* b) const {
+    if (!small) return launch_gemm_equiv(gx, p.st, A, 256, W, 256, b, p.M, 256, p.fn, p.z2, p.mat);
+    const int rc = small_gemm(p.st, A, 256, W, 256, b, p.qkv, 1024, p.M, 1024, 256, EPI_ROWDIV, p.fn);
+    if (rc != SGRL_OK) return rc;
+    hipLaunchKernelGGL(k_zmat_perm, dim3(p.M), dim3(128), 0, p.st, p.z2, p.qkv, p.mat);
+    return SGRL_OK;
+  }
+  // projection site: Z (and Z2) = X . [Wp; Wq]^T on the matrix cores (stacked, zero-padded weights), written straight into
+  // the compact rows zc / z2 the Gram GEMM and the equivariant epilogues read
+  int project(const Part& p, const float* X, int ldx, int K, int site, float* z2) const {
+    if (K % 16 != 0 || (ldx & 3)) return sfail(SGRL_ERR_ARG, "projection: K must be a multiple of 16 and rows 16-byte aligned");
+    if (small) {          // rows 0..29 / 32..61 of the stacked operand: two narrow products (columns 30, 31 hold gdir)
+      int rc = small_gemm(p.st, X, ldx, site_w(site), K, nullptr, p.zc, ZD, 3 * p.M, 30, K);
+      if (rc == SGRL_OK && z2) rc = small_gemm(p.st, X, ldx, site_w(site) + (size_t)32 * K, K, nullptr, z2, ZD, 3 * p.M, 30, K);
+      return rc;
+    }
+    GemmArgs a{X, ldx, site_w(site), K, nullptr, p.zc, ZD, 3 * p.M, z2 ? 64 : 32, K, EPI_ZSPLIT, nullptr, z2, ZD};
+    if (gx.form == SGRL_SET_FORM_F16X3 && gemm_use_split())      // 128 x 64 tiles, four waves, W pre-split
+      hipLaunchKernelGGL(kProjH, dim3(((a.M + 127) / 128) * ((a.N + 63) / 64)), dim3(256), kProjHLds, p.st, with_words(gx, a));
+    else
+      GemmKernels<EPI_ZSPLIT>::launch(gx, p.st, a);
+    return SGRL_OK;
+  }
+  // proj + gram site: X [3 M, K] -> Z (and Z2) -> fn -> relu(G(Z) . W1^T + b1) . W2^T + b2 -> C[:, 0:128], one kernel or three products
+  // (hidden rows [M, hid] in `hbuf`)
+  int site(const Part& p, const float* X, int ldx, int K, int site, float* z2, const float* W1, const float* b1, int hid, float* hbuf,
+           const float* W2, const float* b2, float* C) const {
+    if (chain) return launch_site(gx, p.st, X, ldx, K, site_w(site), p.zc, z2, p.fn, W1, b1, hid, W2, b2, C, 256, p.M);
+    int rc = project(p, X, ldx, K, site, z2);
+    if (rc == SGRL_OK) rc = gram_gemm(p, W1, b1, hbuf, hid, hid);
+    if (rc == SGRL_OK) rc = gemm(p.st, hbuf, hid, W2, hid, b2, C, 256, p.M, 128, hid);
+    return rc;
+  }
+
+  // ---- stages ------------------------------------------------------------------------------------------------------------
+  // memset of the output, live weights packed (and encoded beside the embedding), relation bias, embedding, static weights stacked
+  void prologue(const Part& whole) {
+    const int N = s->N;
+    (void)hipMemsetAsync(act, 0, sizeof(float) * (size_t)s->n_env * act_ld, st);
+    // live weights: flat buffer (and the stacked projection operands in it) rebuilt from the parameters -- by every forward, unless
+    // the caller holds the weights (sgrl_set_hold_weights) and this handle has packed them in the same product form since
+    const bool want_words = !small && gx.form == SGRL_SET_FORM_F16X3 && gemm_use_split();
+    const bool reuse = s->live && s->hold && s->packed_ok && (!want_words || s->packed_form == SGRL_SET_FORM_F16X3) && !capturing;
+    if (reuse) (void)hipStreamWaitEvent(st, s->ev_pack, 0);      // (a forward on another stream than the one that packed)
+    if (s->live && !reuse)
+      hipLaunchKernelGGL(k_pack, dim3(s->n_chunks), dim3(256), 0, st, s->d_segs, s->d_chunks, s->d_tri, s->wflat);
+    const bool encode = s->live && !reuse && want_words;
+    if (encode) {          // the product matrices as row-scaled words: beside the embedding, which reads the f32 buffer only
+      fork(whole);
+      hipLaunchKernelGGL(sgrl_gemm::k_encode_rows, dim3((s->enc_rows + 3) / 4), dim3(256), 0, sd, s->wflat, s->wwords, s->wsc, s->d_enc, s->n_enc,
+                         s->enc_rows);
+    }
+    hipLaunchKernelGGL(k_relbias, dim3(s->n_morph), dim3(256), 0, st, s->d_rel, s->W(SGRL_SET_REL_W), s->W(SGRL_SET_REL_B),
+                       s->d_relb, s->d_m_off, s->d_m_L, s->n_morph);
+    hipLaunchKernelGGL(k_embed, dim3((N + kEmbedNodes - 1) / kEmbedNodes), dim3(128), 0, st, obs, obs_ld, action, action_ld, ngf, nt,
+                       s->W(SGRL_SET_GENC), s->W(SGRL_SET_ENC_W), s->W(SGRL_SET_ENC_B), s->W(SGRL_SET_EMB0), s->W(SGRL_SET_EMB1),
+                       s->W(SGRL_SET_EMB2), s->g, s->cat, s->outg, s->outng, s->gdir, s->zc, s->z2, N);
+    if (encode) join(whole);
+    if (s->live && !reuse && !capturing) {
+      s->packed_ok = s->hold;
+      s->packed_form = want_words ? SGRL_SET_FORM_F16X3 : SGRL_SET_FORM_BF16X6;
+      if (s->hold) (void)hipEventRecord(s->ev_pack, st);
+    }
+    s->cat_cur = s->cat;
+    if (!s->live && (s->stack_dirty || s->stack_critic != critic)) {     // static weights: the sites' stacked operands, rebuilt on this stream
+      s->stack_critic = critic;
+      auto sw = [&](int site) { return s->wstack + (size_t)site * 64 * 128; };
+      for (int l = 0; l < SGRL_SET_LAYERS; l++) {
+        hipLaunchKernelGGL(k_stack_proj, dim3(32), dim3(256), 0, st, s->WL(l, SGRL_SET_A_GPROJ), (const float*)nullptr, D, D, sw(2 * l));
+        hipLaunchKernelGGL(k_stack_proj, dim3(32), dim3(256), 0, st, s->WL(l, SGRL_SET_F_GPROJ2), s->WL(l, SGRL_SET_F_GPROJ3), D, D, sw(2 * l + 1));
+      }
+      hipLaunchKernelGGL(k_stack_proj, dim3(36), dim3(256), 0, st, s->W(SGRL_SET_GGPROJ), critic ? (const float*)nullptr : s->W(SGRL_SET_GPROJ), 136, OGLD, sw(6));
+      s->stack_dirty = false;
+    }
+  }
+  // attention, products: U = g . (Wgo_h Wvg_h)^T of both heads beside site A -> [inv | ng] -> qkv
+  int attn_site(const Part& p, int l) const {
+    fork(p);
+    int rc = gemm(p.sd, p.g, D, s->WL(l, SGRL_SET_VG_W), D, nullptr, p.vg, 256, 3 * p.M, 256, D);
+    if (rc == SGRL_OK)
+      rc = site(p, p.g, D, D, 2 * l, nullptr, s->WL(l, SGRL_SET_A_LG1_W), s->WL(l, SGRL_SET_A_LG1_B), 256, p.h256, s->WL(l, SGRL_SET_A_LG2_W),
+                s->WL(l, SGRL_SET_A_LG2_B), p.catc);
+    if (rc != SGRL_OK) return rc;
+    if (l == 0 && p.ev_site0) (void)hipEventRecord(p.ev_site0, p.st);
+    rc = gemm(p.st, p.catc, 256, s->WL(l, SGRL_SET_QKV_W), 256, s->WL(l, SGRL_SET_QKV_B), p.qkv, 768, p.M, 768, 256, EPI_ROWDIV, p.fn);
+    if (rc != SGRL_OK) return rc;
+    join(p);
+    return SGRL_OK;
+  }
+  // (k_attention finds its rows through the environment table: whole-batch base pointers)
+  int attention(const Part& p, int l) const {
+    const EnvTab etp{et.env_off + p.e0, et.env_L + p.e0, et.env_relb + p.e0};
+    hipLaunchKernelGGL(k_attention, dim3(p.ne), dim3(256), 0, p.st, s->qkv, s->vg, s->gdir, s->d_relb, etp, l == 0 ? 1 : 0,
+                       s->WL(l, SGRL_SET_NGOUT_B), s->WL(l, SGRL_SET_A_GD), s->stop_after == 2 * l ? s->delta : (float*)nullptr,
+                       s->g1, p.catc - 256 * (size_t)p.r0 + 128, 256, s->WL(l, SGRL_SET_N1_W), s->WL(l, SGRL_SET_N1_B));
+    return s->stop_after == 2 * l ? kStop : SGRL_OK;      // probe: g1 = attention's vector output, delta = its scalar output
+  }
+  // equivariant feed-forward, site F
+  int ffn_site(const Part& p, int l) const {
+    return site(p, p.g1, D, D, 2 * l + 1, p.z2, s->WL(l, SGRL_SET_F_LG1_W), s->WL(l, SGRL_SET_F_LG1_B), 256, p.h256, s->WL(l, SGRL_SET_F_LG2_W),
+                s->WL(l, SGRL_SET_F_LG2_B), p.catc);
+  }
+  // unfused linear2 with the scalar stream's second residual + norm2 (ng rewritten in place): it must not start before linear3 -- the
+  // other reader of cat = [inv | ng] -- is done
+  int norm2_unfused(const Part& p, int l) const {
+    float* const ng = p.catc + 128;
+    if (!one_stream) {
+      (void)hipEventRecord(s->ev_l3, p.st);
+      (void)hipStreamWaitEvent(p.sd, s->ev_l3, 0);
+    }
+    if (!small)
+      return launch_gemm_ln(gx, p.sd, p.t256b, 256, s->WL(l, SGRL_SET_L2_W), 256, s->WL(l, SGRL_SET_L2_B), p.M, 256, p.fn, ng, 256,
+                            s->WL(l, SGRL_SET_N2_W), s->WL(l, SGRL_SET_N2_B));
+    const int rc = small_gemm(p.st, p.t256b, 256, s->WL(l, SGRL_SET_L2_W), 256, s->WL(l, SGRL_SET_L2_B), p.delta, 128, p.M, 128, 256, EPI_ROWDIV, p.fn);
+    if (rc != SGRL_OK) return rc;
+    hipLaunchKernelGGL(k_add_ln, dim3((p.M + 3) / 4), dim3(256), 0, p.st, ng, 256, p.delta, 128, s->WL(l, SGRL_SET_N2_W),
+                       s->WL(l, SGRL_SET_N2_B), (float*)nullptr, 0, ng, 256, p.M);
+    return SGRL_OK;
+  }
+  // side: linear1 -> ReLU -> linear2 -> / fn -> residual + norm2 (fused: the new ng into the other buffer); main: linear3 -> ReLU ->
+  // linear4 -> contraction with z, then the update of the vector stream
+  int ffn_tail(Part& p, int l) const {
+    fork(p);
+    int rc;
+    if (chain) {
+      rc = launch_chain_ln(gx, p.sd, p.catc, 256, 256, s->WL(l, SGRL_SET_L1_W), s->WL(l, SGRL_SET_L1_B), s->WL(l, SGRL_SET_L2_W), s->WL(l, SGRL_SET_L2_B),
+                           p.fn, p.catc + 128, 256, s->WL(l, SGRL_SET_N2_W), s->WL(l, SGRL_SET_N2_B), p.M, p.cato + 128);
+    } else {
+      rc = gemm(p.sd, p.catc, 256, s->WL(l, SGRL_SET_L1_W), 256, s->WL(l, SGRL_SET_L1_B), p.t256b, 256, p.M, 256, 256, EPI_RELU);
+    }
+    if (rc == SGRL_OK) rc = gemm(p.st, p.catc, 256, s->WL(l, SGRL_SET_L3_W), 256, s->WL(l, SGRL_SET_L3_B), p.t256, 256, p.M, 256, 256, EPI_RELU);
+    if (rc == SGRL_OK && !chain) rc = norm2_unfused(p, l);
+    if (rc == SGRL_OK) rc = equiv_gemm(p, p.t256, s->WL(l, SGRL_SET_L4_W), s->WL(l, SGRL_SET_L4_B));
+    if (rc != SGRL_OK) return rc;
+    hipLaunchKernelGGL(k_equiv, dim3((p.M + 7) / 8), dim3(128), 0, p.st, p.mat, s->WL(l, SGRL_SET_L5_W), p.g1, p.g,
+                       l == SGRL_SET_LAYERS - 1 ? p.outg : (float*)nullptr, p.M);
+    join(p);
+    if (chain) {
+      std::swap(p.catc, p.cato);
+      s->cat_cur = p.catc - 256 * (size_t)p.r0;
+    }
+    return s->stop_after == 2 * l + 1 ? kStop : SGRL_OK;  // probe: g / ng (= the current cat[:, 128:]) are this layer's outputs
+  }
+  // final norm -> outng[:, ngf : ngf + 128]; the head's ng pair beside its site, into the [l2g | l2ng] rows: the buffer the last norm2 did not write
+  int head_site(const Part& p) const {
+    hipLaunchKernelGGL(k_add_ln, dim3((p.M + 3) / 4), dim3(256), 0, p.st, p.catc + 128, 256, (const float*)nullptr, 0, s->W(SGRL_SET_FNORM_W),
+                       s->W(SGRL_SET_FNORM_B), (float*)nullptr, 0, p.outng + ngf, 160, p.M);
+    fork(p);
+    int rc;
+    if (chain) {
+      rc = launch_chain_ng(gx, p.sd, p.outng, 160, 160, s->W(SGRL_SET_L1NG_W), s->W(SGRL_SET_L1NG_B), s->W(SGRL_SET_L2NG_W), s->W(SGRL_SET_L2NG_B),
+                           p.cato + 128, 256, p.M);
+    } else {
+      rc = gemm(p.sd, p.outng, 160, s->W(SGRL_SET_L1NG_W), 160, s->W(SGRL_SET_L1NG_B), p.t128b, D, p.M, D, 160, EPI_RELU);
+      if (rc == SGRL_OK) rc = gemm(p.sd, p.t128b, D, s->W(SGRL_SET_L2NG_W), D, s->W(SGRL_SET_L2NG_B), p.cato + 128, 256, p.M, D, D);
+    }
+    if (rc == SGRL_OK)
+      rc = site(p, p.outg, OGLD, OGLD, 6, critic ? (float*)nullptr : p.z2, s->W(SGRL_SET_L1G_W), s->W(SGRL_SET_L1G_B), 128, p.t128a,
+                s->W(SGRL_SET_L2G_W), s->W(SGRL_SET_L2G_B), p.cato);
+    if (rc != SGRL_OK) return rc;
+    join(p);
+    return SGRL_OK;
+  }
+  // critic: per-limb Q values.  actor: linear1_m -> linear2_m -> contraction with z -> actions
+  int head_out(const Part& p) const {
+    const int N = p.M;
+    if (critic) {     // slots reused by the critic head: DECG = decoder_ng.weight [256], L1M_B = decoder_ng.bias [1]
+      hipLaunchKernelGGL(k_q_head, dim3((N + 3) / 4), dim3(256), 0, p.st, p.cato, s->W(SGRL_SET_DECG), s->W(SGRL_SET_L1M_B), p.fn, p.nt, act, act_ld, N);
+      return SGRL_OK;
+    }
+    int rc = gemm(p.st, p.cato, 256, s->W(SGRL_SET_L1M_W), 256, s->W(SGRL_SET_L1M_B), p.t256, 256, N, 256, 256, EPI_RELU);
+    if (rc != SGRL_OK) return rc;
+    if (!small && s->live && s->l2mf_w) {
+      // decoder_g folded through linear2_m: the 1024-wide product and its contraction collapse into a 32-wide product
+      rc = gemm(p.st, p.t256, 256, s->l2mf_w, 256, s->l2mf_b, p.mat, 32, N, 32, 256, EPI_ROWDIV, p.fn);
+      if (rc != SGRL_OK) return rc;
+      hipLaunchKernelGGL(k_head_out2, dim3((N + 3) / 4), dim3(128), 0, p.st, p.mat, p.z2, obs, obs_ld, p.nt, act, act_ld, max_action, N);
+      return SGRL_OK;
+    }
+    rc = equiv_gemm(p, p.t256, s->W(SGRL_SET_L2M_W), s->W(SGRL_SET_L2M_B));
+    if (rc != SGRL_OK) return rc;
+    hipLaunchKernelGGL(k_head_out, dim3((N + 3) / 4), dim3(128), 0, p.st, p.mat, s->W(SGRL_SET_DECG), obs, obs_ld, p.nt, act, act_ld, max_action, N);
+    return SGRL_OK;
+  }
+  int stage(Part& p, int k) const {
+    const int l = k / 4;
+    if (k == 4 * SGRL_SET_LAYERS) return head_site(p);
+    if (k > 4 * SGRL_SET_LAYERS) return head_out(p);
+    switch (k % 4) {
+      case 0: return attn_site(p, l);
+      case 1: return attention(p, l);
+      case 2: return ffn_site(p, l);
+      default: return ffn_tail(p, l);
+    }
+  }
+};
+
+// the product context of a forward on this handle
+GemmCtx gemm_ctx_of(const sgrl_set* s) {
+  GemmCtx gx;
+  gx.form = s->gemm_form ? s->gemm_form : gemm_default_form();
+  if (!s->live || !s->wwords) gx.form = SGRL_SET_FORM_BF16X6;   // the two-piece form takes W pre-split by k_pack (bound parameters)
   // SGRL_SET_GEMM=f32: the plain products run on the exact-f32 kernels and nobody encodes the weights' words -- the generated-operand
   // products (Gram, equivariant, LayerNorm epilogue), which are always split kernels, must then take the three-piece form, which
   // splits the f32 weights itself.  (Rounds 4-5 left them on the two-piece form in that mode: they read words that had never been
   // written, and every forward of 2 048 nodes or more under SGRL_SET_GEMM=f32 returned garbage -- found in round 6 through the
   // "control" arm of the learning A/B, tools/diag/stale_pack_probe.py; tests/test_set_gpu.py now runs the mode.)
-  if (!gemm_use_split()) g_gemm.form = SGRL_SET_FORM_BF16X6;
-  g_gemm.w_base = s->w;
-  g_gemm.w_words = s->wwords;
-  g_gemm.wsc = s->wsc;
-  g_gemm.enc_index = &s->enc_index;
-  NodeTab nt{s->d_node_env, s->d_node_limb, s->d_node_mnode, s->d_trav, s->TM};
-  EnvTab et{s->d_env_off, s->d_env_L, s->d_env_relb};
-  const bool small = N <= (s->small_nodes >= 0 ? s->small_nodes : small_nodes());
-  // Independent GEMM chains go to the side stream: fork() makes it wait for everything issued so far on `st`, join()
-  // makes `st` wait for it.  The chains' store-heavy epilogues and partial last tile waves overlap each other.
+  if (!gemm_use_split()) gx.form = SGRL_SET_FORM_BF16X6;
+  gx.w_base = s->w; gx.w_words = s->wwords; gx.wsc = s->wsc; gx.enc_index = &s->enc_index;
+  return gx;
+}
+
+int run_forward(sgrl_set* s, const float* obs, int obs_ld, float* act, int act_ld, float max_action, hipStream_t st,
+                bool critic = false, const float* action = nullptr, int action_ld = 0) {
+  const int N = s->N;
+  Forward f{s, obs, obs_ld, act, act_ld, max_action, critic, action, action_ld, st};
+  f.gx = gemm_ctx_of(s);
+  f.ngf = critic ? 20 : 17;
+  f.nt = NodeTab{s->d_node_env, s->d_node_limb, s->d_node_mnode, s->d_trav, s->TM};
+  f.et = EnvTab{s->d_env_off, s->d_env_L, s->d_env_relb};
+  f.small = N <= (s->small_nodes >= 0 ? s->small_nodes : kSmallNodesDefault);
+  f.chain = !f.small && chain_enabled() && gemm_use_split() && f.gx.form == SGRL_SET_FORM_F16X3;
   // While `st` is being captured into a hipGraph (the TD3 update graphs, td3.GraphedUpdates: batches of 100 environments,
   // where every kernel is far too small to gain from overlap) everything stays on ONE stream: a graph with cross-stream
   // forks costs ~7 us of hipGraphLaunch CPU time per node on this ROCm, a single-stream graph ~0.4 us.
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   (void)hipStreamIsCapturing(st, &cap);
   static const bool serial_env = [] { const char* e = getenv("SGRL_SET_ONE_STREAM"); return e && e[0] == '1'; }();   // diagnostics: per-kernel times without overlap
-  const bool one_stream = small || cap != hipStreamCaptureStatusNone || serial_env;
-  if (!one_stream && sgrl_streams::enabled() && s->side_picks < 6 &&
+  f.capturing = cap != hipStreamCaptureStatusNone;
+  f.one_stream = f.small || f.capturing || serial_env;
+  if (!f.one_stream && sgrl_streams::enabled() && s->side_picks < 6 &&
       std::find(s->side_ok_for.begin(), s->side_ok_for.end(), st) == s->side_ok_for.end()) {
     // first forward on this caller stream: make sure the side stream sits on another hardware queue (stream_pick.h)
     s->side_picks++;
@@ -989,300 +1244,37 @@ int run_forward(sgrl_set* s, const float* obs, int obs_ld, float* act, int act_l
     s->side = chosen;
     s->side_ok_for.push_back(st);
   }
-  hipStream_t sd = one_stream ? st : s->side;
-  auto fork = [&]() { if (!one_stream) { (void)hipEventRecord(s->ev_fork, st); (void)hipStreamWaitEvent(sd, s->ev_fork, 0); } };
-  auto join = [&]() { if (!one_stream) { (void)hipEventRecord(s->ev_join, sd); (void)hipStreamWaitEvent(st, s->ev_join, 0); } };
-  (void)hipMemsetAsync(act, 0, sizeof(float) * (size_t)s->n_env * act_ld, st);
-  // live weights: flat buffer (and the stacked projection operands in it) rebuilt from the parameters -- by every forward, unless
-  // the caller holds the weights (sgrl_set_hold_weights) and this handle has packed them in the same product form since
-  const bool want_words = !small && g_gemm.form == SGRL_SET_FORM_F16X3 && gemm_use_split();
-  const bool reuse = s->live && s->hold && s->packed_ok && (!want_words || s->packed_form == SGRL_SET_FORM_F16X3) && cap == hipStreamCaptureStatusNone;
-  if (reuse) (void)hipStreamWaitEvent(st, s->ev_pack, 0);      // (a forward on another stream than the one that packed)
-  if (s->live && !reuse)
-    hipLaunchKernelGGL(k_pack, dim3(s->n_chunks), dim3(256), 0, st, s->d_segs, s->d_chunks, s->d_tri, s->wflat);
-  const bool encode = s->live && !reuse && want_words;
-  if (encode) {          // the product matrices as row-scaled words: beside the embedding, which reads the f32 buffer only
-    fork();
-    hipLaunchKernelGGL(sgrl_gemm::k_encode_rows, dim3((s->enc_rows + 3) / 4), dim3(256), 0, sd, s->wflat, s->wwords, s->wsc, s->d_enc, s->n_enc,
-                       s->enc_rows);
-  }
-  hipLaunchKernelGGL(k_relbias, dim3(s->n_morph), dim3(256), 0, st, s->d_rel, s->W(SGRL_SET_REL_W), s->W(SGRL_SET_REL_B),
-                     s->d_relb, s->d_m_off, s->d_m_L, s->n_morph);
-  hipLaunchKernelGGL(k_embed, dim3((N + kEmbedNodes - 1) / kEmbedNodes), dim3(128), 0, st, obs, obs_ld, action, action_ld, ngf, nt,
-                     s->W(SGRL_SET_GENC), s->W(SGRL_SET_ENC_W), s->W(SGRL_SET_ENC_B), s->W(SGRL_SET_EMB0), s->W(SGRL_SET_EMB1),
-                     s->W(SGRL_SET_EMB2), s->g, s->cat, s->outg, s->outng, s->gdir, s->zc, s->z2, N);
-  if (encode) join();
-  if (s->live && !reuse && cap == hipStreamCaptureStatusNone) {
-    s->packed_ok = s->hold;
-    s->packed_form = want_words ? SGRL_SET_FORM_F16X3 : SGRL_SET_FORM_BF16X6;
-    if (s->hold) (void)hipEventRecord(s->ev_pack, st);
-  }
-  // back-to-back products as one kernel each: the tile path in its two-piece form on bound (pre-split) weights
-  const bool chain = !small && chain_enabled() && gemm_use_split() && g_gemm.form == SGRL_SET_FORM_F16X3;
-  // linear3 -> linear4 -> contraction (-> vector-stream update) as ONE kernel exists (chain_f16.h, EPI_EQUIV; tests hold it against
-  // float64) but LOSES to the two launches: a 64-row workgroup streams the 1 MB of linear4 words out of L2 twice as often as the
-  // 128-row tiles do (587 MB per launch) and its three-instruction k-steps are barrier-bound -- 151 us against 135 us
-  // (profiles/r4_chain_lab_ffn.txt).  SGRL_SET_CHAIN_EQ=1 selects it for A/B runs (SGRL_SET_FUSE_UPDATE=0: k_equiv stays a launch).
-  // linear3 -> ReLU -> linear4 -> contraction as ONE kernel (launch_chain_equiv) is written, tested in tools/chain_lab.hip and 12 % slower
-  // than its two launches (profiles/r4_chain_lab_ffn.txt): not part of the forward; the head folded through linear2_m and the fused
-  // residual update are (the A/B switches of rounds 4-5 are gone, their numbers are in LAB_LOG)
-  constexpr bool chain_eq = false, head_fold = true, fuse_update = true;
-  // Everything behind the embedding is local to an environment (row-wise products and norms, attention per environment), so the
-  // encoder and the head run on any range of whole environments: a Part.  The forward is either one Part (the whole batch) or, on
-  // the fused tile path from kSplitMinNodes nodes on, two halves cut at an environment boundary (pick_split) that walk the same
-  // stages on the same scratch rows, the first half on the caller's stream and the second on the side stream, issued one stage
-  // behind it: each half's kernel tails, partial last tile rounds and launch gaps are filled by the other half's kernels.  A half
-  // keeps ALL its kernels on its own stream, the siblings of the single pass (U, the norm2 chain, the head's ng chain) included:
-  // the other half is the independent work in flight, and no event ties the halves together between the embedding and the end.
-  // Within a half the kernels, their order and their arithmetic are those of the single pass: every row's result is bit-identical.
-  // SGRL_SET_SPLIT=0 keeps the single pass; the forms that measured slower stay selectable (include/sgrl_set.h):
-  // SGRL_SET_SPLIT=2 puts a half's siblings on the OTHER half's stream, SGRL_SET_SPLIT=3 also starts the second half only when the
-  // first half's first site kernel is done.
-  struct Part {
-    int r0, M, e0, ne;                 // first node / nodes / first environment / environments
-    hipStream_t st, sd;                // chain stream, stream of the sibling launches
-    hipEvent_t ev_fork, ev_join;
-    float *catc, *cato;                // the [inv | ng] buffer in use and the other one (whole-batch base pointers)
-    hipEvent_t ev_site0;               // recorded on `st` behind the first site kernel (null: not wanted)
-  };
-  // cat = [invariants | ng] is double-buffered in the fused form: norm2 writes the next ng into the OTHER buffer, so that the two
-  // readers of [inv | ng] behind the feed-forward site (linear1 -> linear2 -> norm2 on the side stream, linear3 -> linear4 on the
-  // main one) never wait for each other
-  s->cat_cur = s->cat;
-  // proj + gram site: Z (and Z2) = X . [Wp; Wq]^T on the matrix cores (stacked, zero-padded weights), then the packed
-  // Gram triangle per node
-  auto site_w = [&](int site) -> const float* {   // site 6 (the head, Cpad 144) is last
-    return s->live ? s->site_ptr[site] : s->wstack + (size_t)site * 64 * 128;
-  };
-  if (!s->live && (s->stack_dirty || s->stack_critic != critic)) {
-    s->stack_critic = critic;
-    auto sw = [&](int site) { return s->wstack + (size_t)site * 64 * 128; };
-    for (int l = 0; l < SGRL_SET_LAYERS; l++) {
-      hipLaunchKernelGGL(k_stack_proj, dim3(32), dim3(256), 0, st, s->WL(l, SGRL_SET_A_GPROJ), (const float*)nullptr, D, D, sw(2 * l));
-      hipLaunchKernelGGL(k_stack_proj, dim3(32), dim3(256), 0, st, s->WL(l, SGRL_SET_F_GPROJ2), s->WL(l, SGRL_SET_F_GPROJ3), D, D, sw(2 * l + 1));
-    }
-    hipLaunchKernelGGL(k_stack_proj, dim3(36), dim3(256), 0, st, s->W(SGRL_SET_GGPROJ), critic ? (const float*)nullptr : s->W(SGRL_SET_GPROJ), 136, OGLD, sw(6));
-    s->stack_dirty = false;
-  }
-  constexpr int kStages = 4 * SGRL_SET_LAYERS + 2, kStop = 1;
-  // one stage of a part: 4 l + (0: U || site A -> qkv, 1: attention, 2: site F, 3: norm2 chain || linear3 -> linear4 -> k_equiv) of
-  // encoder layer l, then the head's (final norm, ng chain || site) and (linear1_m -> linear2_m -> actions).  kStop: a parity probe ends the forward here
-  auto stage = [&](Part& p, int k) -> int {
-    const int N = p.M, N3 = 3 * p.M, lnb = (N + 3) / 4;
-    hipStream_t st = p.st, sd = p.sd;
-    const size_t r = (size_t)p.r0;
-    float *const g = s->g + 384 * r, *const zc = s->zc + 96 * r, *const z2 = s->z2 + 96 * r, *const fn = s->fn + r,
-          *const h256 = s->h256 + 256 * r, *const qkv = s->qkv + 768 * r, *const vg = s->vg + 768 * r, *const g1 = s->g1 + 384 * r,
-          *const mat = s->mat + 96 * r, *const t256 = s->t256 + 256 * r, *const t256b = s->t256b + 256 * r,
-          *const t128a = s->t128a + 128 * r, *const t128b = s->t128b + 128 * r, *const delta = s->delta + 128 * r,
-          *const outg = s->outg + 3 * OGLD * r, *const outng = s->outng + 160 * r, *const cat = s->cat + 256 * r,
-          *const cat2 = s->cat2 + 256 * r;
-    float *const catc = p.catc + 256 * r, *const cato = p.cato + 256 * r, *const ng = catc + 128;
-    const NodeTab ntp{nt.node_env + r, nt.node_limb + r, nt.node_mnode + r, nt.trav, nt.TM};
-    auto fork = [&]() { if (!one_stream && sd != st) { (void)hipEventRecord(p.ev_fork, st); (void)hipStreamWaitEvent(sd, p.ev_fork, 0); } };
-    auto join = [&]() { if (!one_stream && sd != st) { (void)hipEventRecord(p.ev_join, sd); (void)hipStreamWaitEvent(st, p.ev_join, 0); } };
-    int rc = SGRL_OK;
-    float* const scratch = qkv;         // small path: [N, 576] Gram triangle / [N, 1024] per-node matrices (spans qkv | vg)
-#define G(...) do { rc = small ? small_gemm(st, __VA_ARGS__) : launch_gemm(st, __VA_ARGS__); if (rc != SGRL_OK) return rc; } while (0)
-    auto gram_gemm = [&](const float* W_, const float* b_, float* C_, int ldc_, int N_) -> int {
-      if (!small) return launch_gemm_gram(st, zc, W_, b_, C_, ldc_, N, N_, fn);
-      hipLaunchKernelGGL(k_gram576, dim3((N + 3) / 4), dim3(256), 0, st, zc, s->d_tri, scratch, fn, N);
-      return small_gemm(st, scratch, GK, W_, GK, b_, C_, ldc_, N, N_, GK, EPI_RELU);
-    };
-    // linear4 / linear2_m + equivariant contraction; linear2 + residual + LayerNorm
-    auto equiv_gemm = [&](const float* A_, const float* W_, const float* b_) -> int {
-      if (!small) return launch_gemm_equiv(st, A_, 256, W_, 256, b_, N, 256, fn, z2, mat);
-      const int r_ = small_gemm(st, A_, 256, W_, 256, b_, scratch, 1024, N, 1024, 256, EPI_ROWDIV, fn);
-      if (r_ != SGRL_OK) return r_;
-      hipLaunchKernelGGL(k_zmat_perm, dim3(N), dim3(128), 0, st, z2, scratch, mat);
-      return SGRL_OK;
-    };
-#define GG(W_, b_, C_, ldc_, N_) do { rc = gram_gemm(W_, b_, C_, ldc_, N_); if (rc != SGRL_OK) return rc; } while (0)
-    // projection site: Z (and Z2) = X . [Wp; Wq]^T on the matrix cores (stacked, zero-padded weights), written straight into
-    // the compact rows zc / z2 the Gram GEMM and the equivariant epilogues read
-    auto pg = [&](const float* X, int ldx, int K, int site, float* z2_) -> int {
-      if (K % 16 != 0 || (ldx & 3)) return sfail(SGRL_ERR_ARG, "projection: K must be a multiple of 16 and rows 16-byte aligned");
-      if (small) {          // rows 0..29 / 32..61 of the stacked operand: two narrow products (columns 30, 31 hold gdir)
-        int r_ = small_gemm(st, X, ldx, site_w(site), K, nullptr, zc, ZD, N3, 30, K);
-        if (r_ == SGRL_OK && z2_) r_ = small_gemm(st, X, ldx, site_w(site) + (size_t)32 * K, K, nullptr, z2_, ZD, N3, 30, K);
-        return r_;
-      }
-      GemmArgs a{X, ldx, site_w(site), K, nullptr, zc, ZD, N3, z2_ ? 64 : 32, K, EPI_ZSPLIT, nullptr, z2_, ZD};
-      if (g_gemm.form == SGRL_SET_FORM_F16X3 && gemm_use_split())      // 128 x 64 tiles, four waves, W pre-split
-        hipLaunchKernelGGL(kProjH, dim3(((a.M + 127) / 128) * ((a.N + 63) / 64)), dim3(256), kProjHLds, st, with_words(a));
-      else
-        GemmKernels<EPI_ZSPLIT>::launch(st, a);
-      return SGRL_OK;
-    };
-#define PG(...) do { rc = pg(__VA_ARGS__); if (rc != SGRL_OK) return rc; } while (0)
-#define GS(...) do { rc = small ? small_gemm(sd, __VA_ARGS__) : launch_gemm(sd, __VA_ARGS__); if (rc != SGRL_OK) return rc; } while (0)
-    const int l = k / 4;
-    if (k < 4 * SGRL_SET_LAYERS && k % 4 == 0) {
-      // --- attention ---
-      fork();
-      GS(g, D, s->WL(l, SGRL_SET_VG_W), D, nullptr, vg, 256, N3, 256, D);          // U = g . (Wgo_h Wvg_h)^T, both heads
-      if (chain) {
-        rc = launch_site(st, g, D, D, site_w(2 * l), zc, nullptr, fn, s->WL(l, SGRL_SET_A_LG1_W), s->WL(l, SGRL_SET_A_LG1_B), 256,
-                         s->WL(l, SGRL_SET_A_LG2_W), s->WL(l, SGRL_SET_A_LG2_B), catc, 256, N);
-        if (rc != SGRL_OK) return rc;
-        if (l == 0 && p.ev_site0) (void)hipEventRecord(p.ev_site0, st);
-      } else {
-        PG(g, D, D, 2 * l, nullptr);
-        GG(s->WL(l, SGRL_SET_A_LG1_W), s->WL(l, SGRL_SET_A_LG1_B), h256, 256, 256);
-        G(h256, 256, s->WL(l, SGRL_SET_A_LG2_W), 256, s->WL(l, SGRL_SET_A_LG2_B), catc, 256, N, 128, 256);
-      }
-      G(catc, 256, s->WL(l, SGRL_SET_QKV_W), 256, s->WL(l, SGRL_SET_QKV_B), qkv, 768, N, 768, 256, EPI_ROWDIV, fn);
-      join();
-    } else if (k < 4 * SGRL_SET_LAYERS && k % 4 == 1) {
-      // (k_attention finds its rows through the environment table: whole-batch base pointers)
-      const EnvTab etp{et.env_off + p.e0, et.env_L + p.e0, et.env_relb + p.e0};
-      hipLaunchKernelGGL(k_attention, dim3(p.ne), dim3(256), 0, st, s->qkv, s->vg, s->gdir, s->d_relb, etp, l == 0 ? 1 : 0,
-                         s->WL(l, SGRL_SET_NGOUT_B), s->WL(l, SGRL_SET_A_GD), s->stop_after == 2 * l ? s->delta : (float*)nullptr,
-                         s->g1, p.catc + 128, 256, s->WL(l, SGRL_SET_N1_W), s->WL(l, SGRL_SET_N1_B));
-      if (s->stop_after == 2 * l) return kStop;      // probe: g1 = attention's vector output, delta = its scalar output
-    } else if (k < 4 * SGRL_SET_LAYERS && k % 4 == 2) {
-      // --- equivariant feed-forward ---
-      if (chain) {
-        rc = launch_site(st, g1, D, D, site_w(2 * l + 1), zc, z2, fn, s->WL(l, SGRL_SET_F_LG1_W), s->WL(l, SGRL_SET_F_LG1_B), 256,
-                         s->WL(l, SGRL_SET_F_LG2_W), s->WL(l, SGRL_SET_F_LG2_B), catc, 256, N);
-        if (rc != SGRL_OK) return rc;
-      } else {
-        PG(g1, D, D, 2 * l + 1, z2);
-        GG(s->WL(l, SGRL_SET_F_LG1_W), s->WL(l, SGRL_SET_F_LG1_B), h256, 256, 256);
-        G(h256, 256, s->WL(l, SGRL_SET_F_LG2_W), 256, s->WL(l, SGRL_SET_F_LG2_B), catc, 256, N, 128, 256);
-      }
-    } else if (k < 4 * SGRL_SET_LAYERS) {
-      fork();
-      if (chain) {
-        // side: linear1 -> ReLU -> linear2 -> / fn -> residual + norm2, the new ng into the other buffer; main: linear3 -> ReLU ->
-        // linear4 -> contraction with z, then the update of the vector stream
-        rc = launch_chain_ln(sd, catc, 256, 256, s->WL(l, SGRL_SET_L1_W), s->WL(l, SGRL_SET_L1_B), s->WL(l, SGRL_SET_L2_W), s->WL(l, SGRL_SET_L2_B),
-                             fn, ng, 256, s->WL(l, SGRL_SET_N2_W), s->WL(l, SGRL_SET_N2_B), N, cato + 128);
-        if (rc == SGRL_OK && chain_eq) {
-          rc = launch_chain_equiv(st, catc, 256, 256, s->WL(l, SGRL_SET_L3_W), s->WL(l, SGRL_SET_L3_B), s->WL(l, SGRL_SET_L4_W), s->WL(l, SGRL_SET_L4_B),
-                                  fn, z2, mat, N, fuse_update ? g : (float*)nullptr, g1, s->WL(l, SGRL_SET_L5_W),
-                                  l == SGRL_SET_LAYERS - 1 ? outg : (float*)nullptr);
-        } else if (rc == SGRL_OK) {
-          rc = launch_gemm(st, catc, 256, s->WL(l, SGRL_SET_L3_W), 256, s->WL(l, SGRL_SET_L3_B), t256, 256, N, 256, 256, EPI_RELU);
-          if (rc == SGRL_OK) rc = equiv_gemm(t256, s->WL(l, SGRL_SET_L4_W), s->WL(l, SGRL_SET_L4_B));
-        }
-        if (rc != SGRL_OK) return rc;
-        if (!(chain_eq && fuse_update))
-          hipLaunchKernelGGL(k_equiv, dim3((N + 7) / 8), dim3(128), 0, st, mat, s->WL(l, SGRL_SET_L5_W), g1, g,
-                             l == SGRL_SET_LAYERS - 1 ? outg : (float*)nullptr, N);
-        join();
-        std::swap(p.catc, p.cato);
-        s->cat_cur = p.catc;
-        if (s->stop_after == 2 * l + 1) return kStop;  // probe: g / ng (= the current cat[:, 128:]) are this layer's outputs
-        return SGRL_OK;
-      }
-      GS(cat, 256, s->WL(l, SGRL_SET_L1_W), 256, s->WL(l, SGRL_SET_L1_B), t256b, 256, N, 256, 256, EPI_RELU);
-      G(cat, 256, s->WL(l, SGRL_SET_L3_W), 256, s->WL(l, SGRL_SET_L3_B), t256, 256, N, 256, 256, EPI_RELU);
-      // linear2 carries the scalar stream's second residual + norm2 in its epilogue (ng rewritten in place): it must not start
-      // before linear3 -- the other reader of cat = [inv | ng] -- is done
-      if (!one_stream) {
-        (void)hipEventRecord(s->ev_l3, st);
-        (void)hipStreamWaitEvent(sd, s->ev_l3, 0);
-      }
-      if (small) {
-        rc = small_gemm(st, t256b, 256, s->WL(l, SGRL_SET_L2_W), 256, s->WL(l, SGRL_SET_L2_B), delta, 128, N, 128, 256, EPI_ROWDIV, fn);
-        if (rc != SGRL_OK) return rc;
-        hipLaunchKernelGGL(k_add_ln, dim3(lnb), dim3(256), 0, st, ng, 256, delta, 128, s->WL(l, SGRL_SET_N2_W),
-                           s->WL(l, SGRL_SET_N2_B), (float*)nullptr, 0, ng, 256, N);
-      } else {
-        rc = launch_gemm_ln(sd, t256b, 256, s->WL(l, SGRL_SET_L2_W), 256, s->WL(l, SGRL_SET_L2_B), N, 256, fn, ng, 256,
-                            s->WL(l, SGRL_SET_N2_W), s->WL(l, SGRL_SET_N2_B));
-        if (rc != SGRL_OK) return rc;
-      }
-      rc = equiv_gemm(t256, s->WL(l, SGRL_SET_L4_W), s->WL(l, SGRL_SET_L4_B));
-      if (rc != SGRL_OK) return rc;
-      hipLaunchKernelGGL(k_equiv, dim3((N + 7) / 8), dim3(128), 0, st, mat, s->WL(l, SGRL_SET_L5_W), g1, g,
-                         l == SGRL_SET_LAYERS - 1 ? outg : (float*)nullptr, N);
-      join();
-      if (s->stop_after == 2 * l + 1) return kStop;  // probe: g / ng (= cat[:, 128:]) are this layer's outputs
-    } else if (k == 4 * SGRL_SET_LAYERS) {
-      // final norm -> outng[:, 17:145]; head
-      hipLaunchKernelGGL(k_add_ln, dim3(lnb), dim3(256), 0, st, ng, 256, (const float*)nullptr, 0, s->W(SGRL_SET_FNORM_W),
-                         s->W(SGRL_SET_FNORM_B), (float*)nullptr, 0, outng + ngf, 160, N);
-      float* const hd = chain ? cato : cat2;     // the head's [l2g | l2ng] rows: the buffer the last norm2 did not write
-      fork();
-      if (chain) {
-        rc = launch_chain_ng(sd, outng, 160, 160, s->W(SGRL_SET_L1NG_W), s->W(SGRL_SET_L1NG_B), s->W(SGRL_SET_L2NG_W), s->W(SGRL_SET_L2NG_B),
-                             hd + 128, 256, N);
-        if (rc == SGRL_OK)
-          rc = launch_site(st, outg, OGLD, OGLD, site_w(6), zc, critic ? (float*)nullptr : z2, fn, s->W(SGRL_SET_L1G_W),
-                           s->W(SGRL_SET_L1G_B), 128, s->W(SGRL_SET_L2G_W), s->W(SGRL_SET_L2G_B), hd, 256, N);
-        if (rc != SGRL_OK) return rc;
-      } else {
-        GS(outng, 160, s->W(SGRL_SET_L1NG_W), 160, s->W(SGRL_SET_L1NG_B), t128b, D, N, D, 160, EPI_RELU);
-        GS(t128b, D, s->W(SGRL_SET_L2NG_W), D, s->W(SGRL_SET_L2NG_B), cat2 + 128, 256, N, D, D);
-        PG(outg, OGLD, OGLD, 6, critic ? (float*)nullptr : z2);
-        GG(s->W(SGRL_SET_L1G_W), s->W(SGRL_SET_L1G_B), t128a, D, D);
-        G(t128a, D, s->W(SGRL_SET_L2G_W), D, s->W(SGRL_SET_L2G_B), cat2, 256, N, D, D);
-      }
-      join();
-    } else if (critic) {
-      float* const hd = chain ? cato : cat2;
-      // slots reused by the critic head: DECG = decoder_ng.weight [256], L1M_B = decoder_ng.bias [1]
-      hipLaunchKernelGGL(k_q_head, dim3((N + 3) / 4), dim3(256), 0, st, hd, s->W(SGRL_SET_DECG), s->W(SGRL_SET_L1M_B), fn,
-                         ntp, act, act_ld, N);
-    } else {
-      float* const hd = chain ? cato : cat2;
-      const bool folded = !small && s->live && s->l2mf_w && head_fold;
-      if (folded) {
-        // decoder_g folded through linear2_m: the 1024-wide product and its contraction collapse into a 32-wide product
-        G(hd, 256, s->W(SGRL_SET_L1M_W), 256, s->W(SGRL_SET_L1M_B), t256, 256, N, 256, 256, EPI_RELU);
-        G(t256, 256, s->l2mf_w, 256, s->l2mf_b, mat, 32, N, 32, 256, EPI_ROWDIV, fn);
-        hipLaunchKernelGGL(k_head_out2, dim3((N + 3) / 4), dim3(128), 0, st, mat, z2, obs, obs_ld, ntp, act, act_ld, max_action, N);
-      } else if (chain && chain_eq) {
-        rc = launch_chain_equiv(st, hd, 256, 256, s->W(SGRL_SET_L1M_W), s->W(SGRL_SET_L1M_B), s->W(SGRL_SET_L2M_W), s->W(SGRL_SET_L2M_B), fn, z2,
-                                mat, N);
-      } else {
-        G(hd, 256, s->W(SGRL_SET_L1M_W), 256, s->W(SGRL_SET_L1M_B), t256, 256, N, 256, 256, EPI_RELU);
-        rc = equiv_gemm(t256, s->W(SGRL_SET_L2M_W), s->W(SGRL_SET_L2M_B));
-      }
-      if (rc != SGRL_OK) return rc;
-      if (!folded)
-        hipLaunchKernelGGL(k_head_out, dim3((N + 3) / 4), dim3(128), 0, st, mat, s->W(SGRL_SET_DECG), obs, obs_ld, ntp,
-                           act, act_ld, max_action, N);
-    }
-    return rc;
-  };
+  hipStream_t sd = f.sd = f.one_stream ? st : s->side;
+  Part whole = f.part(0, N, 0, s->n_env, st, sd, s->ev_fork, s->ev_join, nullptr);
+  f.prologue(whole);
   static const int split_mode = [] { const char* e = getenv("SGRL_SET_SPLIT"); return e && e[0] >= '0' && e[0] <= '3' ? e[0] - '0' : 1; }();
-  const bool split = split_mode != 0 && chain && !one_stream && s->stop_after < 0 && N >= kSplitMinNodes && s->split_node > 0 && s->split_node < N;
+  const bool split = split_mode != 0 && f.chain && !f.one_stream && s->stop_after < 0 && N >= kSplitMinNodes && s->split_node > 0 && s->split_node < N;
   s->last_split = split ? s->split_node : 0;
   if (!split) {
-    Part whole{0, N, 0, s->n_env, st, sd, s->ev_fork, s->ev_join, s->cat, s->cat2, nullptr};
     for (int k = 0; k < kStages; k++) {
-      const int rc = stage(whole, k);
+      const int rc = f.stage(whole, k);
       if (rc == kStop) return SGRL_OK;
       if (rc != SGRL_OK) return rc;
     }
   } else {
     const bool head_start = split_mode == 3;
-    Part a{0, s->split_node, 0, s->split_env, st, sd, s->ev_fork, s->ev_join, s->cat, s->cat2, head_start ? s->ev_split : (hipEvent_t) nullptr};
-    Part b{s->split_node, N - s->split_node, s->split_env, s->n_env - s->split_env, sd, st, s->ev_fork_b, s->ev_join_b, s->cat, s->cat2, nullptr};
+    Part a = f.part(0, s->split_node, 0, s->split_env, st, sd, s->ev_fork, s->ev_join, head_start ? s->ev_split : (hipEvent_t) nullptr);
+    Part b = f.part(s->split_node, N - s->split_node, s->split_env, s->n_env - s->split_env, sd, st, s->ev_fork_b, s->ev_join_b, nullptr);
     if (split_mode == 1) { a.sd = a.st; b.sd = b.st; }                  // every half on its own stream, siblings included
     if (!head_start) (void)hipEventRecord(s->ev_split, st);            // the embedding is done: the second half may start
     for (int k = 0; k <= kStages; k++) {
-      int rc = k < kStages ? stage(a, k) : SGRL_OK;
+      int rc = k < kStages ? f.stage(a, k) : SGRL_OK;
       if (rc != SGRL_OK) return rc;
       if (k == 0) (void)hipStreamWaitEvent(sd, s->ev_split, 0);
-      if (k > 0) rc = stage(b, k - 1);
+      if (k > 0) rc = f.stage(b, k - 1);
       if (rc != SGRL_OK) return rc;
     }
     (void)hipEventRecord(s->ev_merge, sd);
     (void)hipStreamWaitEvent(st, s->ev_merge, 0);
   }
-#undef GS
-#undef GG
-#undef G
-#undef PG
-  {
-    const hipError_t le = hipGetLastError();
-    if (le != hipSuccess)
-      return sfail(SGRL_ERR_HIP, std::string("kernel launch failed in sgrl_set_forward (") + hipGetErrorName(le) + ": " + hipGetErrorString(le) + ")");
-  }
+  const hipError_t le = hipGetLastError();
+  if (le != hipSuccess)
+    return sfail(SGRL_ERR_HIP, std::string("kernel launch failed in sgrl_set_forward (") + hipGetErrorName(le) + ": " + hipGetErrorString(le) + ")");
   return SGRL_OK;
 }
 
@@ -1425,18 +1417,19 @@ int sgrl_set_bind_params(sgrl_set* s, const sgrl_pack_seg* segs, int n_segs, con
       hipMemcpy(s->d_chunks, chunks.data(), sizeof(int2) * chunks.size(), hipMemcpyHostToDevice) != hipSuccess)
     return sfail(SGRL_ERR_HIP, "device allocation failed in sgrl_set_bind_params");
   s->wflat_floats = total_floats;
+  // floats a slot holds: up to the next offset (or the end of the buffer)
+  std::vector<int64_t> bounds(offsets, offsets + n_offsets);
+  bounds.push_back(total_floats);
+  std::sort(bounds.begin(), bounds.end());
+  auto room = [&](int64_t off) { return *std::upper_bound(bounds.begin(), bounds.end(), off) - off; };
   {
     // the product matrices of the buffer (slot shapes: include/sgrl_set.h), for k_encode_rows.  A slot the bound network does not
     // fill (the critic has no linear1_m / linear2_m) is shorter than its matrix and is left out.
-    std::vector<int64_t> bounds(offsets, offsets + n_offsets);
-    bounds.push_back(total_floats);
-    std::sort(bounds.begin(), bounds.end());
     std::vector<sgrl_gemm::EncMat> mats;
     s->enc_index.clear();
     int rows_total = 0;
     auto add = [&](int64_t off, int rows, int K, int group = 1) {
-      const int64_t next = *std::upper_bound(bounds.begin(), bounds.end(), off);
-      if (next - off < (int64_t)rows * K) return;
+      if (room(off) < (int64_t)rows * K) return;
       mats.push_back(sgrl_gemm::EncMat{off, rows, K, rows_total, group});
       s->enc_index.emplace_back(off, rows_total);
       rows_total += rows;
@@ -1465,11 +1458,8 @@ int sgrl_set_bind_params(sgrl_set* s, const sgrl_pack_seg* segs, int n_segs, con
   for (int k = 0; k < SGRL_SET_NSITES; k++) s->site_ptr[k] = s->wflat + offsets[SGRL_SET_NW + k];
   {
     // the folded head exists when its slot is long enough for the [32, 256] matrix (an actor network; the critic binds a filler)
-    std::vector<int64_t> b2(offsets, offsets + n_offsets);
-    b2.push_back(total_floats);
-    std::sort(b2.begin(), b2.end());
     const int64_t ow = offsets[SGRL_SET_NW + SGRL_SET_NSITES], ob = offsets[SGRL_SET_NW + SGRL_SET_NSITES + 1];
-    const bool have = *std::upper_bound(b2.begin(), b2.end(), ow) - ow >= 32 * 256;
+    const bool have = room(ow) >= 32 * 256;
     s->l2mf_w = have ? s->wflat + ow : nullptr;
     s->l2mf_b = have ? s->wflat + ob : nullptr;
   }
@@ -1676,13 +1666,13 @@ int sgrl_set_debug_product(sgrl_set* s, int kind, int form, const float* A, int 
     return sfail(SGRL_ERR_HIP, "cannot raise the dynamic LDS limit of the tile kernels");
   TempWords tw;
   const std::vector<std::pair<int64_t, int>> index{{0, 0}};
-  g_gemm.form = form == 1 ? SGRL_SET_FORM_BF16X6 : form;
-  g_gemm.w_base = W;
-  g_gemm.w_words = nullptr; g_gemm.wsc = nullptr; g_gemm.enc_index = nullptr;
+  GemmCtx gx;
+  gx.form = form == 1 ? SGRL_SET_FORM_BF16X6 : form;
+  gx.w_base = W;
   if (form == SGRL_SET_FORM_F16X3) {
     if (ldw != K) return sfail(SGRL_ERR_ARG, "debug product: the two-piece form takes W rows of K contiguous floats");
     if (tw.make(st, W, N, K, kind == 4 ? 32 : 1) != SGRL_OK) return SGRL_ERR_HIP;
-    g_gemm.w_words = tw.w; g_gemm.wsc = tw.sc; g_gemm.enc_index = &index;
+    gx.w_words = tw.w; gx.wsc = tw.sc; gx.enc_index = &index;
   }
   int rc = SGRL_OK;
   if (form == 1) {
@@ -1696,13 +1686,13 @@ int sgrl_set_debug_product(sgrl_set* s, int kind, int form, const float* A, int 
     }
   } else if (kind <= 2) {
     if (N <= 64 || (K % 32) != 0) rc = sfail(SGRL_ERR_ARG, "debug product: the split kernels serve N > 64, K % 32 == 0");
-    else rc = launch_gemm(st, A, lda, W, ldw, bias, C, ldc, M, N, K, kind == 1 ? EPI_RELU : (kind == 2 ? EPI_ROWDIV : 0), rowdiv);
+    else rc = launch_gemm(gx, st, A, lda, W, ldw, bias, C, ldc, M, N, K, kind == 1 ? EPI_RELU : (kind == 2 ? EPI_ROWDIV : 0), rowdiv);
   } else if (kind == 3) {
     if (K != GK || ldw != GK || !aux_out) rc = sfail(SGRL_ERR_ARG, "debug product: Gram operand needs K = ldw = 576 and aux_out");
-    else rc = launch_gemm_gram(st, A, W, bias, C, ldc, M, N, aux_out);
+    else rc = launch_gemm_gram(gx, st, A, W, bias, C, ldc, M, N, aux_out);
   } else if (kind == 4) {
     if (N != 1024 || !rowdiv || !aux_in) rc = sfail(SGRL_ERR_ARG, "debug product: equivariant epilogue needs N = 1024, rowdiv, zq");
-    else rc = launch_gemm_equiv(st, A, lda, W, ldw, bias, M, K, rowdiv, aux_in, C);
+    else rc = launch_gemm_equiv(gx, st, A, lda, W, ldw, bias, M, K, rowdiv, aux_in, C);
   } else if (kind == 5) {
     if (N != 64 || !aux_out || (K % 16) != 0) rc = sfail(SGRL_ERR_ARG, "debug product: stacked projections need N = 64 and aux_out");
     else {
@@ -1710,18 +1700,17 @@ int sgrl_set_debug_product(sgrl_set* s, int kind, int form, const float* A, int 
       if (form == SGRL_SET_FORM_F16X3) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(kProjH), hipFuncAttributeMaxDynamicSharedMemorySize, kProjHLds) != hipSuccess)
           rc = sfail(SGRL_ERR_HIP, "debug product: LDS limit");
-        else hipLaunchKernelGGL(kProjH, dim3(((M + 127) / 128) * 1), dim3(256), kProjHLds, st, with_words(a));
-      } else if (GemmKernels<EPI_ZSPLIT>::raise_lds_limits()) GemmKernels<EPI_ZSPLIT>::launch(st, a);
+        else hipLaunchKernelGGL(kProjH, dim3(((M + 127) / 128) * 1), dim3(256), kProjHLds, st, with_words(gx, a));
+      } else if (GemmKernels<EPI_ZSPLIT>::raise_lds_limits()) GemmKernels<EPI_ZSPLIT>::launch(gx, st, a);
       else rc = sfail(SGRL_ERR_HIP, "debug product: LDS limit");
     }
   } else if (kind == 6) {
     if (N != 128 || !rowdiv || !aux_in) rc = sfail(SGRL_ERR_ARG, "debug product: LayerNorm epilogue needs N = 128, rowdiv, ln_w | ln_b");
-    else rc = launch_gemm_ln(st, A, lda, W, ldw, bias, M, K, rowdiv, C, ldc, aux_in, aux_in + 128);
+    else rc = launch_gemm_ln(gx, st, A, lda, W, ldw, bias, M, K, rowdiv, C, ldc, aux_in, aux_in + 128);
   } else rc = sfail(SGRL_ERR_ARG, "debug product: unknown kind");
   const hipError_t le = hipGetLastError();
   if (rc == SGRL_OK && le != hipSuccess) rc = sfail(SGRL_ERR_HIP, std::string("debug product: launch failed: ") + hipGetErrorString(le));
   (void)hipStreamSynchronize(st);
-  g_gemm.enc_index = nullptr;
   return rc;
 }
 

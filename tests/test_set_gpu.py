@@ -534,3 +534,100 @@ def test_the_ab_product_forms_of_the_environment_are_forwards_too(mode):
     for l in lines:
         before, after = (float(x) for x in re.findall(r"(?:before the change|weights_changed\(\)) ([0-9.e+-]+|nan)", l))
         assert before < 2e-6 and after < 2e-6, l
+
+
+CHAIN_ARM_BATCH = (["3d_walker_7_full", "3d_walker_2_right_leg_left_knee"], [4, 4])     # 36 nodes
+
+
+def _chain_arm_inputs():
+    """(obs [8, 287], action [8, 21], rows): oracle.formula.synth_obs observations and uniform actions, zero padded to the widest morphology."""
+    from oracle.formula import synth_obs
+    from sgrl_amd import mjcf
+    names, counts = CHAIN_ARM_BATCH
+    Ls = [mjcf.load_asset(n).num_limbs for n in names]
+    obs = np.zeros((sum(counts), 41 * max(Ls)), dtype=np.float32)
+    action = np.zeros((sum(counts), 3 * max(Ls)), dtype=np.float32)
+    rows, r = [], 0
+    for k, (n, c, L) in enumerate(zip(names, counts, Ls)):
+        obs[r:r + c, :41 * L] = synth_obs(L, c, 700 + k)
+        action[r:r + c, :3 * L] = np.random.RandomState(710 + k).uniform(-1, 1, size=(c, 3 * L))
+        rows.append((n, r, c, L))
+        r += c
+    return obs, action, rows
+
+
+def _chain_arm_child(out_path):
+    """One arm of test_the_unfused_tile_path_is_a_forward_too: the actor and the twin critics on the tile kernels at 36 nodes."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import torch
+    from oracle.formula import apply_formula_
+    from sgrl_amd import graph as G, mjcf
+    from sgrl_amd.set_hip import HipSetActor, HipSetCritic
+    from sgrl_amd.set_policy import make_critic, make_policy
+    names, counts = CHAIN_ARM_BATCH
+    obs, action, _ = _chain_arm_inputs()
+    obs, action = torch.from_numpy(obs).cuda(), torch.from_numpy(action).cuda()
+    gds = [G.getGraphDict(mjcf.load_asset(n).parents, TRAV, [], device=torch.device("cuda:0")) for n in names]
+    pol = apply_formula_(make_policy(device="cuda:0", use_hip=True).eval())
+    crit = apply_formula_(make_critic(device="cuda:0").eval())
+    act, qs = HipSetActor(pol), HipSetCritic(crit)
+    act.scale_redos()
+    for h in (act, qs.q1, qs.q2):
+        h.configure(gds, counts)
+        h.debug_small_nodes(0)
+    a = act.forward_batch(obs)
+    q1, q2 = qs.forward_batch(obs, action)
+    torch.cuda.synchronize()
+    np.savez(out_path, a=a.cpu().numpy(), q1=q1.cpu().numpy(), q2=q2.cpu().numpy(), redos=act.scale_redos(), split=act.last_split())
+
+
+def test_the_unfused_tile_path_is_a_forward_too(ctx, tmp_path):
+    """SGRL_SET_CHAIN=0 (read once per process: a child process each, one with it and one without) keeps every product of the tile path
+    a launch of its own -- the comparison arm bench.py and INTEGRATION.md offer.  36 nodes of two morphologies with different limb
+    counts on the tile kernels: one partial 128-row product tile, one partial 64-row chain workgroup.  Both arms: actions against the
+    float64 NumPy oracle, the twin critics' values against the module's PyTorch path (the reference of
+    test_critic_hip_path_matches_reference_fixtures_and_torch_path, itself held to the reference's fixtures by tests/test_set_critic.py)."""
+    import subprocess
+    import sys
+    torch, pol, graphs, keys, z = ctx
+    from oracle import set_ref
+    from oracle.formula import apply_formula_
+    from sgrl_amd import graph as G
+    from sgrl_amd.set_policy import make_critic
+    obs, action, rows = _chain_arm_inputs()
+    sd = set_ref.formula_state_dict(keys, np.float64)
+    crit = apply_formula_(make_critic(device="cpu", use_hip=False).eval())
+    ref = {}
+    for n, r0, c, L in rows:
+        a64 = set_ref.set_actor_forward(sd, obs[r0:r0 + c, :41 * L].astype(np.float64), graphs[n]["traversals"],
+                                        np.array(graphs[n]["relation"], dtype=np.float32).astype(np.float64))
+        crit.change_morphology(_gd(torch, graphs[n], "cpu"))
+        with torch.no_grad():
+            q1, q2 = crit(torch.from_numpy(obs[r0:r0 + c, :41 * L]), torch.from_numpy(action[r0:r0 + c, :3 * L]))
+        ref[n] = (a64, q1.numpy(), q2.numpy())
+    got = {}
+    for arm in ("0", None):
+        env = dict(os.environ)
+        env.pop("SGRL_SET_CHAIN", None)
+        if arm is not None:
+            env["SGRL_SET_CHAIN"] = arm
+        out = os.path.join(str(tmp_path), "chain_%s.npz" % arm)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), out], env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout + r.stderr
+        o = got[arm] = np.load(out)
+        assert int(o["redos"]) == 0 and int(o["split"]) == 0, (arm, int(o["redos"]), int(o["split"]))
+        for n, r0, c, L in rows:
+            a64, q1, q2 = ref[n]
+            errs = [np.abs(o["a"][r0:r0 + c, :3 * L] - a64).max(), np.abs(o["q1"][r0:r0 + c, :L] - q1).max(), np.abs(o["q2"][r0:r0 + c, :L] - q2).max()]
+            print("SGRL_SET_CHAIN=%s %s: |a - f64| %.3e  |q1 - torch| %.3e  |q2 - torch| %.3e  (max |q| %.3e)" % (arm, n, *errs, np.abs(q1).max()))
+            assert max(errs) < TOL, (arm, n, errs)
+            assert max(errs[1:]) < 2e-4 * np.abs(q1).max(), (arm, n, errs)       # the critic test's bound against the PyTorch path (|q| ~ 3e-3)
+            assert (o["a"][r0:r0 + c, 3 * L:] == 0).all() and (o["q1"][r0:r0 + c, L:] == 0).all() and (o["q2"][r0:r0 + c, L:] == 0).all(), (arm, n)
+    print("largest difference between the arms: actions %.3e, q1 %.3e, q2 %.3e" % tuple(
+        np.abs(got["0"][k] - got[None][k]).max() for k in ("a", "q1", "q2")))
+
+
+if __name__ == "__main__":
+    import sys
+    _chain_arm_child(sys.argv[1])

@@ -1,5 +1,5 @@
 """GPU time of one SET actor forward at the TD3 update's batch (100 environments of one morphology) and at one environment,
-replayed from a hipGraph; run with SGRL_SET_SMALL_NODES=0 for the 128 x 128 tile path at every size."""
+replayed from a hipGraph (the small-batch products; HipSetActor.debug_small_nodes(0) puts a handle on the 128 x 128 tile path at every size)."""
 import os, sys, time
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, REPO)
