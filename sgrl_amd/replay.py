@@ -6,9 +6,37 @@ pointer `curr`, fill level `max_sample_size`, wrap-around overwrite -- but the s
 rollout's transition block never leaves HBM: `add_transitions` scatters a whole batch of rows in one indexed copy
 (the reference's `add_transition` row by row is also kept).  `state_arrays()` / `load_state_arrays()` exchange the
 exact `.npy` payloads of the reference's snapshot (reference common/trainer.py:261-322).
+
+`sample_into` is the read side as ONE library call (include/sgrl_replay.h sgrl_replay_sample): the draw from a counter RNG defined
+in integers, the gather of the five arrays and the target-policy noise go straight into tensors the caller owns.
 """
+import ctypes
+
 import numpy as np
 import torch
+
+from . import _lib
+
+
+class _Ring(ctypes.Structure):
+    """sgrl_ring of include/sgrl.h: a host struct of device pointers."""
+    _fields_ = [("obs", ctypes.c_void_p), ("action", ctypes.c_void_p), ("next_obs", ctypes.c_void_p), ("reward", ctypes.c_void_p),
+                ("done", ctypes.c_void_p), ("obs_dim", ctypes.c_int32), ("act_dim", ctypes.c_int32)]
+
+
+def _bind(L):
+    """The entry points of include/sgrl_replay.h (declared there, not in sgrl.h)."""
+    if getattr(L, "_replay_bound", False):
+        return
+    vp, ci, i64, u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64
+    L.sgrl_replay_sample.argtypes = [ctypes.POINTER(_Ring), i64, ci, u64, u64, i64, vp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, ci,
+                                     ctypes.c_float, vp]
+    L.sgrl_replay_sample.restype = ci
+    L.sgrl_replay_sample_launches.argtypes = []
+    L.sgrl_replay_sample_launches.restype = ci
+    L.sgrl_replay_last_error.argtypes = []
+    L.sgrl_replay_last_error.restype = ctypes.c_char_p
+    L._replay_bound = True
 
 
 class DeviceReplayBuffer(object):
@@ -121,6 +149,56 @@ class DeviceReplayBuffer(object):
         idx = self.draw_indices(batch_size, generator=generator)
         return dict(obs=self.obs_buffer[idx], action=self.action_buffer[idx], next_obs=self.next_obs_buffer[idx],
                     reward=self.reward_buffer[idx].reshape(-1, 1), done=self.done_buffer[idx].reshape(-1, 1))
+
+    def sample_into(self, out, batch_size, seed, draw, noise=None, noise_std=0.0, idx_out=None, max_candidates=0, idx_in=None):
+        """k = min(max_sample_size, batch_size) distinct rows, uniform over the filled part, written into rows 0 .. k-1 of the
+        caller's float32 CUDA tensors out["obs" / "action" / "next_obs" / "reward" / "done"] (reward and done [B, 1] or [B]; rows
+        from k on are left alone), and noise_std * N(0, 1) into columns 0 .. action_dim-1 of `noise` when given: one launch on
+        the current stream, no host synchronisation, no allocation (include/sgrl_replay.h sgrl_replay_sample).  The rows are a
+        function of (seed, draw, fill) alone -- Philox4x32-10 and sequential rejection of repeats in integers, restated in NumPy
+        by tests/test_replay_sample.py -- and land in `idx_out` (int64 CUDA [>= k]) when given; `idx_in` (int64 CUDA [>= k])
+        replaces the draw (gather only).  Returns k.  There is no CPU fallback: a CPU buffer raises SgrlError."""
+        if self.device.type != "cuda":
+            raise _lib.SgrlError("sample_into needs a buffer on the GPU (no CPU fallback exists)")
+        fill = self.max_sample_size                     # folds a device-side writer's counters in
+        L = _lib.lib()
+        _bind(L)
+        k = min(fill, int(batch_size))
+        if fill == 0:                                   # an empty ring has no rows to hand out (sample() returns empty tensors)
+            return 0
+
+        def ptr(t, name, rows, cols, dtype=torch.float32):
+            if t is None:
+                return None, 0
+            if not (torch.is_tensor(t) and t.is_cuda and t.device == self.device and t.dtype == dtype):
+                raise _lib.SgrlError("sample_into: %s must be a %s tensor on %s" % (name, dtype, self.device))
+            if cols is None:                            # a vector: [n] or [n, 1]
+                if not (t.is_contiguous() and t.numel() >= rows and (t.dim() == 1 or (t.dim() == 2 and t.shape[1] == 1))):
+                    raise _lib.SgrlError("sample_into: %s must be a contiguous [>= %d] or [>= %d, 1] tensor" % (name, rows, rows))
+                return ctypes.c_void_p(t.data_ptr()), 1
+            if not (t.dim() == 2 and t.shape[0] >= rows and t.shape[1] >= cols and t.stride(1) == 1 and
+                    (t.shape[0] == 1 or t.stride(0) >= t.shape[1])):
+                raise _lib.SgrlError("sample_into: %s must be a row-major [>= %d, >= %d] tensor" % (name, rows, cols))
+            return ctypes.c_void_p(t.data_ptr()), int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+
+        rows = max(k, 0)
+        p_obs, ld_obs = ptr(out["obs"], "out['obs']", rows, self.obs_dim)
+        p_act, ld_act = ptr(out["action"], "out['action']", rows, self.action_dim)
+        p_next, ld_next = ptr(out["next_obs"], "out['next_obs']", rows, self.obs_dim)
+        p_rew, _ = ptr(out["reward"], "out['reward']", rows, None)
+        p_done, _ = ptr(out["done"], "out['done']", rows, None)
+        p_noise, ld_noise = ptr(noise, "noise", rows, self.action_dim)
+        p_iout, _ = ptr(idx_out, "idx_out", rows, None, torch.int64)
+        p_iin, _ = ptr(idx_in, "idx_in", rows, None, torch.int64)
+        ring = _Ring(self.obs_buffer.data_ptr(), self.action_buffer.data_ptr(), self.next_obs_buffer.data_ptr(),
+                     self.reward_buffer.data_ptr(), self.done_buffer.data_ptr(), self.obs_dim, self.action_dim)
+        mask = (1 << 64) - 1
+        rc = L.sgrl_replay_sample(ctypes.byref(ring), fill, int(batch_size), int(seed) & mask, int(draw) & mask, int(max_candidates),
+                                  p_iin, p_obs, ld_obs, p_act, ld_act, p_next, ld_next, p_rew, p_done, p_iout, p_noise, ld_noise,
+                                  float(noise_std), ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        if rc != 0:
+            raise _lib.SgrlError("sgrl_replay_sample failed (%d): %s" % (rc, L.sgrl_replay_last_error().decode()))
+        return k
 
     # ---- snapshot interchange with the reference's .npy files --------------------------------------------
     def state_arrays(self):

@@ -583,14 +583,27 @@ class GraphedUpdates(object):
         """Eager updates on a side stream (PyTorch's capture protocol).  They are REAL updates: the caller passes the first
         `iters` iterations of its schedule (`data_batch` may be a callable returning a fresh batch per iteration, `first_it`
         the index of the first one) instead of adding updates of its own.  Returns the loss dicts."""
+        return self._warm(key, graph, L, lambda sl, n: self._load(sl, data_batch() if callable(data_batch) else data_batch), iters, first_it)
+
+    def warm_from(self, key, graph, L, buffer, seed, draw, iters=3, first_it=0):
+        """`warm` with the slot filled by `buffer.sample_into` (replay.DeviceReplayBuffer): iteration n of the `iters` uses draw
+        number `draw + n`.  The buffer must hold at least a full batch."""
+        if buffer.max_sample_size < self.B:
+            raise RuntimeError("warm_from needs at least %d rows in the buffer" % self.B)
+        return self._warm(key, graph, L, lambda sl, n: self._load_from(sl, buffer, seed, draw + n), iters, first_it)
+
+    def _load_from(self, sl, buffer, seed, draw):
+        buffer.sample_into(sl["batch"], self.B, seed, draw, noise=sl["noise"], noise_std=self.agent.args.policy_noise)
+
+    def _warm(self, key, graph, L, load, iters, first_it):
         sl = self._slot(key, graph, L)
         self.agent.change_morphology(graph)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         outs = []
         with torch.cuda.stream(s):
-            for it in range(first_it, first_it + iters):
-                self._load(sl, data_batch() if callable(data_batch) else data_batch)
+            for n, it in enumerate(range(first_it, first_it + iters)):
+                load(sl, n)
                 outs.append(self.agent.update(sl["batch"], it, noise=sl["noise"], lazy_stats=True, skip_unused_critic_grads=True))
         torch.cuda.current_stream().wait_stream(s)
         self.warmed.add(key)
@@ -604,8 +617,30 @@ class GraphedUpdates(object):
         sl = self._slot(key, graph, L)
         if key not in self.warmed:
             raise RuntimeError("warm(%r, ...) every morphology before the first graphed update" % (key,))
-        flag = 0 if it % self.agent.args.policy_freq == 0 else 1
         self._load(sl, data_batch)
+        return self._replay(sl, key, graph, it)
+
+    def update_from(self, key, graph, L, buffer, it, seed, draw):
+        """`update` with the batch drawn by the library: the slot's static batch and noise tensors are filled by ONE
+        `buffer.sample_into(..., seed, draw, noise=...)` (replay.DeviceReplayBuffer, include/sgrl_replay.h) -- launched outside the
+        captured graph, before the replay -- instead of sample() + five copies + normal_().  What the graphs record is unchanged."""
+        if buffer.max_sample_size < self.B:             # short batch (buffer not yet filled): eager, on the k rows there are
+            self.agent.change_morphology(graph)
+            k, dev = buffer.max_sample_size, self.agent.device
+            e = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
+            batch = {"obs": e(k, 41 * L), "action": e(k, 3 * L), "next_obs": e(k, 41 * L), "reward": e(k, 1), "done": e(k, 1)}
+            noise = torch.zeros((k, 3 * L), dtype=torch.float32, device=dev)
+            buffer.sample_into(batch, k, seed, draw, noise=noise, noise_std=self.agent.args.policy_noise)
+            return self.agent.update(batch, it, noise=noise)
+        sl = self._slot(key, graph, L)
+        if key not in self.warmed:
+            raise RuntimeError("warm(%r, ...) every morphology before the first graphed update" % (key,))
+        self._load_from(sl, buffer, seed, draw)
+        return self._replay(sl, key, graph, it)
+
+    def _replay(self, sl, key, graph, it):
+        """Everything of a graphed update after the slot's static tensors have been filled."""
+        flag = 0 if it % self.agent.args.policy_freq == 0 else 1
         # A graph bakes the addresses of the SET handles' workspaces.  They only ever grow, and every morphology is run eagerly
         # before any capture -- but a graph captured before a LATER regrowth would fault on replay (a GPU memory fault, not an
         # exception): the workspaces' sizes are compared with those at capture time and such a graph is captured again.

@@ -23,12 +23,18 @@ from .td3 import Agent, default_train_args
 
 class DeviceTrainer(object):
     def __init__(self, env_names, envs_per_morph, args=None, seed=0, device="cuda:0", max_buffer_size=1000000,
-                 batch_size=None, dst=0, graph_updates=False, tune_gemms=False, rollout=None, lag_flag=True, **env_kw):
+                 batch_size=None, dst=0, graph_updates=False, tune_gemms=False, rollout=None, lag_flag=True, device_sampler=False,
+                 **env_kw):
         """graph_updates: replay the TD3 update from hipGraphs (td3.GraphedUpdates); tune_gemms: let PyTorch's TunableOp pick
         the rocBLAS / hipBLASLt algorithm per GEMM shape on first use (the defaults choose 256 x 256 tiles for the 700-row
         weight-gradient GEMMs of a 100-row update: 50 -> 38 ms per update, round 1).  batch_size: rows per TD3 update, default
         args.agent_batch_size = 256 (the reference's trainer.py:289-291).  lag_flag (GPU ranks): the round-finished flag is read one
-        step late instead of synchronising every collection step (rollout.TransitionSink); False = the immediate flag."""
+        step late instead of synchronising every collection step (rollout.TransitionSink); False = the immediate flag.
+        device_sampler (learner): every update of update_after_round takes its batch and its target-policy noise from ONE library call
+        (replay.DeviceReplayBuffer.sample_into, include/sgrl_replay.h) with seed = `seed` and draw = a counter incremented once per
+        update, instead of sample(generator=self.gen) and normal_().  Off by default: it changes which rows a seeded run samples,
+        and the learning curves have not been re-run on the new stream.  The draw counter is NOT part of a
+        snapshot: assigning tot_env_steps (how a resumed run restores its count) restarts it at draw = tot_env_steps."""
         import torch.distributed as dist
         self.dist = dist
         self.rank = dist.get_rank() if dist.is_initialized() else 0
@@ -72,6 +78,10 @@ class DeviceTrainer(object):
         self.rounds = 0
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(int(seed) * 7919 + 13)
+        self.device_sampler = bool(device_sampler) and self.is_learner
+        self.sample_seed = int(seed)
+        self.draw = 0                # draw number of the next update's batch (device_sampler)
+        self._eager_slots = {}       # morphology -> (batch tensors, noise) of the eager device-sampled updates
         self.last_losses = {}
         self.graphed = None
         if graph_updates and self.is_learner:
@@ -95,6 +105,7 @@ class DeviceTrainer(object):
         if self.is_learner:
             self._tot_base = int(v) - (self.sink.stored + self._updates)
         self._tot_synced = int(v)
+        self.draw = int(v)           # the draw counter is not in a snapshot: a resumed run starts at draw = tot_env_steps
 
     def sync_step_count(self):
         """Every rank learns the learner's count (called at the round ends and after the warm-up: rank-local logic that reads the
@@ -149,14 +160,23 @@ class DeviceTrainer(object):
                 for k in range(len(self.env_names)):
                     if k not in self.graphed.warmed and self.buffers[k].max_sample_size >= self.batch_size and per_morph_iter > 0:
                         n = min(2, per_morph_iter)
-                        outs = self.graphed.warm(k, self.graph_dicts[k], self.ro.env.num_limbs[k],
-                                                 lambda k=k: self.buffers[k].sample(self.batch_size, generator=self.gen), iters=n)
+                        if self.device_sampler:
+                            outs = self.graphed.warm_from(k, self.graph_dicts[k], self.ro.env.num_limbs[k], self.buffers[k],
+                                                          self.sample_seed, self.draw, iters=n)
+                            self.draw += n
+                        else:
+                            outs = self.graphed.warm(k, self.graph_dicts[k], self.ro.env.num_limbs[k],
+                                                     lambda k=k: self.buffers[k].sample(self.batch_size, generator=self.gen), iters=n)
                         self.last_losses[self.env_names[k]] = outs[-1]
                         start[k] = n
                         self._updates += n
             for k, name in enumerate(self.env_names):
                 self.agent.change_morphology(self.graph_dicts[k])
                 for it in range(start[k], per_morph_iter):
+                    if self.device_sampler:
+                        self.last_losses[name] = self._device_sampled_update(k, it)
+                        self._updates += 1
+                        continue
                     batch = self.buffers[k].sample(self.batch_size, generator=self.gen)
                     if self.graphed is not None and k in self.graphed.warmed:
                         self.last_losses[name] = self.graphed.update(k, self.graph_dicts[k], self.ro.env.num_limbs[k], batch, it)
@@ -170,6 +190,24 @@ class DeviceTrainer(object):
             self.ro.weights_changed()          # with the weights every rank rolls out next
         self.rounds += 1
         return per_morph_iter
+
+    def _device_sampled_update(self, k, it):
+        """One update of morphology k on a batch drawn by sample_into with (sample_seed, draw); the counter moves once per update."""
+        draw, buf, L = self.draw, self.buffers[k], self.ro.env.num_limbs[k]
+        self.draw += 1
+        if self.graphed is not None and k in self.graphed.warmed:
+            return self.graphed.update_from(k, self.graph_dicts[k], L, buf, it, self.sample_seed, draw)
+        sl = self._eager_slots.get(k)
+        if sl is None:               # per-morphology tensors kept by the trainer: nothing is allocated per update
+            z = lambda *sh: torch.zeros(sh, dtype=torch.float32, device=self.device)
+            B = self.batch_size
+            sl = self._eager_slots[k] = ({"obs": z(B, 41 * L), "action": z(B, 3 * L), "next_obs": z(B, 41 * L), "reward": z(B, 1),
+                                          "done": z(B, 1)}, z(B, 3 * L))
+        batch, noise = sl
+        n = buf.sample_into(batch, self.batch_size, self.sample_seed, draw, noise=noise, noise_std=self.args.policy_noise)
+        if n < self.batch_size:      # buffer not yet filled: the k rows there are (views of the kept tensors)
+            batch, noise = {name: t[:n] for name, t in batch.items()}, noise[:n]
+        return self.agent.update(batch, it, noise=noise)
 
     def broadcast_actor(self):
         if self.world == 1:
