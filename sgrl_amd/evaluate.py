@@ -13,9 +13,19 @@ The reference steps `num_envs_train` sub-environments (one per morphology) throu
 `evaluate()` returns the same dictionary (`performance/eval_return`, `performance/eval_length`: means over all
 contributed pairs).  Arrays stay on the device of the environment; the only host sync per step is the `all(done)` test,
 which the reference also performs.
+
+`DeviceEvaluator` lays the trajectories of one evaluation side by side instead: every environment belongs to a trajectory GROUP,
+the bookkeeping above is ONE launch per step (include/sgrl_eval.h sgrl_eval_record) with the `all(done)` test as a property of a
+group, and the number of open groups is read a step late through pinned memory -- at most `max_trajectory_length` engine steps
+per evaluation instead of up to `num_eval_trajectories` times that, and no host synchronisation in the loop.  `reduce_groups`
+turns the resulting state into the reference's dictionary.
 """
+import ctypes
+
 import numpy as np
 import torch
+
+from . import _lib
 
 
 class BatchedEvaluator(object):
@@ -57,3 +67,162 @@ class BatchedEvaluator(object):
         # np.mean of an empty list is nan (with a warning) in the reference as well
         return {"performance/eval_return": float(np.mean(returns)) if returns else float("nan"),
                 "performance/eval_length": float(np.mean(lengths)) if lengths else float("nan")}
+
+
+class _EvalState(ctypes.Structure):
+    """sgrl_eval_state of include/sgrl_eval.h: a host struct of device pointers."""
+    _fields_ = [(name, ctypes.c_void_p) for name in ("group", "done_ever", "ep_steps", "ep_reward", "acc", "remaining", "close_step",
+                                                     "open")]
+
+
+def _bind(L):
+    """The entry points of include/sgrl_eval.h (declared there, not in sgrl.h)."""
+    if getattr(L, "_eval_bound", False):
+        return
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    L.sgrl_eval_begin.argtypes = [ctypes.POINTER(_EvalState), ci, ci, vp]
+    L.sgrl_eval_begin.restype = ci
+    L.sgrl_eval_record.argtypes = [ctypes.POINTER(_EvalState), vp, vp, vp, ci, ci, ci, ci, vp]
+    L.sgrl_eval_record.restype = ci
+    L.sgrl_eval_record_launches.argtypes = []
+    L.sgrl_eval_record_launches.restype = ci
+    L.sgrl_eval_last_error.argtypes = []
+    L.sgrl_eval_last_error.restype = ctypes.c_char_p
+    L._eval_bound = True
+
+
+def _host(a, dtype):
+    if torch.is_tensor(a):
+        a = a.detach().cpu().numpy()
+    return np.asarray(a, dtype=dtype).reshape(-1)
+
+
+def reduce_groups(ep_reward, ep_steps, group, close_step, env_morph=None, names=None):
+    """The reference's evaluation dictionary from the state of a grouped evaluation (tensors or NumPy arrays, any device; the
+    reduction itself runs on the host in float64): means of `ep_reward` / `ep_steps` over the environments whose group completed
+    (`close_step[group] != 0`) -- a trajectory in which some sub-environment never finished contributes nothing (reference
+    common/trainer.py:139-145) -- and NaN when no group completed, as np.mean of the reference's empty lists.  With `env_morph`
+    (morphology id per environment) and `names` also `performance/eval_return/<name>` and `performance/eval_length/<name>`: the
+    same means over the environments of one morphology."""
+    ret, length = _host(ep_reward, np.float64), _host(ep_steps, np.float64)
+    grp, closed = _host(group, np.int64), _host(close_step, np.int64) != 0
+    keep = closed[grp]
+
+    def mean(a, m):
+        return float(a[m].mean()) if m.any() else float("nan")
+    out = {"performance/eval_return": mean(ret, keep), "performance/eval_length": mean(length, keep)}
+    if env_morph is not None and names is not None:
+        morph = _host(env_morph, np.int64)
+        for k, name in enumerate(names):
+            m = keep & (morph == k)
+            out["performance/eval_return/%s" % name] = mean(ret, m)
+            out["performance/eval_length/%s" % name] = mean(length, m)
+    return out
+
+
+class DeviceEvaluator(object):
+    """All trajectories of one evaluation in one batched pass on the device (there is no CPU fallback)."""
+
+    def __init__(self, ro, act_fn=None, num_eval_trajectories=10, max_trajectory_length=1000, max_episode_steps=1000, group=None):
+        """ro: a rollout.Rollout built with envs_per_morph = num_eval_trajectories (or anything with its surface: `device`,
+        `env.num_envs` / `env.env_morph` / `env.env_names` / `env.morph_slices`, `reset()`, `step(actions)`, `policy_forward(obs)`).
+        act_fn(obs) -> actions; default ro.policy_forward, the deterministic policy (no exploration noise).  group: trajectory
+        group id per environment; default = an environment's index within its morphology's slice, so that every group holds one
+        environment of every morphology -- the reference's set of sub-environments."""
+        self.ro = ro
+        self.act_fn = act_fn if act_fn is not None else ro.policy_forward
+        self.num_eval_trajectories = int(num_eval_trajectories)
+        self.max_trajectory_length = int(max_trajectory_length)
+        self.max_episode_steps = int(max_episode_steps)
+        env = ro.env
+        n, n_groups = int(env.num_envs), self.num_eval_trajectories
+        if n_groups < 1 or self.max_trajectory_length < 1 or self.max_episode_steps < 1:
+            raise ValueError("num_eval_trajectories, max_trajectory_length and max_episode_steps must be at least 1")
+        if group is None:
+            g = np.zeros(n, dtype=np.int64)
+            for sl in env.morph_slices:
+                g[sl] = np.arange(sl.stop - sl.start)
+        else:
+            g = np.asarray(group.detach().cpu().numpy() if torch.is_tensor(group) else group)
+            if g.dtype.kind not in "iu":
+                raise ValueError("group ids must be integers, not %s" % g.dtype)
+            if g.shape != (n,):
+                raise ValueError("group must hold one id per environment (%d), not shape %s" % (n, g.shape))
+        if g.min() < 0 or g.max() >= n_groups:
+            raise ValueError("group ids must lie in 0 .. %d (num_eval_trajectories - 1)" % (n_groups - 1))
+        members = np.bincount(g, minlength=n_groups)
+        if (members == 0).any():
+            raise ValueError("trajectory group(s) %s have no environment: they could never complete" % np.nonzero(members == 0)[0].tolist())
+        self.device = torch.device(ro.device)
+        if self.device.type != "cuda":
+            raise _lib.SgrlError("DeviceEvaluator needs a rollout on the GPU (no CPU fallback exists)")
+        self.n_env, self.n_groups = n, n_groups
+        self.env_morph = np.asarray(env.env_morph, dtype=np.int64)
+        self.names = list(env.env_names)
+        z = lambda m, dtype: torch.zeros(m, dtype=dtype, device=self.device)
+        self.group = torch.from_numpy(g.astype(np.int32)).to(self.device)
+        self.done_ever, self.ep_steps = z(n, torch.uint8), z(n, torch.int64)
+        self.ep_reward, self.acc = z(n, torch.float64), z(n, torch.float64)
+        self.remaining, self.close_step, self.open = z(n_groups, torch.int32), z(n_groups, torch.int32), z(1, torch.int32)
+        self._state = _EvalState(*[t.data_ptr() for t in (self.group, self.done_ever, self.ep_steps, self.ep_reward, self.acc,
+                                                          self.remaining, self.close_step, self.open)])
+        # the open-group count of a step, fetched behind an event and read one step late (rollout.TransitionSink's lag_flag)
+        self._lag_slots = [(torch.zeros(1, dtype=torch.int32).pin_memory(), torch.cuda.Event()) for _ in range(2)]
+        self.early_stop = True
+        self.last_steps = 0
+        self._L = _lib.lib()
+        _bind(self._L)
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise _lib.SgrlError("%s failed (%d): %s" % (what, rc, self._L.sgrl_eval_last_error().decode()))
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def begin(self):
+        self._check(self._L.sgrl_eval_begin(ctypes.byref(self._state), self.n_env, self.n_groups, self._stream()), "sgrl_eval_begin")
+
+    def record(self, reward, done, step):
+        """One step's reward (float32, or float64 for parity tests) and done (bool / uint8) of every environment: one launch."""
+        if reward.dtype not in (torch.float32, torch.float64) or not reward.is_contiguous():
+            reward = reward.to(torch.float32).contiguous()
+        if done.dtype == torch.bool:
+            done = done.contiguous().view(torch.uint8)
+        elif done.dtype != torch.uint8 or not done.is_contiguous():
+            done = (done != 0).contiguous().view(torch.uint8)
+        if reward.numel() != self.n_env or done.numel() != self.n_env or reward.device != self.device or done.device != self.device:
+            raise _lib.SgrlError("record: reward and done must hold one value per environment on %s" % self.device)
+        p = ctypes.c_void_p(reward.data_ptr())
+        f32 = reward.dtype == torch.float32
+        self._check(self._L.sgrl_eval_record(ctypes.byref(self._state), p if f32 else None, None if f32 else p,
+                                             ctypes.c_void_p(done.data_ptr()), self.n_env, self.n_groups, int(step),
+                                             self.max_episode_steps, self._stream()), "sgrl_eval_record")
+
+    @torch.no_grad()
+    def evaluate(self, early_stop=None):
+        """reset, then at most max_trajectory_length steps of act_fn / step / record; the loop ends when the open-group count read
+        one step late is 0 (steps taken after the last group closed change nothing: their groups are frozen); ONE synchronisation
+        after the loop, then reduce_groups.  early_stop=False runs all max_trajectory_length steps.  `last_steps`: steps taken."""
+        early_stop = self.early_stop if early_stop is None else bool(early_stop)
+        obs = self.ro.reset()
+        self.begin()
+        stream = torch.cuda.current_stream(self.device)
+        prev, steps = None, 0
+        for step in range(self.max_trajectory_length):
+            obs, rew, done = self.ro.step(self.act_fn(obs))[:3]
+            self.record(rew, done, step)
+            steps += 1
+            if not early_stop:
+                continue
+            host, ev = self._lag_slots[step & 1]
+            host.copy_(self.open, non_blocking=True)
+            ev.record(stream)
+            if prev is not None:
+                prev[1].synchronize()           # recorded a whole step ago
+                if int(prev[0][0]) == 0:
+                    break
+            prev = (host, ev)
+        self.last_steps = steps
+        stream.synchronize()
+        return reduce_groups(self.ep_reward, self.ep_steps, self.group, self.close_step, self.env_morph, self.names)

@@ -42,6 +42,8 @@ class DeviceTrainer(object):
         self.dst = dst
         self.args = args if args is not None else default_train_args()
         self.env_names = list(env_names)
+        self.seed = int(seed)
+        self.eval_rollouts = {}      # tuple of names -> (settings, Rollout, DeviceEvaluator) of evaluate()
         torch.manual_seed(seed)               # same initial weights on every rank
         self.agent = Agent(self.args, device=device)
         if tune_gemms:
@@ -221,6 +223,33 @@ class DeviceTrainer(object):
                 n = p.numel()
                 p.data.copy_(flat[off:off + n].view_as(p))     # in place: the HIP actor reads the live storage
                 off += n
+
+    # ---- evaluation ------------------------------------------------------------------------------------
+    def evaluate(self, num_eval_trajectories=10, max_trajectory_length=1000, env_names=None, **env_kw):
+        """Periodic evaluation of the deterministic policy (reference common/trainer.py:80-146), all trajectories in one batched pass
+        on the device (evaluate.DeviceEvaluator): `num_eval_trajectories` environments per morphology, trajectory t = environment t of
+        every morphology.  env_names=None: the training morphologies; any other list: zero-shot evaluation on those (xml_paths= and
+        the other environment keywords pass through `env_kw`).  The environments are an evaluation Rollout of this trainer's own,
+        built on first use and kept per tuple of names: the training environments, their observations and the round's counters are
+        never touched.  That Rollout shares `self.agent.actor` and reads its live weights on every forward (it holds no packed copy),
+        so it always evaluates the current policy.  Returns the DeviceEvaluator dictionary: `performance/eval_return`,
+        `performance/eval_length` and the same two per morphology name.  RANK-LOCAL: no collective is issued -- every rank that calls
+        it evaluates its own copy of the actor on its own device, and a rank may call it alone."""
+        from .evaluate import DeviceEvaluator
+        names = tuple(self.env_names if env_names is None else env_names)
+        n_traj = int(num_eval_trajectories)
+        settings = (n_traj, repr(sorted(env_kw.items())))      # what the cached environments were built with
+        entry = self.eval_rollouts.get(names)
+        if entry is None or entry[0] != settings:
+            kw = dict(max_episode_steps=self.args.max_episode_steps)
+            kw.update(env_kw)
+            ro = Rollout(list(names), n_traj, policy=self.agent.actor, seed=self.seed + 7001, device=self.device, rank=self.rank,
+                         hold_weights=False, **kw)
+            ev = DeviceEvaluator(ro, num_eval_trajectories=n_traj, max_trajectory_length=max_trajectory_length,
+                                 max_episode_steps=kw["max_episode_steps"])
+            entry = self.eval_rollouts[names] = (settings, ro, ev)
+        entry[2].max_trajectory_length = int(max_trajectory_length)
+        return entry[2].evaluate()
 
     def train_round(self, max_steps=None, max_iters=None):
         """Collect until every environment has finished one episode (or max_steps), update, reset.  Returns a summary."""
