@@ -11,7 +11,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGRL_HIP_LIB", os.path.join(_HERE, "libsgrl_hip.so"))   # override: A/B benchmarking of builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["engine.hip", "set_actor.hip", "train_gemm.hip", "render.hip", "swat_actor.hip", "smp_actor.hip", "replay_sample.hip", "eval_record.hip"]
+SOURCES = ["engine.hip", "set_actor.hip", "train_gemm.hip", "render.hip", "swat_actor.hip", "smp_actor.hip", "replay_sample.hip", "eval_record.hip", "explore_actions.hip"]
 
 _lib = None
 
@@ -97,7 +97,7 @@ def build(verbose=False):
         table += "".join("SGRL_MEMBER(%d, %d, %s)\n" % (i, k, ", ".join(str(x) for x in d)) for k, d in enumerate(dims))
     _write_if_changed(os.path.join(CSRC, "spec_table.inc"), table)
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
-    hdrs += [os.path.join(_HERE, "..", "include", f) for f in ("sgrl.h", "sgrl_model.h", "sgrl_set.h", "sgrl_swat.h", "sgrl_smp.h", "sgrl_train.h", "sgrl_render.h", "sgrl_replay.h", "sgrl_eval.h")
+    hdrs += [os.path.join(_HERE, "..", "include", f) for f in ("sgrl.h", "sgrl_model.h", "sgrl_set.h", "sgrl_swat.h", "sgrl_smp.h", "sgrl_train.h", "sgrl_render.h", "sgrl_replay.h", "sgrl_eval.h", "sgrl_explore.h")
              if os.path.exists(os.path.join(_HERE, "..", "include", f))]
     newest_hdr = max(os.path.getmtime(d) for d in hdrs)
     objdir = os.path.join(_HERE, "..", "build", "obj")
@@ -187,6 +187,24 @@ def lib():
     L.sgrl_ingest_ws_words.argtypes = [ci]
     L.sgrl_ingest_ws_words.restype = ctypes.c_int64
     _lib = L
+    return L
+
+
+EXPLORE_GAUSS, EXPLORE_UNIFORM = 0, 1      # the modes of include/sgrl_explore.h
+
+
+def bind_explore(L):
+    """The entry points of include/sgrl_explore.h (declared there, not in sgrl.h; rollout.Rollout calls them)."""
+    if getattr(L, "_explore_bound", False):
+        return L
+    vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    L.sgrl_explore_actions.argtypes = [vp, ci, vp, ci, vp, ci, ci, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64, ci, cf, cf, cf, vp]
+    L.sgrl_explore_actions.restype = ci
+    L.sgrl_explore_actions_launches.argtypes = []
+    L.sgrl_explore_actions_launches.restype = ci
+    L.sgrl_explore_last_error.argtypes = []
+    L.sgrl_explore_last_error.restype = ctypes.c_char_p
+    L._explore_bound = True
     return L
 
 

@@ -8,6 +8,7 @@ import ctypes
 import numpy as np
 import torch
 
+from . import _lib
 from . import graph as G
 from .replay import DeviceReplayBuffer
 from .set_hip import HipSetActor
@@ -41,9 +42,17 @@ def hip_actor_class(policy):
 class Rollout(object):
     """Environments of one rank + the shared actor (SET, SWAT or SMP)."""
 
-    def __init__(self, env_names, envs_per_morph, policy=None, seed=0, device="cuda:0", rank=0, hold_weights=False, **env_kw):
+    def __init__(self, env_names, envs_per_morph, policy=None, seed=0, device="cuda:0", rank=0, hold_weights=False, device_noise=False,
+                 **env_kw):
+        """device_noise: the exploration noise (`explore_into`) and the warm-up actions (`random_actions`) come from ONE library call
+        each (include/sgrl_explore.h sgrl_explore_actions): a function of (`noise_seed` = seed, `noise_step`, global environment
+        number, slot) through the counter RNG, written straight into `self.actions`; `noise_step` is a host integer that moves by
+        one per call.  Off by default: `random_actions` and `add_exploration_noise` then draw from `self.gen` as they always did."""
         counts = [envs_per_morph] * len(env_names) if np.isscalar(envs_per_morph) else list(envs_per_morph)
         n_local = int(sum(counts))
+        self.device_noise = bool(device_noise)
+        if self.device_noise and torch.device(device).type != "cuda":
+            raise _lib.SgrlError("Rollout(device_noise=True) needs the GPU: sgrl_explore_actions has no CPU fallback")
         self.env = BatchedModularVecEnv(env_names, counts, seed=seed, device=device, env_id_base=rank * n_local, **env_kw)
         self.device = self.env.device
         self.policy = policy
@@ -66,6 +75,16 @@ class Rollout(object):
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(int(seed) * 1000003 + rank)
         self.obs = None
+        self.noise_seed = int(seed)
+        self.noise_step = 0            # step number of the next explore_into / random_actions (device_noise)
+        self.env_id_base = rank * n_local
+        self.act_len = None
+        if self.device_noise:
+            live = np.zeros(n, dtype=np.int32)
+            for k, sl in enumerate(self.env.morph_slices):
+                live[sl] = 3 * self.env.num_limbs[k]
+            self.act_len = torch.from_numpy(live).to(self.device)
+            self._explore_lib = _lib.bind_explore(_lib.lib())
 
     def _weights_fingerprint(self):
         """(storage address, in-place version counter) of every parameter: changes with optimizer steps, load_state_dict, copy_,
@@ -90,7 +109,10 @@ class Rollout(object):
         return self.obs
 
     def random_actions(self):
-        """i.i.d. U(-1, 1) per slot (reference trainer.py:95-102), zero in the padding slots."""
+        """i.i.d. U(-1, 1) per slot (reference trainer.py:95-102), zero in the padding slots.  device_noise: one launch, stream 3 of
+        (noise_seed, noise_step), which then moves on by one."""
+        if self.device_noise:
+            return self._explore(None, _lib.EXPLORE_UNIFORM, 0.0)
         self.actions.uniform_(-1.0, 1.0, generator=self.gen)
         self.actions.mul_(self.act_mask)
         return self.actions
@@ -106,6 +128,34 @@ class Rollout(object):
         """a + N(0, expl_noise) clipped to the action range (reference trainer.py:184-189)."""
         noise = torch.randn(actions.shape, device=self.device, generator=self.gen) * expl_noise
         return ((actions + noise).clamp_(-1.0, 1.0)) * self.act_mask
+
+    def explore_into(self, policy_actions, expl_noise=0.126):
+        """device_noise only: self.actions = clip(policy_actions + N(0, expl_noise), -1, 1), zero in the padding slots, in one launch
+        (stream 2 of (noise_seed, noise_step), which then moves on by one).  policy_actions: float32 [num_envs, >= action_max_len]
+        on this rollout's device with unit column stride; it may be self.actions.  Returns self.actions."""
+        if not self.device_noise:
+            raise _lib.SgrlError("explore_into needs Rollout(device_noise=True)")
+        return self._explore(policy_actions, _lib.EXPLORE_GAUSS, float(expl_noise))
+
+    def _explore(self, policy_actions, mode, std):
+        n, amax = self.actions.shape
+        p_in, ld_in = None, 0
+        if policy_actions is not None:
+            t = policy_actions
+            if (t.dtype != torch.float32 or t.device != self.actions.device or t.dim() != 2 or t.shape[0] != n or t.shape[1] < amax
+                    or t.stride(1) != 1):
+                raise _lib.SgrlError("explore_into: policy_actions must be float32 [%d, >= %d] on %s with unit column stride"
+                                     % (n, amax, self.actions.device))
+            p_in, ld_in = ctypes.c_void_p(t.data_ptr()), int(t.stride(0))
+        L = self._explore_lib
+        rc = L.sgrl_explore_actions(p_in, ld_in, ctypes.c_void_p(self.actions.data_ptr()), int(self.actions.stride(0)),
+                                    ctypes.c_void_p(self.act_len.data_ptr()), n, amax, self.env_id_base,
+                                    self.noise_seed & (2 ** 64 - 1), self.noise_step & (2 ** 64 - 1), mode, std, -1.0, 1.0,
+                                    ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        if rc != 0:
+            raise _lib.SgrlError("sgrl_explore_actions failed (%d): %s" % (rc, L.sgrl_explore_last_error().decode()))
+        self.noise_step += 1
+        return self.actions
 
     def step(self, actions):
         return self.env.step_device(actions)

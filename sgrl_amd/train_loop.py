@@ -24,7 +24,7 @@ from .td3 import Agent, default_train_args
 class DeviceTrainer(object):
     def __init__(self, env_names, envs_per_morph, args=None, seed=0, device="cuda:0", max_buffer_size=1000000,
                  batch_size=None, dst=0, graph_updates=False, tune_gemms=False, rollout=None, lag_flag=True, device_sampler=False,
-                 **env_kw):
+                 device_noise=False, **env_kw):
         """graph_updates: replay the TD3 update from hipGraphs (td3.GraphedUpdates); tune_gemms: let PyTorch's TunableOp pick
         the rocBLAS / hipBLASLt algorithm per GEMM shape on first use (the defaults choose 256 x 256 tiles for the 700-row
         weight-gradient GEMMs of a 100-row update: 50 -> 38 ms per update, round 1).  batch_size: rows per TD3 update, default
@@ -34,7 +34,13 @@ class DeviceTrainer(object):
         (replay.DeviceReplayBuffer.sample_into, include/sgrl_replay.h) with seed = `seed` and draw = a counter incremented once per
         update, instead of sample(generator=self.gen) and normal_().  Off by default: it changes which rows a seeded run samples,
         and the learning curves have not been re-run on the new stream.  The draw counter is NOT part of a
-        snapshot: assigning tot_env_steps (how a resumed run restores its count) restarts it at draw = tot_env_steps."""
+        snapshot: assigning tot_env_steps (how a resumed run restores its count) restarts it at draw = tot_env_steps.
+        device_noise (the training rollout only; evaluation never adds noise): the exploration noise and the warm-up actions of
+        collect_step come from ONE library call each (Rollout.explore_into / random_actions, include/sgrl_explore.h) as a function of
+        (`seed`, the rollout's noise_step, global environment number, slot), instead of torch.randn / uniform_ on the rollout's
+        generator.  Off by default for the same reason: it changes what a seeded run explores, and the learning curves have not
+        been re-run on it.  noise_step is NOT part of a snapshot either and follows the same rule as the draw counter: assigning
+        tot_env_steps sets the rollout's noise_step to the restored value."""
         import torch.distributed as dist
         self.dist = dist
         self.rank = dist.get_rank() if dist.is_initialized() else 0
@@ -58,7 +64,9 @@ class DeviceTrainer(object):
             # the actor's parameters change only in update_after_round (updates on the learner, the broadcast on the others): the
             # rollout holds its packed weights across a collection round
             self.ro = Rollout(self.env_names, envs_per_morph, policy=self.agent.actor, seed=seed, device=device, rank=self.rank,
-                              max_episode_steps=self.args.max_episode_steps, hold_weights=True, **env_kw)
+                              max_episode_steps=self.args.max_episode_steps, hold_weights=True, device_noise=device_noise, **env_kw)
+        # an injected driver without explore_into keeps the tensor-op path
+        self.device_noise = bool(device_noise) and hasattr(self.ro, "explore_into")
         env = self.ro.env
         self.device = env.device
         self.graph_dicts = self.ro.graph_dicts
@@ -108,6 +116,8 @@ class DeviceTrainer(object):
             self._tot_base = int(v) - (self.sink.stored + self._updates)
         self._tot_synced = int(v)
         self.draw = int(v)           # the draw counter is not in a snapshot: a resumed run starts at draw = tot_env_steps
+        if hasattr(self.ro, "noise_step"):
+            self.ro.noise_step = int(v)      # ... and neither is the exploration's step number: same rule
 
     def sync_step_count(self):
         """Every rank learns the learner's count (called at the round ends and after the warm-up: rank-local logic that reads the
@@ -131,10 +141,13 @@ class DeviceTrainer(object):
             a = self.ro.random_actions()
         else:                                    # select_action + exploration noise (trainer.py:173-196)
             a = self.ro.policy_forward(self.prev_obs)
-            if self.args.expl_noise != 0:
-                a = self.ro.add_exploration_noise(a, self.args.expl_noise)
-            self.ro.actions.copy_(a)
-            a = self.ro.actions
+            if self.device_noise and self.args.expl_noise != 0:
+                a = self.ro.explore_into(a, self.args.expl_noise)      # one launch, straight into ro.actions
+            else:
+                if self.args.expl_noise != 0:
+                    a = self.ro.add_exploration_noise(a, self.args.expl_noise)
+                self.ro.actions.copy_(a)
+                a = self.ro.actions
         obs, rew, done, _ = self.ro.step(a)
         return self.sink.push(self.prev_obs, a, obs, rew, done)    # the round-finished flag (GPU: read one step late, no stall)
 

@@ -11,10 +11,12 @@
     `sgrl_get_records` every 50 steps of environments whose episode has lasted at least 50 steps.  Writes
     gpurun_out/policy_states.npz (copied to tests/golden/ by hand).
 
-usage: learn_curve.py [train_seconds=480] [envs_per_morph=64] [seed=3] [hopper|walker] [set|swat|smp]
+usage: learn_curve.py [train_seconds=480] [envs_per_morph=64] [seed=3] [hopper|walker] [set|swat|smp] [device_noise]
 The fifth argument picks the actor and critic type (default set).  With swat / smp the collection runs on the batched HIP SWAT /
 SMP forward (sgrl_amd/swat_hip.py, sgrl_amd/smp_hip.py), the updates eagerly through td3.Agent (no graphed updates), and only
 (1) runs.  smp is the published mode (td and bu) with max_children = the largest child count among the chosen morphologies.
+A trailing `device_noise` takes the exploration noise and the warm-up actions from the counter RNG (DeviceTrainer(device_noise=True),
+include/sgrl_explore.h); without it the run explores exactly as before.
 """
 import json
 import os
@@ -38,6 +40,9 @@ per = int(sys.argv[2]) if len(sys.argv) > 2 else 64
 seed = int(sys.argv[3]) if len(sys.argv) > 3 else 3
 family = sys.argv[4] if len(sys.argv) > 4 else "hopper"      # "walker" / "humanoid" / "cheetah" / "cwhh" (config 5): training only
 actor_type = sys.argv[5] if len(sys.argv) > 5 else "set"
+device_noise = len(sys.argv) > 6 and sys.argv[6] == "device_noise"
+if len(sys.argv) > 6 and not device_noise:
+    raise SystemExit("the sixth argument can only be device_noise, not %r" % sys.argv[6])
 if actor_type not in ("set", "swat", "smp"):
     raise SystemExit("actor type must be set, swat or smp, not %r" % actor_type)
 HOPPERS = ["3d_hopper_3_shin", "3d_hopper_4_lower_shin", "3d_hopper_5_full"]
@@ -62,7 +67,7 @@ def train():
         args.td = args.bu = True
         args.max_children = max(list(mjcf.load_asset(n).parents).count(i) for n in names for i in range(mjcf.load_asset(n).num_limbs))
     tr = DeviceTrainer(names, per, args=args, seed=seed, device="cuda:0", max_buffer_size=400000,
-                      graph_updates=actor_type == "set")
+                      graph_updates=actor_type == "set", device_noise=device_noise)
     env = tr.ro.env
     curve = []
     t0 = time.time()
@@ -88,7 +93,7 @@ def train():
         if rnd % 5 == 0:
             print("round %d: return %.2f length %.1f iters %d wall %.0f s" % (rnd, s["performance/train_return"],
                   s["performance/train_length"], s["per_morph_iter"], s["wall_s"]), flush=True)
-    out = {"seed": seed, "actor_type": actor_type, "config": "BASELINE.json config %s (%s) x %d envs" % ({"hopper": "2: 3D_Hopper++", "walker": "3: 3D_Walker++", "humanoid": "4: 3D_Humanoid++", "cwhh": "5: 3D_CWHH++"}.get(family, family), ", ".join(names), per),
+    out = {"seed": seed, "actor_type": actor_type, "device_noise": device_noise, "config": "BASELINE.json config %s (%s) x %d envs" % ({"hopper": "2: 3D_Hopper++", "walker": "3: 3D_Walker++", "humanoid": "4: 3D_Humanoid++", "cwhh": "5: 3D_CWHH++"}.get(family, family), ", ".join(names), per),
            "schedule": "reference trainer.py:143-286 (per_morph_iter updates per morphology per round, batch %d (agent_batch_size, reference configs/default.py:61), lr 1e-4, expl_noise 0.126)" % tr.batch_size,
            "random_policy": {"train_return_mean": float(np.mean(rand_returns)) if rand_returns else None,
                              "train_length_mean": float(np.mean(rand_lengths)) if rand_lengths else None, "rounds": len(rand_returns)},
