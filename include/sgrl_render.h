@@ -14,6 +14,8 @@
 
 #include <stdint.h>
 
+#include "sgrl.h"   /* sgrl_engine */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -27,6 +29,23 @@ extern "C" {
 /* rgb[n_img][height][width][3] (uint8).  geoms[n_img][max_geoms][16], n_geoms[n_img], cams[n_img][13]. */
 int sgrl_render(const float* geoms, const int32_t* n_geoms, int max_geoms, const float* cams, int n_img, int width, int height,
                 uint8_t* rgb, void* stream);
+
+/* ---- scene assembly on the device -------------------------------------------------------------------------------------------
+ * What it replaces: the state hand-over of `SubprocVecEnv.get_images()` (reference src/subproc_vec_env.py:70-73: every worker
+ * renders its own MuJoCo state) and the tracking camera of `viewer_setup` (<env>.py:166-170).  sgrl_scene turns the engine's state
+ * records into the geom / camera records above without leaving the device: forward kinematics of the requested environments from
+ * the qpos in their records and the geoms of their morphology blobs, ONE launch, one 64-thread workgroup per image.  Its definition
+ * is `render.scene_of` (sgrl_amd/render.py): float64 arithmetic, one rounding to float32 at the store.  Geom records g >= ngeom of
+ * an image are written as zeros.  An id outside [0, n_env) gives an empty scene (n_geoms = 0, zero records) and reads nothing: the
+ * ids live on the device, so the caller validates them before the upload. */
+int sgrl_max_geoms(const sgrl_engine* e);     /* largest ngeom over the engine's morphologies */
+int sgrl_scene_launches(void);                /* kernel launches per sgrl_scene call: 1 */
+/* env_ids DEV int32[n_img]; cam_dist HOST double[n_morph]: camera distance per morphology (0.5 * model extent * 2.2, a constant of
+ * the environment object; float64 because the eye is computed in float64 and rounded once); it is uploaded when it differs from
+ * the previous call's, in stream order.  geoms DEV float[n_img][max_geoms][16]; n_geoms DEV int32[n_img]; cams DEV float[n_img][13].
+ * SGRL_ERR_ARG (nothing launched) for a null pointer, n_img <= 0 or max_geoms < sgrl_max_geoms(e). */
+int sgrl_scene(sgrl_engine* e, const int32_t* env_ids, int n_img, const double* cam_dist, int max_geoms, float* geoms,
+               int32_t* n_geoms, float* cams, void* stream);
 
 #ifdef __cplusplus
 }

@@ -31,6 +31,7 @@
 #endif
 #endif
 #include "../../include/sgrl.h"
+#include "engine_view.h"
 #include "step_body.h"
 #include "wave_hip.h"
 #include "wave_half.h"
@@ -40,12 +41,7 @@ namespace sgrl_engine_dev {
 using sgrl::DimsAny;
 using sgrl::DimsFixed;
 
-struct MorphDev {
-  const int32_t* ib;
-  const double* fb;
-  int32_t slot;      // which instance of its family's fixed-dimension kernel serves this morphology (-1: generic kernel only)
-  int32_t pad_;
-};
+// MorphDev: engine_view.h (scene.hip reads the blobs through it too)
 
 struct BatchArgs {
   const MorphDev* morphs;     // [n_morph]

@@ -19,6 +19,11 @@ the bookkeeping above is ONE launch per step (include/sgrl_eval.h sgrl_eval_reco
 group, and the number of open groups is read a step late through pinned memory -- at most `max_trajectory_length` engine steps
 per evaluation instead of up to `num_eval_trajectories` times that, and no host synchronisation in the loop.  `reduce_groups`
 turns the resulting state into the reference's dictionary.
+
+`VideoDemo` is the reference's `save_video_demo` (common/trainer.py:149-258) on the same machinery: one environment per morphology,
+the evaluator's rule with one group, and after every step a frame of every environment rendered on the device
+(BatchedModularVecEnv.get_images_device) into a frame chunk that crosses to the host in one copy.  `write_demo_gifs` writes the
+frames with the reference's four text lines as one GIF per environment (host only, PIL).
 """
 import ctypes
 
@@ -226,3 +231,141 @@ class DeviceEvaluator(object):
         self.last_steps = steps
         stream.synchronize()
         return reduce_groups(self.ep_reward, self.ep_steps, self.group, self.close_step, self.env_morph, self.names)
+
+
+CHUNK_BYTES = 256 * 1000 * 1000      # default ceiling of one device frame chunk
+
+
+class VideoDemo(object):
+    """The rollout of the reference's `save_video_demo` (common/trainer.py:149-258) with every frame rendered on the device (there is
+    no CPU fallback): reset, frame 0, then per step the deterministic policy, the engine step, the bookkeeping of :191-201 -- the
+    evaluator's rule, `DeviceEvaluator.record` with ONE group holding every environment -- and a frame of every environment
+    (finished ones auto-reset and keep being rendered, as in the reference) until every environment has finished its first episode
+    or `max_trajectory_length` steps were taken."""
+
+    def __init__(self, ro, act_fn=None, width=500, height=500, max_trajectory_length=1000, max_episode_steps=1000, chunk_frames=None):
+        """ro: a rollout.Rollout with ONE environment per morphology (the reference's `eval_env`); act_fn(obs) -> actions, default
+        ro.policy_forward.  chunk_frames: frames per device chunk, default as many as stay under CHUNK_BYTES (256 MB) -- 1001
+        frames of 23 environments at 500 x 500 do not fit on the device in one piece."""
+        self.ro = ro
+        self.act_fn = act_fn if act_fn is not None else ro.policy_forward
+        self.width, self.height = int(width), int(height)
+        self.max_trajectory_length = int(max_trajectory_length)
+        self.max_episode_steps = int(max_episode_steps)
+        if self.width < 1 or self.height < 1:
+            raise ValueError("width and height must be at least 1")
+        n = int(ro.env.num_envs)
+        self.ev = DeviceEvaluator(ro, act_fn=self.act_fn, num_eval_trajectories=1, max_trajectory_length=self.max_trajectory_length,
+                                  max_episode_steps=self.max_episode_steps, group=np.zeros(n, dtype=np.int64))
+        self.device, self.n_env = self.ev.device, n
+        frame_bytes = n * self.height * self.width * 3
+        if chunk_frames is None:
+            chunk_frames = max(1, CHUNK_BYTES // frame_bytes)
+        self.chunk_frames = max(1, min(int(chunk_frames), self.max_trajectory_length + 1))
+        self.last_dones = None       # uint8 [T, n]: the environments' own done flags of the kept steps (before the time-limit rule)
+        self.last_steps = 0          # engine steps taken, the lagged extra ones included
+
+    @torch.no_grad()
+    def run(self):
+        """-> (frames uint8 [T + 1, n, H, W, 3] on the host, overlay float64 [T, n, 4] on the host, close_step).  Overlay row t =
+        (dist, reward, episode reward buffer, episode timesteps) of every environment after step t: what the reference draws on frame
+        t + 1.  close_step: the number of steps after which every environment had finished its first episode, 0 when that did not
+        happen within max_trajectory_length; T = close_step, or max_trajectory_length then.  The stop flag is read one step late
+        (DeviceEvaluator), so one or two steps more than T are taken; their frames and rows are dropped.  No host synchronisation per
+        step: a full frame chunk goes to pinned memory in one copy, and the host waits for it while the next chunk renders."""
+        ro, ev, env = self.ro, self.ev, self.ro.env
+        n, H, W, C, max_len = self.n_env, self.height, self.width, self.chunk_frames, self.max_trajectory_length
+        dev, stream = self.device, torch.cuda.current_stream(self.device)
+        chunk = torch.empty((C, n, H, W, 3), dtype=torch.uint8, device=dev)
+        stage = [(torch.empty((C, n, H, W, 3), dtype=torch.uint8).pin_memory(), torch.cuda.Event()) for _ in range(2)]
+        frames = np.empty((max_len + 1, n, H, W, 3), dtype=np.uint8)       # pages are touched only as far as frames arrive
+        overlay = torch.zeros((max_len, n, 4), dtype=torch.float64, device=dev)
+        dones = torch.zeros((max_len, n), dtype=torch.uint8, device=dev)
+        pending = []                 # [(stage slot, first frame, count)] copies in flight, at most two
+
+        def drain(keep=0):
+            while len(pending) > keep:
+                k, first, cnt = pending.pop(0)
+                stage[k][1].synchronize()
+                frames[first:first + cnt] = stage[k][0][:cnt].numpy()
+
+        def flush(first, cnt, k):
+            stage[k][0][:cnt].copy_(chunk[:cnt], non_blocking=True)      # slot k was drained a whole chunk ago
+            stage[k][1].record(stream)
+            pending.append((k, first, cnt))
+            drain(keep=1)            # the chunk before this one: its copy ran while this one rendered
+
+        obs = ro.reset()
+        ev.begin()
+        env.get_images_device(None, W, H, out=chunk[0])
+        n_frames, first, flushed = 1, 0, 0
+        prev, steps = None, 0
+        for step in range(max_len):
+            obs, rew, done, dist = ro.step(self.act_fn(obs))[:4]
+            ev.record(rew, done, step)
+            if n_frames - first == C:
+                flush(first, C, flushed & 1)
+                first, flushed = n_frames, flushed + 1
+            env.get_images_device(None, W, H, out=chunk[n_frames - first])
+            n_frames += 1
+            row = overlay[step]
+            row[:, 0], row[:, 1], row[:, 2], row[:, 3] = dist, rew, ev.acc, ev.ep_steps
+            dones[step] = done.view(torch.uint8) if done.dtype == torch.bool else done
+            steps += 1
+            host, lag = ev._lag_slots[step & 1]
+            host.copy_(ev.open, non_blocking=True)
+            lag.record(stream)
+            if prev is not None:
+                prev[1].synchronize()           # recorded a whole step ago
+                if int(prev[0][0]) == 0:
+                    break
+            prev = (host, lag)
+        if n_frames > first:
+            flush(first, n_frames - first, flushed & 1)
+        drain()
+        stream.synchronize()
+        close_step = int(ev.close_step[0])
+        T = close_step if close_step != 0 else steps
+        self.last_steps = steps
+        self.last_dones = dones[:T].cpu().numpy()
+        return frames[:T + 1], overlay[:T].cpu().numpy(), close_step
+
+
+def _demo_font():
+    from PIL import ImageFont
+    try:
+        return ImageFont.truetype("./misc/sans-serif.ttf", 20)      # the reference's font, where a run directory ships it
+    except OSError:
+        return ImageFont.load_default()
+
+
+def write_demo_gifs(frames, overlay, out_dir, fps=60, text=True):
+    """One `<i>.gif` per environment in `out_dir` from VideoDemo.run()'s (frames [T + 1, n, H, W, 3] uint8, overlay [T, n, 4]); host
+    only.  text: the reference's four yellow lines at (100, 10 / 32 / 54 / 76) on every frame but the first
+    (common/trainer.py:213-232).  The frames are written as they are: the reference's rot90(k=2) undoes the upside-down off-screen
+    buffer of MuJoCo's renderer, and this repository's ray caster renders upright.  Returns the list of written paths."""
+    import os
+    from PIL import Image, ImageDraw
+    frames, overlay = np.asarray(frames), np.asarray(overlay)
+    if frames.ndim != 5 or frames.shape[-1] != 3 or frames.dtype != np.uint8:
+        raise ValueError("frames must be uint8 [T + 1, n, H, W, 3]")
+    if overlay.shape != (frames.shape[0] - 1, frames.shape[1], 4):
+        raise ValueError("overlay must be [T, n, 4] for frames [T + 1, n, H, W, 3], not %s" % (overlay.shape,))
+    os.makedirs(out_dir, exist_ok=True)
+    font = _demo_font() if text else None
+    labels = ("Distance: ", "Instant Reward: ", "Episode Reward: ", "Episode Timesteps: ")
+    paths = []
+    for i in range(frames.shape[1]):
+        imgs = []
+        for t in range(frames.shape[0]):
+            img = Image.fromarray(frames[t, i], "RGB")
+            if text and t > 0:
+                draw = ImageDraw.Draw(img)
+                dist, rew, acc, ts = overlay[t - 1, i]
+                for k, v in enumerate((str(float(dist)), str(float(rew)), str(float(acc)), str(int(ts)))):
+                    draw.text((100, 10 + 22 * k), labels[k] + v, (255, 255, 0), font=font)
+            imgs.append(img)
+        path = os.path.join(out_dir, "%d.gif" % i)
+        imgs[0].save(path, save_all=True, append_images=imgs[1:], duration=max(1, int(round(1000.0 / fps))), loop=0)
+        paths.append(path)
+    return paths

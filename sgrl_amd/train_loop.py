@@ -50,6 +50,7 @@ class DeviceTrainer(object):
         self.env_names = list(env_names)
         self.seed = int(seed)
         self.eval_rollouts = {}      # tuple of names -> (settings, Rollout, DeviceEvaluator) of evaluate()
+        self.demo_rollouts = {}      # tuple of names -> (settings, Rollout, max_episode_steps) of save_video_demo()
         torch.manual_seed(seed)               # same initial weights on every rank
         self.agent = Agent(self.args, device=device)
         if tune_gemms:
@@ -263,6 +264,27 @@ class DeviceTrainer(object):
             entry = self.eval_rollouts[names] = (settings, ro, ev)
         entry[2].max_trajectory_length = int(max_trajectory_length)
         return entry[2].evaluate()
+
+    def save_video_demo(self, out_dir, width=500, height=500, max_trajectory_length=1000, env_names=None, **env_kw):
+        """The reference's `save_video_demo` (common/trainer.py:149-258): roll the deterministic policy out in ONE environment per
+        morphology until every one has finished its first episode (or `max_trajectory_length` steps) and write one `<i>.gif` per
+        environment into `out_dir`, every frame rendered on the device (evaluate.VideoDemo, evaluate.write_demo_gifs).  Built like
+        evaluate(): the environments are a Rollout of this trainer's own, kept per tuple of names, that shares `self.agent.actor` and
+        reads its live weights; the training environments and the round's counters are never touched; env_names: zero-shot demos on
+        held-out morphologies; RANK-LOCAL (no collective).  Returns the list of written paths."""
+        from .evaluate import VideoDemo, write_demo_gifs
+        names = tuple(self.env_names if env_names is None else env_names)
+        settings = repr(sorted(env_kw.items()))
+        entry = self.demo_rollouts.get(names)
+        if entry is None or entry[0] != settings:
+            kw = dict(max_episode_steps=self.args.max_episode_steps)
+            kw.update(env_kw)
+            ro = Rollout(list(names), 1, policy=self.agent.actor, seed=self.seed + 7002, device=self.device, rank=self.rank,
+                         hold_weights=False, **kw)
+            entry = self.demo_rollouts[names] = (settings, ro, kw["max_episode_steps"])
+        demo = VideoDemo(entry[1], width=width, height=height, max_trajectory_length=max_trajectory_length, max_episode_steps=entry[2])
+        frames, overlay, _ = demo.run()
+        return write_demo_gifs(frames, overlay, str(out_dir))
 
     def train_round(self, max_steps=None, max_iters=None):
         """Collect until every environment has finished one episode (or max_steps), update, reset.  Returns a summary."""

@@ -352,6 +352,15 @@ class BatchedModularVecEnv(VecEnv):
             scenes.append(render.scene_of(m, rec[i, :m.nq]))
         return render.render(scenes, width=width, height=height, device=self.device).cpu().numpy()
 
+    def get_images_device(self, env_ids=None, width=256, height=256, out=None):
+        """The frames of `get_images` as a device tensor, uint8 [n, height, width, 3], without the host in between: the scenes come
+        from the state records where they lie (render.device_scenes, ONE launch) and go straight into the ray caster
+        (render.render_device).  No host synchronisation, no `get_records`; `out`: a tensor of that shape to render into (a slot of a
+        frame buffer).  The scenes equal the host-assembled ones to float32 rounding (tests/test_scene_gpu.py)."""
+        from . import render
+        geoms, counts, cams = render.device_scenes(self, env_ids)
+        return render.render_device(geoms, counts, cams, width=width, height=height, out=out)
+
     def close(self):
         if self.closed:
             return
