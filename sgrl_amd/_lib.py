@@ -11,7 +11,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGRL_HIP_LIB", os.path.join(_HERE, "libsgrl_hip.so"))   # override: A/B benchmarking of builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["engine.hip", "set_actor.hip", "train_gemm.hip", "render.hip", "swat_actor.hip", "smp_actor.hip", "replay_sample.hip", "eval_record.hip", "explore_actions.hip", "scene.hip"]
+SOURCES = ["engine.hip", "set_actor.hip", "train_gemm.hip", "render.hip", "swat_actor.hip", "smp_actor.hip", "replay_sample.hip", "eval_record.hip", "explore_actions.hip", "scene.hip", "mlp_actor.hip"]
 
 _lib = None
 
@@ -97,7 +97,7 @@ def build(verbose=False):
         table += "".join("SGRL_MEMBER(%d, %d, %s)\n" % (i, k, ", ".join(str(x) for x in d)) for k, d in enumerate(dims))
     _write_if_changed(os.path.join(CSRC, "spec_table.inc"), table)
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
-    hdrs += [os.path.join(_HERE, "..", "include", f) for f in ("sgrl.h", "sgrl_model.h", "sgrl_set.h", "sgrl_swat.h", "sgrl_smp.h", "sgrl_train.h", "sgrl_render.h", "sgrl_replay.h", "sgrl_eval.h", "sgrl_explore.h")
+    hdrs += [os.path.join(_HERE, "..", "include", f) for f in ("sgrl.h", "sgrl_model.h", "sgrl_set.h", "sgrl_swat.h", "sgrl_smp.h", "sgrl_train.h", "sgrl_render.h", "sgrl_replay.h", "sgrl_eval.h", "sgrl_explore.h", "sgrl_mlp.h")
              if os.path.exists(os.path.join(_HERE, "..", "include", f))]
     newest_hdr = max(os.path.getmtime(d) for d in hdrs)
     objdir = os.path.join(_HERE, "..", "build", "obj")

@@ -1,7 +1,7 @@
 """Batched rollout driver: the build's counterpart of the reference's per-env Python loop
 (`for i in range(num_envs_train): change_morphology; select_action; ...; envs.step`, reference trainer.py:173-236
 and the random-action warm-up loop trainer.py:90-138), with the same per-environment semantics but ONE engine
-launch and ONE batched actor forward (SET, SWAT or SMP) per time step, plus the replay push as a single gather to the learner rank.
+launch and ONE batched actor forward (SET, SWAT, SMP or MLP) per time step, plus the replay push as a single gather to the learner rank.
 """
 import ctypes
 
@@ -11,6 +11,7 @@ import torch
 from . import _lib
 from . import graph as G
 from .replay import DeviceReplayBuffer
+from .mlp_hip import HipMlpActor
 from .set_hip import HipSetActor
 from .smp_hip import HipSmpActor
 from .swat_hip import HipSwatActor
@@ -24,23 +25,39 @@ FUSED_INGEST = True      # False (tests): the learner writes a gathered block mo
 
 def hip_actor_class(policy):
     """The batched HIP forward for `policy`'s type: `SEPolicy` -> `HipSetActor`, `StructurePolicy` (SWAT) -> `HipSwatActor`,
-    `ActorGraphPolicy` (SMP) in its published mode (td and bu) -> `HipSmpActor`."""
+    `ActorGraphPolicy` (SMP) in its published mode (td and bu) -> `HipSmpActor`, `MlpPolicy` -> `HipMlpActor`."""
+    from .mlp_policy import MlpPolicy
     from .set_policy import SEPolicy
     from .smp_policy import ActorGraphPolicy
     from .swat_policy import StructurePolicy
     if isinstance(policy, SEPolicy):
         return HipSetActor
+    if isinstance(policy, MlpPolicy):
+        return HipMlpActor
     if isinstance(policy, StructurePolicy):
         return HipSwatActor
     if isinstance(policy, ActorGraphPolicy) and policy.td and policy.bu:
         return HipSmpActor
-    raise NotImplementedError("the batched rollout has HIP actor forwards for SEPolicy (SET), StructurePolicy (SWAT) and "
+    raise NotImplementedError("the batched rollout has HIP actor forwards for SEPolicy (SET), StructurePolicy (SWAT), MlpPolicy and "
                               "ActorGraphPolicy (SMP, in the td and bu mode only), not for %s%s"
                               % (type(policy).__name__, " with td and not bu" if isinstance(policy, ActorGraphPolicy) else ""))
 
 
+def check_mlp_limbs(policy, env_names, xml_paths=None):
+    """A monolithic `MlpPolicy` reads rows of ONE limb count: ValueError naming the first environment of `env_names` with another
+    (the reference would die on a shape error at its first forward).  Host only; any other policy passes."""
+    L = getattr(policy, "mlp_num_limbs", None)
+    if L is None:
+        return
+    from .vec_env import resolve_models
+    for name, m in zip(env_names, resolve_models(list(env_names), xml_paths)):
+        if m.num_limbs != L:
+            raise ValueError("environment %r has %d limbs, but the MLP policy was built for %d: a monolithic network serves one limb "
+                             "count (args.mlp_num_limbs / the last training morphology)" % (name, m.num_limbs, L))
+
+
 class Rollout(object):
-    """Environments of one rank + the shared actor (SET, SWAT or SMP)."""
+    """Environments of one rank + the shared actor (SET, SWAT, SMP or MLP)."""
 
     def __init__(self, env_names, envs_per_morph, policy=None, seed=0, device="cuda:0", rank=0, hold_weights=False, device_noise=False,
                  **env_kw):
@@ -50,6 +67,7 @@ class Rollout(object):
         one per call.  Off by default: `random_actions` and `add_exploration_noise` then draw from `self.gen` as they always did."""
         counts = [envs_per_morph] * len(env_names) if np.isscalar(envs_per_morph) else list(envs_per_morph)
         n_local = int(sum(counts))
+        check_mlp_limbs(policy, env_names, env_kw.get("xml_paths"))
         self.device_noise = bool(device_noise)
         if self.device_noise and torch.device(device).type != "cuda":
             raise _lib.SgrlError("Rollout(device_noise=True) needs the GPU: sgrl_explore_actions has no CPU fallback")

@@ -279,7 +279,10 @@ def default_train_args(**over):
     a.disable_fold, a.td, a.bu = True, False, False
     a.lr, a.discount, a.policy_noise, a.noise_clip, a.policy_freq = 1e-4, 0.99, 0.2, 0.5, 2
     a.expl_noise, a.grad_clipping_value, a.max_episode_steps = 0.126, 0.1, 1000
-    a.agent = types.SimpleNamespace(target_smoothing_tau=0.005, reward_scale=1.0)
+    # policy_network / q_network (configs/default.py:13-28) and mlp_num_limbs are read by the 'mlp' types only (mlp_policy.py)
+    a.agent = types.SimpleNamespace(target_smoothing_tau=0.005, reward_scale=1.0, policy_network={"hidden_dims": [256, 256]},
+                                    q_network={"hidden_dims": [256, 256]})
+    a.mlp_num_limbs = None
     for k, v in over.items():
         setattr(a, k, v)
     return a
@@ -290,15 +293,24 @@ class Agent(nn.Module):
         super().__init__()
         self.args = args
         atype, ctype = getattr(args, "actor_type", "set"), getattr(args, "critic_type", "set")
-        if atype not in ("set", "swat", "smp") or ctype not in ("set", "swat", "smp"):
-            raise NotImplementedError("actor / critic types 'set', 'swat' and 'smp' are built (the actors with a batched HIP forward for collection, "
-                                      "smp in its td and bu mode; the target chain of a swat or an smp (td and bu) update on HIP, the rest of swat / "
-                                      "smp updates in PyTorch); 'mlp' is not (SURVEY 8 f4)")
+        if atype not in ("set", "swat", "smp", "mlp") or ctype not in ("set", "swat", "smp", "mlp"):
+            raise NotImplementedError("actor / critic types 'set', 'swat', 'smp' and 'mlp' are built (the actors with a batched HIP forward for "
+                                      "collection, smp in its td and bu mode; the target chain of a swat or an smp (td and bu) update on HIP, the "
+                                      "rest of swat / smp updates and all of an mlp update in PyTorch); got actor_type %r, critic_type %r"
+                                      % (atype, ctype))
+        if (atype == "mlp") != (ctype == "mlp"):
+            raise NotImplementedError("an 'mlp' actor goes with an 'mlp' critic only (got actor_type %r, critic_type %r): the monolithic "
+                                      "networks read rows of the last training morphology's own length (reference main.py:118-120), the graph "
+                                      "types rows padded to the widest morphology" % (atype, ctype))
         self.networks = {}
         from .smp_policy import ActorGraphPolicy, CriticGraphPolicy
         from .swat_policy import CriticStructurePolicy, StructurePolicy
+        from .mlp_policy import MlpCritic, MlpPolicy
 
         def actor():
+            if atype == "mlp":
+                return MlpPolicy(args.limb_obs_size, args.limb_action_size, args.msg_dim, args.batch_size, args.max_action,
+                                 args.max_children, args.disable_fold, args.td, args.bu, args, device=device)
             if atype == "swat":
                 return StructurePolicy(args.limb_obs_size, args.limb_action_size, args.msg_dim, args.batch_size, args.max_action,
                                        args.max_children, args.disable_fold, args.td, args.bu, args, device=device)
@@ -309,6 +321,9 @@ class Agent(nn.Module):
                             args.max_children, args.disable_fold, args.td, args.bu, args, device=device, use_hip=use_hip)
 
         def critic():
+            if ctype == "mlp":
+                return MlpCritic(args.limb_obs_size, args.limb_action_size, args.msg_dim, args.batch_size, args.max_children,
+                                 args.disable_fold, args.td, args.bu, args, device=device)
             if ctype == "swat":
                 return CriticStructurePolicy(args.limb_obs_size, args.limb_action_size, args.msg_dim, args.batch_size,
                                              args.max_children, args.disable_fold, args.td, args.bu, args, device=device)
@@ -526,6 +541,8 @@ class GraphedUpdates(object):
 
     def __init__(self, agent, batch_size):
         self.agent, self.B = agent, int(batch_size)
+        if getattr(agent.args, "actor_type", "set") == "mlp":
+            raise NotImplementedError("GraphedUpdates is not built for 'mlp' agents: run their updates eagerly (DeviceTrainer(graph_updates=False))")
         dev = agent.device
         if dev.type != "cuda":
             raise RuntimeError("GraphedUpdates needs the agent on the GPU")

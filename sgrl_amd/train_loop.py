@@ -51,6 +51,14 @@ class DeviceTrainer(object):
         self.seed = int(seed)
         self.eval_rollouts = {}      # tuple of names -> (settings, Rollout, DeviceEvaluator) of evaluate()
         self.demo_rollouts = {}      # tuple of names -> (settings, Rollout, max_episode_steps) of save_video_demo()
+        if getattr(self.args, "actor_type", "set") == "mlp":
+            if graph_updates:
+                raise NotImplementedError("graph_updates is not built for 'mlp' agents: their updates run eagerly")
+            if getattr(self.args, "mlp_num_limbs", None) is None and getattr(self.args, "graphs", None) is None:
+                # the reference sizes the network for the LAST training morphology (MLPActor.py:42)
+                from .vec_env import resolve_models
+                xml = env_kw.get("xml_paths")
+                self.args.mlp_num_limbs = resolve_models(self.env_names[-1:], None if xml is None else xml[-1:])[0].num_limbs
         torch.manual_seed(seed)               # same initial weights on every rank
         self.agent = Agent(self.args, device=device)
         if tune_gemms:

@@ -11,10 +11,11 @@
     `sgrl_get_records` every 50 steps of environments whose episode has lasted at least 50 steps.  Writes
     gpurun_out/policy_states.npz (copied to tests/golden/ by hand).
 
-usage: learn_curve.py [train_seconds=480] [envs_per_morph=64] [seed=3] [hopper|walker] [set|swat|smp] [device_noise]
+usage: learn_curve.py [train_seconds=480] [envs_per_morph=64] [seed=3] [hopper|walker] [set|swat|smp|mlp] [device_noise]
 The fifth argument picks the actor and critic type (default set).  With swat / smp the collection runs on the batched HIP SWAT /
 SMP forward (sgrl_amd/swat_hip.py, sgrl_amd/smp_hip.py), the updates eagerly through td3.Agent (no graphed updates), and only
 (1) runs.  smp is the published mode (td and bu) with max_children = the largest child count among the chosen morphologies.
+mlp is the single-morphology baseline (sgrl_amd/mlp_hip.py): it trains on the LAST morphology of the chosen family alone.
 A trailing `device_noise` takes the exploration noise and the warm-up actions from the counter RNG (DeviceTrainer(device_noise=True),
 include/sgrl_explore.h); without it the run explores exactly as before.
 """
@@ -43,8 +44,8 @@ actor_type = sys.argv[5] if len(sys.argv) > 5 else "set"
 device_noise = len(sys.argv) > 6 and sys.argv[6] == "device_noise"
 if len(sys.argv) > 6 and not device_noise:
     raise SystemExit("the sixth argument can only be device_noise, not %r" % sys.argv[6])
-if actor_type not in ("set", "swat", "smp"):
-    raise SystemExit("actor type must be set, swat or smp, not %r" % actor_type)
+if actor_type not in ("set", "swat", "smp", "mlp"):
+    raise SystemExit("actor type must be set, swat, smp or mlp, not %r" % actor_type)
 HOPPERS = ["3d_hopper_3_shin", "3d_hopper_4_lower_shin", "3d_hopper_5_full"]
 
 
@@ -63,6 +64,8 @@ def train():
         names = sorted(n for n in mjcf.list_assets() if n not in held)
     else:
         names = sorted(n for n in mjcf.list_assets() if family in n)
+    if actor_type == "mlp":         # a monolithic network serves one limb count: the family's last morphology (reference MLPActor.py:42)
+        names = names[-1:]
     if actor_type == "smp":         # the defaults (td = bu = False, max_children 3) are SET's: SMP needs both message passes and a slot per child
         args.td = args.bu = True
         args.max_children = max(list(mjcf.load_asset(n).parents).count(i) for n in names for i in range(mjcf.load_asset(n).num_limbs))
