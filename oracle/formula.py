@@ -63,6 +63,38 @@ def apply_formula_(module, dtype=None):
     return module
 
 
+# ---- full-rank weights, regenerated from (name, seed) ------------------------------------------------------------------------
+# formula_values is a sum of two sinusoids over the flattened index: every matrix has rank <= 4 and nearly repeats every 8 columns,
+# so two exchanged weight columns (a wrong pack permutation, K-slice order or fragment layout) often move no output above the
+# parity tolerance.  These values keep formula_values' scales (1/sqrt(fan_in) x _gain, every branch O(0.1..1)) with independent
+# standard-normal entries.  qk_gain multiplies q_proj / k_proj: at gain 1 the attention is nearly uniform and the two projections
+# are invisible in every output; the effect grows with the square of the gain (tests/test_set_full_rank.py counts it).
+QK_GAIN = 40.0
+
+
+def full_rank_values(name, shape, seed, qk_gain=QK_GAIN):
+    """Deterministic float64 array for parameter `name` of weight set `seed`: N(0,1) entries, formula_values' scales."""
+    rng = np.random.RandomState((zlib.crc32(name.encode("utf-8")) + 7919 * int(seed)) % (2 ** 32))
+    v = rng.standard_normal(size=tuple(shape))
+    if len(shape) == 2:
+        if "embeddings" in name:
+            return 0.3 * v
+        gain = qk_gain if name.endswith(("q_proj.weight", "k_proj.weight")) else _gain(name)
+        return v * (gain / np.sqrt(shape[1]))
+    if "norm" in name and name.endswith("weight"):
+        return 1.0 + 0.1 * v
+    return 0.05 * v
+
+
+def apply_full_rank_(module, seed, qk_gain=QK_GAIN):
+    """Overwrite every parameter of a torch module in place (an SEPolicy / SECritic, any device or dtype) with full_rank_values."""
+    import torch
+    with torch.no_grad():
+        for name, p in module.state_dict().items():
+            p.copy_(torch.from_numpy(full_rank_values(name, tuple(p.shape), seed, qk_gain)).to(p.dtype))
+    return module
+
+
 def synth_obs(num_limbs, batch, seed):
     """Synthetic but plausible per-limb observations (layout of <env>.py:116-140), float64 [B, 41*L]."""
     rng = np.random.RandomState(seed)
