@@ -1,4 +1,5 @@
-/* sgrl_mlp.h -- C ABI of the monolithic MLP actor forward in libsgrl_hip.so.
+/* sgrl_mlp.h -- C ABI of the monolithic MLP agent's no-grad forwards in libsgrl_hip.so: the actor, the twin critic and the TD3
+ * target chain (further down), one launch each.
  *
  * Replaces, for inference under torch.no_grad(), the chain
  *   Agent.select_action                    reference src/agent.py:189-198
@@ -74,6 +75,45 @@ int sgrl_mlp_num_envs(const sgrl_mlp* s);
  * sgrl_mlp_set_params with other widths): a hipGraph holding forwards of this handle must be captured again once it has changed. */
 int64_t sgrl_mlp_generation(const sgrl_mlp* s);
 const char* sgrl_mlp_last_error(void);
+
+/* ---- twin critic and TD3 target chain ----------------------------------------------------------------------------------------
+ * Replaces, under torch.no_grad(), MlpCritic.forward / Q1 (reference src/MLPCritic.py:40-52) and the target half of Agent.update
+ * (reference src/agent.py:126-148).  A critic is two stacks of identical widths dims = [(feature + act_feature) L, hidden ..., 1]
+ * over cat([state, action]).  A handle is an actor or a critic: the last bind decides. */
+
+/* Bind a critic: ptrs is a HOST array of n_ptrs = 4 * (n_dims - 1) DEVICE addresses, critic1's W0, b0, W1, b1, ... then critic2's;
+ * dims[n_dims - 1] must be 1.  Both stacks go into one packed buffer back to back, each in the layout sgrl_mlp_plan describes for
+ * dims (stack 2 at float offset *total); ONE pack launch covers both.  sgrl_mlp_hold_weights and sgrl_mlp_generation as for an
+ * actor.  On a critic handle sgrl_mlp_configure(..., feature, out) checks (feature + out) * morph_L[k] == dims[0]. */
+int sgrl_mlp_set_critic_params(sgrl_mlp* s, const void* const* ptrs, int n_ptrs, const int32_t* dims, int n_dims);
+
+/* q1[e] / q2[e] = critic{1,2}(cat(obs[e, 0 : feature L], act[e, 0 : out L])) for the configured environments; q2 == NULL: Q1 only
+ * (the same bits as the twin call's q1).  obs: DEV float [n_env, obs_ld]; act: DEV float [n_env, act_ld]; q1, q2: DEV float
+ * [n_env].  Columns beyond feature L / out L of a row are never read.  One launch (plus the pack when not holding).  SGRL_ERR_ARG
+ * before any launch for null pointers, narrow rows, a handle not bound as a critic or not configured. */
+int sgrl_mlp_critic_forward(sgrl_mlp* s, const float* obs, int obs_ld, const float* act, int act_ld, float* q1, float* q2, void* stream);
+
+/* The whole target chain in ONE launch (plus the two packs when not holding):
+ *   a           = clamp(max_action * tanh(actor_t(next_obs)) + clamp(noise, +-noise_clip), +-max_action)
+ *   target_q[e] = reward[e] + (1 - done[e]) * discount * min(Q1_t, Q2_t)(next_obs[e], a[e])
+ * next_obs: DEV float [n_env, obs_ld]; noise (the unclipped draw, laid out like an action row): DEV float [n_env, noise_ld];
+ * reward, done, target_q: DEV float [n_env].  action_out may be NULL; otherwise DEV float [n_env, action_ld], it receives a and
+ * exact zeros in columns [out width, action_ld).  With action_out NULL the actions pass through a workspace of the critic handle
+ * (grown on demand, which bumps its generation; a capture cannot grow it: run the batch size eagerly first).  SGRL_ERR_ARG before
+ * any launch for null pointers, narrow rows, handles of the wrong kind, different n_env, a critic whose input is not the actor's
+ * input + output width. */
+int sgrl_mlp_td_target(sgrl_mlp* actor_t, sgrl_mlp* critic_t, const float* next_obs, int obs_ld, const float* noise, int noise_ld,
+                       const float* reward, const float* done, float max_action, float noise_clip, float discount, float* target_q,
+                       float* action_out, int action_ld, void* stream);
+
+/* HOST ONLY.  What the fused chain kernel uses for the pair: info[0] = column chunks (the larger of the two plans), info[1] = panel
+ * depth, info[2] = LDS bytes, info[3] = activation row stride in floats (from the widest padded input of either network).
+ * SGRL_ERR_ARG for what sgrl_mlp_plan refuses, a critic whose last width is not 1 or whose input is not the actor's input + output. */
+int sgrl_mlp_chain_plan(const int32_t* actor_dims, int n_a, const int32_t* critic_dims, int n_c, int32_t* info);
+
+/* Launches of the chain proper (1) and of a critic forward proper (1); each pack adds sgrl_mlp_pack_launches(). */
+int sgrl_mlp_td_target_launches(void);
+int sgrl_mlp_critic_forward_launches(void);
 
 #ifdef __cplusplus
 }

@@ -1,11 +1,16 @@
-"""Batched HIP forward of the monolithic MLP actor (csrc/mlp_actor.hip, C ABI in include/sgrl_mlp.h).
+"""Batched HIP forwards of the monolithic MLP agent (csrc/mlp_actor.hip, C ABI in include/sgrl_mlp.h): the actor, the twin critic
+and the TD3 target chain, one launch each.
 
 `HipMlpActor` binds the `nn.Linear` parameters of an `MlpPolicy` (mlp_policy.py, reference-compatible state_dict) to a handle BY
 ADDRESS.  The library pads the widths in a packed copy of its own (`plan`), built by one pack launch at the top of a forward;
 `hold_weights(True)` is the caller's promise that the parameters stay put until the next `hold_weights` / `weights_changed`, so a
 collection round packs once.  The forward of all environments is ONE launch.  It has the surface `Rollout` uses on the other
 actors (`configure`, `forward_batch`, `hold_weights`, `sync_weights`, `n_env`, `max_limbs`).  No CPU fallback: without the MI355X
-every device entry point raises `_lib.SgrlError`; `plan` alone is host-side."""
+every device entry point raises `_lib.SgrlError`; `plan` and `chain_plan` alone are host-side.
+
+`HipMlpCritic` binds the two Q stacks of an `MlpCritic` the same way (one packed buffer, one pack launch); `HipMlpTargets` runs the
+no-grad half of a TD3 update (target actor -> clipped noise -> clamp -> twin target critics -> min -> Bellman target) as ONE launch
+of the fused chain kernel over the two handles."""
 import ctypes
 
 import numpy as np
@@ -34,7 +39,16 @@ def _bind(L):
     L.sgrl_mlp_configure.restype = ci
     L.sgrl_mlp_forward.argtypes = [vp, vp, ci, vp, ci, ctypes.c_float, vp]
     L.sgrl_mlp_forward.restype = ci
-    for name in ("sgrl_mlp_forward_launches", "sgrl_mlp_pack_launches"):
+    L.sgrl_mlp_set_critic_params.argtypes = [vp, vp, ci, vp, ci]
+    L.sgrl_mlp_set_critic_params.restype = ci
+    L.sgrl_mlp_critic_forward.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp]
+    L.sgrl_mlp_critic_forward.restype = ci
+    cf = ctypes.c_float
+    L.sgrl_mlp_td_target.argtypes = [vp, vp, vp, ci, vp, ci, vp, vp, cf, cf, cf, vp, vp, ci, vp]
+    L.sgrl_mlp_td_target.restype = ci
+    L.sgrl_mlp_chain_plan.argtypes = [vp, ci, vp, ci, vp]
+    L.sgrl_mlp_chain_plan.restype = ci
+    for name in ("sgrl_mlp_forward_launches", "sgrl_mlp_pack_launches", "sgrl_mlp_td_target_launches", "sgrl_mlp_critic_forward_launches"):
         getattr(L, name).argtypes = []
         getattr(L, name).restype = ci
     L.sgrl_mlp_num_envs.argtypes = [vp]
@@ -85,25 +99,34 @@ def plan(dims, n_env=None):
     return out
 
 
-class HipMlpActor(object):
-    """HIP forward of the actor network of an `MlpPolicy` (or, with `net=`, any mlp_policy.MLPNetwork followed by tanh)."""
+def chain_plan(actor_dims, critic_dims):
+    """What the fused target-chain kernel uses for an actor / critic pair (include/sgrl_mlp.h sgrl_mlp_chain_plan; host only): dict
+    of `chunks` (the larger of the two plans), panel depth `bk`, `lds_bytes`, the activation tile's row stride `sx` (from the widest
+    padded input of either network) and `tile_rows`.  Raises for a critic whose last width is not 1 or whose input is not the
+    actor's input + output width."""
+    L = _lib.lib()
+    _bind(L)
+    a, c = np.asarray(actor_dims, dtype=np.int32), np.asarray(critic_dims, dtype=np.int32)
+    info = np.zeros(4, dtype=np.int32)
+    vp = lambda x: ctypes.c_void_p(x.ctypes.data)
+    _check(L, L.sgrl_mlp_chain_plan(vp(a), len(a), vp(c), len(c), vp(info)), "sgrl_mlp_chain_plan")
+    return {"chunks": int(info[0]), "bk": int(info[1]), "lds_bytes": int(info[2]), "sx": int(info[3]), "tile_rows": TILE_ROWS}
 
-    def __init__(self, policy, device=None, net=None):
+
+class _HipMlpHandle(object):
+    """What the actor's and the critic's handles share: the library handle, the parameters bound by address (`nets`: the MLP
+    stacks in the order the bind takes them, all of the widths `dims`), the weight hold and the batch structure.  `per_limb`:
+    the two per-limb sizes sgrl_mlp_configure checks the limb counts with."""
+
+    def __init__(self, module, nets, dims, per_limb, num_limbs, device=None):
         if not torch.cuda.is_available():
             raise _lib.SgrlError("%s needs an MI355X (no CPU fallback)" % type(self).__name__)
         self.L = _lib.lib()
         _bind(self.L)
-        self.policy = policy
-        self.net = net if net is not None else policy.actor
-        self.device = torch.device(device) if device is not None else next(self.net.parameters()).device
+        self.nets, self.dims, self._per_limb, self.num_limbs = list(nets), list(dims), tuple(per_limb), int(num_limbs)
+        self.device = torch.device(device) if device is not None else next(self.nets[0].parameters()).device
         if self.device.type != "cuda":
-            raise _lib.SgrlError("the MlpPolicy must live on the GPU for the HIP path")
-        self.dims = net_dims(self.net)
-        self.feature, self.out_dim = int(policy.state_dim), int(policy.action_dim)
-        self.num_limbs = self.dims[0] // self.feature
-        if self.dims[0] != self.feature * self.num_limbs or self.dims[-1] != self.out_dim * self.num_limbs:
-            raise _lib.SgrlError("the MLP maps %d -> %d values: not %d / %d per limb of one limb count"
-                                 % (self.dims[0], self.dims[-1], self.feature, self.out_dim))
+            raise _lib.SgrlError("the %s must live on the GPU for the HIP path" % type(module).__name__)
         h = ctypes.c_void_p()
         _check(self.L, self.L.sgrl_mlp_create(ctypes.byref(h)), "sgrl_mlp_create")
         self.h = h
@@ -112,6 +135,9 @@ class HipMlpActor(object):
         self._hold = False
         self.n_env = 0
         self.max_limbs = 0
+
+    def _bind_call(self, arr, n, dims):
+        raise NotImplementedError
 
     def __del__(self):
         try:
@@ -123,7 +149,7 @@ class HipMlpActor(object):
 
     # ---- weights ------------------------------------------------------------------------------------
     def _params(self):
-        return [p for l in linears(self.net) for p in (l.weight, l.bias)]
+        return [p for net in self.nets for l in linears(net) for p in (l.weight, l.bias)]
 
     def sync_weights(self, force=False):
         """Bind the handle to the parameters' storage (include/sgrl_mlp.h sgrl_mlp_set_params).  The VALUES are packed at the top
@@ -138,8 +164,7 @@ class HipMlpActor(object):
                                      % (self.device, p.dtype, tuple(p.shape), p.device))
         arr = (ctypes.c_void_p * len(ptrs))(*ptrs)
         dims = np.asarray(self.dims, dtype=np.int32)
-        _check(self.L, self.L.sgrl_mlp_set_params(self.h, ctypes.cast(arr, ctypes.c_void_p), len(ptrs),
-                                                  ctypes.c_void_p(dims.ctypes.data), len(dims)), "sgrl_mlp_set_params")
+        self._bind_call(ctypes.cast(arr, ctypes.c_void_p), len(ptrs), dims)
         self._bound = ptrs
         cfg, self._cfg_key = self._cfg_key, None      # a new binding drops the batch structure: set it again
         if cfg is not None:
@@ -172,14 +197,10 @@ class HipMlpActor(object):
             return
         la, ca = np.asarray(Ls, dtype=np.int32), np.asarray(counts, dtype=np.int32)
         _check(self.L, self.L.sgrl_mlp_configure(self.h, len(la), ctypes.c_void_p(la.ctypes.data), ctypes.c_void_p(ca.ctypes.data),
-                                                 self.feature, self.out_dim), "sgrl_mlp_configure")
+                                                 self._per_limb[0], self._per_limb[1]), "sgrl_mlp_configure")
         self._cfg_key = (Ls, counts)
         self.n_env = int(ca.sum())
         self.max_limbs = int(la.max())
-
-    def launches(self):
-        """Kernel launches of the forward proper (constant: 1; a forward that packs adds `pack_launches()`)."""
-        return int(self.L.sgrl_mlp_forward_launches())
 
     def pack_launches(self):
         return int(self.L.sgrl_mlp_pack_launches())
@@ -193,6 +214,32 @@ class HipMlpActor(object):
     @staticmethod
     def _ld(t):
         return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+
+    def check_rows(self, t, width, what):
+        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == self.n_env, what
+        assert t.shape[1] >= width, "%s rows narrower than the network's %d columns" % (what, width)
+
+
+class HipMlpActor(_HipMlpHandle):
+    """HIP forward of the actor network of an `MlpPolicy` (or, with `net=`, any mlp_policy.MLPNetwork followed by tanh)."""
+
+    def __init__(self, policy, device=None, net=None):
+        self.policy = policy
+        self.net = net if net is not None else policy.actor
+        dims = net_dims(self.net)
+        self.feature, self.out_dim = int(policy.state_dim), int(policy.action_dim)
+        num_limbs = dims[0] // self.feature
+        if dims[0] != self.feature * num_limbs or dims[-1] != self.out_dim * num_limbs:
+            raise _lib.SgrlError("the MLP maps %d -> %d values: not %d / %d per limb of one limb count"
+                                 % (dims[0], dims[-1], self.feature, self.out_dim))
+        super().__init__(policy, [self.net], dims, (self.feature, self.out_dim), num_limbs, device=device)
+
+    def _bind_call(self, arr, n, dims):
+        _check(self.L, self.L.sgrl_mlp_set_params(self.h, arr, n, ctypes.c_void_p(dims.ctypes.data), len(dims)), "sgrl_mlp_set_params")
+
+    def launches(self):
+        """Kernel launches of the forward proper (constant: 1; a forward that packs adds `pack_launches()`)."""
+        return int(self.L.sgrl_mlp_forward_launches())
 
     def forward_batch(self, obs, out=None, act_ld=None):
         """obs: float32 CUDA [n_env, obs_ld] -> actions float32 [n_env, act_ld] (MlpPolicy.forward for every environment; slots
@@ -216,3 +263,112 @@ class HipMlpActor(object):
         """MlpPolicy.forward(state [B, feature * L])."""
         self.configure([graph], [state.shape[0]])
         return self.forward_batch(state.contiguous().float())
+
+
+class HipMlpCritic(_HipMlpHandle):
+    """HIP forward of an `MlpCritic` (inference only: the TD3 target values).  One handle serves both Q stacks: they share one
+    packed buffer and one pack launch, the twin forward is one launch.  Weights, batch structure, `hold_weights`, `generation` and
+    re-binding as on `HipMlpActor`."""
+
+    def __init__(self, module, device=None):
+        self.module = module
+        dims = net_dims(module.critic1)
+        if net_dims(module.critic2) != dims or dims[-1] != 1:
+            raise _lib.SgrlError("an MlpCritic's two stacks must have the same widths and one output (got %s / %s)"
+                                 % (dims, net_dims(module.critic2)))
+        self.feature, self.act_feature = int(module.state_dim), int(module.action_dim)
+        per_limb = self.feature + self.act_feature
+        num_limbs = dims[0] // per_limb
+        if dims[0] != per_limb * num_limbs:
+            raise _lib.SgrlError("the critic reads %d values: not %d + %d per limb of one limb count" % (dims[0], self.feature, self.act_feature))
+        super().__init__(module, [module.critic1, module.critic2], dims, (self.feature, self.act_feature), num_limbs, device=device)
+
+    def _bind_call(self, arr, n, dims):
+        _check(self.L, self.L.sgrl_mlp_set_critic_params(self.h, arr, n, ctypes.c_void_p(dims.ctypes.data), len(dims)),
+               "sgrl_mlp_set_critic_params")
+
+    def launches(self):
+        """Kernel launches of one forward_q, twin or not (constant: 1; a forward that packs adds `pack_launches()`)."""
+        return int(self.L.sgrl_mlp_critic_forward_launches())
+
+    def forward_q(self, obs, action, twin=True):
+        """obs [n_env, >= 41 L], action [n_env, >= 3 L] (float32 CUDA) -> (q1, q2) float32 [n_env, 1] each (MlpCritic.forward for
+        every environment), or q1 alone with twin=False (MlpCritic.Q1; bit-identical to the twin call's q1)."""
+        self.check_rows(obs, self.feature * self.num_limbs, "observation")
+        self.check_rows(action, self.act_feature * self.num_limbs, "action")
+        self.sync_weights()
+        out = torch.empty((2 if twin else 1, self.n_env, 1), dtype=torch.float32, device=self.device)
+        vp = ctypes.c_void_p
+        stream = vp(torch.cuda.current_stream(self.device).cuda_stream)
+        _check(self.L, self.L.sgrl_mlp_critic_forward(self.h, vp(obs.data_ptr()), self._ld(obs), vp(action.data_ptr()), self._ld(action),
+                                                      vp(out[0].data_ptr()), vp(out[1].data_ptr()) if twin else vp(None), stream),
+               "sgrl_mlp_critic_forward")
+        return (out[0], out[1]) if twin else out[0]
+
+    def forward_single(self, state, action, graph, twin=True):
+        """MlpCritic.forward(state [B, 41 L], action [B, 3 L])."""
+        self.configure([graph], [state.shape[0]])
+        return self.forward_q(state.contiguous().float(), action.contiguous().float(), twin=twin)
+
+
+class HipMlpTargets(object):
+    """The no-grad half of a TD3 update of an MLP agent (reference src/agent.py:126-148) on the HIP path: the handles of the target
+    actor (`MlpPolicy`) and the twin target critic (`MlpCritic`), and `target_q` over sgrl_mlp_td_target -- ONE launch (plus one pack
+    per handle: the handles do not hold, so every chain reads the live target parameters)."""
+
+    def __init__(self, actor_target, critic_target):
+        if not torch.cuda.is_available():
+            raise _lib.SgrlError("HipMlpTargets needs an MI355X (no CPU fallback)")
+        self.actor = actor_target.hip_handle()        # cached on the modules (dropped when they are pickled / deep-copied)
+        self.critic = critic_target.hip_handle()
+        self.L, self.device = self.actor.L, self.actor.device
+        a, c = self.actor, self.critic
+        if c.dims[0] != a.dims[0] + a.dims[-1] or c.feature != a.feature or c.act_feature != a.out_dim:
+            raise _lib.SgrlError("the target critic must read the target actor's input + output (%d + %d values), not %d"
+                                 % (a.dims[0], a.dims[-1], c.dims[0]))
+
+    def configure(self, graphs, counts):
+        self.actor.configure(graphs, counts)
+        self.critic.configure(graphs, counts)
+
+    def launches(self):
+        """Kernel launches of the chain proper (constant: 1; each handle that packs adds `pack_launches()`)."""
+        return int(self.L.sgrl_mlp_td_target_launches())
+
+    def plan(self):
+        return chain_plan(self.actor.dims, self.critic.dims)
+
+    def target_q(self, next_obs, noise, reward, done, graph, noise_clip, discount, counts=None, out=None, action_out=None):
+        """reward + (1 - done) * discount * min(Q1_t, Q2_t)(next_obs, clamp(actor_t(next_obs) + clamp(noise, +-noise_clip),
+        +-max_action)) -> float32 [B, 1].  next_obs [B, >= 41 L], noise [B, >= 3 L] (the unclipped draw, laid out like an action
+        row), reward / done [B] or [B, 1].  graph: the morphology's graph dict (a list of them with `counts`; None: the limb count
+        the networks were built for).  action_out: float32 [B, >= 3 L] contiguous, receives the noisy clamped target action (exact
+        zeros beyond 3 L).  Both the tanh head and the final clamp use the target policy's `max_action` (td3.Agent refuses the HIP
+        chain when args.max_action differs from it)."""
+        a, c = self.actor, self.critic
+        if graph is None:
+            graph = {"parents": [0] * a.num_limbs}
+        graphs = graph if isinstance(graph, (list, tuple)) else [graph]
+        self.configure(graphs, counts if counts is not None else [next_obs.shape[0]])
+        c.check_rows(next_obs, a.dims[0], "observation")
+        c.check_rows(noise, a.dims[-1], "noise")
+        reward, done = reward.reshape(-1).contiguous(), done.reshape(-1).contiguous()
+        for t in (reward, done):
+            assert t.is_cuda and t.dtype == torch.float32 and t.shape[0] == a.n_env
+        a.sync_weights()
+        c.sync_weights()
+        if out is None:
+            out = torch.empty((a.n_env, 1), dtype=torch.float32, device=self.device)
+        assert out.is_contiguous() and out.shape == (a.n_env, 1) and out.dtype == torch.float32
+        vp, cf = ctypes.c_void_p, ctypes.c_float
+        act_ptr, act_ld = vp(None), 0
+        if action_out is not None:
+            assert action_out.is_cuda and action_out.dtype == torch.float32 and action_out.is_contiguous() and action_out.dim() == 2
+            assert action_out.shape[0] == a.n_env and action_out.shape[1] >= a.dims[-1], "action_out rows narrower than the actor's output"
+            act_ptr, act_ld = vp(action_out.data_ptr()), int(action_out.shape[1])
+        stream = vp(torch.cuda.current_stream(self.device).cuda_stream)
+        _check(self.L, self.L.sgrl_mlp_td_target(a.h, c.h, vp(next_obs.data_ptr()), a._ld(next_obs), vp(noise.data_ptr()), a._ld(noise),
+                                                 vp(reward.data_ptr()), vp(done.data_ptr()), cf(float(a.policy.max_action)),
+                                                 cf(float(noise_clip)), cf(float(discount)), vp(out.data_ptr()), act_ptr, act_ld, stream),
+               "sgrl_mlp_td_target")
+        return out

@@ -10,7 +10,8 @@ L comes from `args.mlp_num_limbs` when set, otherwise from `args.graphs[args.env
 MLPActor.py:42); the hidden widths from `args.agent['policy_network']['hidden_dims']` / `args.agent['q_network']['hidden_dims']`
 when present, otherwise the reference's [256, 256] (configs/default.py:13-28).  Pinned to fixtures produced by executing the
 reference's own modules (tests/golden/mlp_forward.npz, tools/capture_golden_mlp.py).  The batched rollout runs the actor's
-no-grad forward as one HIP launch (mlp_hip.HipMlpActor, csrc/mlp_actor.hip); `forward` itself stays plain PyTorch for autograd."""
+no-grad forward as one HIP launch (mlp_hip.HipMlpActor, csrc/mlp_actor.hip), a TD3 update its no-grad target chain as one launch over
+the target modules' handles (mlp_hip.HipMlpTargets); `forward` itself stays plain PyTorch for autograd."""
 import torch
 import torch.nn as nn
 
@@ -156,6 +157,19 @@ class MlpCritic(nn.Module):
             self.to(device)
         self.graph = None
         self.num_limbs = self.mlp_num_limbs
+        self._mlp_hip = None
+
+    def __getstate__(self):
+        d = self.__dict__.copy()
+        d["_mlp_hip"] = None      # per-process device handle: never pickled / deep-copied with the module
+        return d
+
+    def hip_handle(self):
+        """The module's mlp_hip.HipMlpCritic, created on first use (raises _lib.SgrlError without an MI355X: no fallback)."""
+        if getattr(self, "_mlp_hip", None) is None:
+            from .mlp_hip import HipMlpCritic
+            self._mlp_hip = HipMlpCritic(self)
+        return self._mlp_hip
 
     def forward(self, state, action):
         inpt = torch.cat([state, action], dim=-1)

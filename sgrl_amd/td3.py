@@ -295,8 +295,8 @@ class Agent(nn.Module):
         atype, ctype = getattr(args, "actor_type", "set"), getattr(args, "critic_type", "set")
         if atype not in ("set", "swat", "smp", "mlp") or ctype not in ("set", "swat", "smp", "mlp"):
             raise NotImplementedError("actor / critic types 'set', 'swat', 'smp' and 'mlp' are built (the actors with a batched HIP forward for "
-                                      "collection, smp in its td and bu mode; the target chain of a swat or an smp (td and bu) update on HIP, the "
-                                      "rest of swat / smp updates and all of an mlp update in PyTorch); got actor_type %r, critic_type %r"
+                                      "collection, smp in its td and bu mode; the target chain of a swat, an smp (td and bu) or an mlp update on HIP, the "
+                                      "rest of those updates in PyTorch); got actor_type %r, critic_type %r"
                                       % (atype, ctype))
         if (atype == "mlp") != (ctype == "mlp"):
             raise NotImplementedError("an 'mlp' actor goes with an 'mlp' critic only (got actor_type %r, critic_type %r): the monolithic "
@@ -349,16 +349,22 @@ class Agent(nn.Module):
         # the same for SMP actor AND critic in the published mode (td and bu; smp_hip.HipSmpTargets); the td-only mode stays PyTorch
         self.use_smp_hip = bool(use_hip) and atype == "smp" and ctype == "smp" and bool(args.td) and bool(args.bu)
         self._smp_targets = None
+        # and for the monolithic MLP pair: the whole chain is ONE launch (mlp_hip.HipMlpTargets).  The handles do not hold: every
+        # chain packs from the live target parameters, so soft updates and load_state_dict need no notification
+        self.use_mlp_hip = bool(use_hip) and atype == "mlp" and ctype == "mlp"
+        self._mlp_targets = None
 
     def __getstate__(self):
         d = self.__dict__.copy()
         d["_swat_targets"] = None     # per-process device handles: never pickled / deep-copied with the agent
         d["_smp_targets"] = None
+        d["_mlp_targets"] = None
         return d
 
     def _hip_targets(self, next_obs):
-        """swat_hip.HipSwatTargets / smp_hip.HipSmpTargets when this update's target chain runs on HIP, else None."""
-        if not ((self.use_swat_hip or self.use_smp_hip) and next_obs.is_cuda and next_obs.dtype == torch.float32 and
+        """swat_hip.HipSwatTargets / smp_hip.HipSmpTargets / mlp_hip.HipMlpTargets when this update's target chain runs on HIP, else
+        None."""
+        if not ((self.use_swat_hip or self.use_smp_hip or self.use_mlp_hip) and next_obs.is_cuda and next_obs.dtype == torch.float32 and
                 self.device.type == "cuda"):
             return None
         if self.use_smp_hip:
@@ -366,6 +372,15 @@ class Agent(nn.Module):
             if t is None or t.actor.policy is not self.actor_target or t.critic.module is not self.critic_target:
                 from .smp_hip import HipSmpTargets      # raises SgrlError when the extension is missing (no fallback)
                 t = self._smp_targets = HipSmpTargets(self.actor_target, self.critic_target)
+            return t
+        if self.use_mlp_hip:
+            if float(self.actor_target.max_action) != float(self.args.max_action):
+                raise ValueError("the HIP target chain of an mlp agent scales and clamps with one max_action: the target policy's (%r) differs "
+                                 "from args.max_action (%r); build the agent with use_hip=False" % (self.actor_target.max_action, self.args.max_action))
+            t = self._mlp_targets
+            if t is None or t.actor.policy is not self.actor_target or t.critic.module is not self.critic_target:
+                from .mlp_hip import HipMlpTargets      # raises SgrlError when the extension is missing (no fallback)
+                t = self._mlp_targets = HipMlpTargets(self.actor_target, self.critic_target)
             return t
         t = self._swat_targets
         if t is None or t.actor.policy is not self.actor_target or t.critic.module is not self.critic_target:
