@@ -103,8 +103,26 @@ typedef struct sgrl_pack_seg {
 /* ... followed by SGRL_SET_NEXTRA more offsets: the actor head with decoder_g FOLDED through linear2_m (exact algebra, reference
  * SEActor.py:272-279: decoder_g(z . mat) = z . (mat . w_dec), so only the 32 numbers m2[q] = sum_c mat[q][c] w_dec[c] per node are
  * needed):  [32, 256] rows q = sum_c w_dec[c] * linear2_m.weight[q * 32 + c]  and  [32] = sum_c w_dec[c] * linear2_m.bias[q * 32 + c]
- * (MATMUL segments over the live parameters).  A critic network binds 64-float fillers there. */
-#define SGRL_SET_NEXTRA 2
+ * (MATMUL segments over the live parameters).  A critic network binds 64-float fillers there.
+ * The third extra offset is the LAYER-0 FOLD block, 256 * 48 + 8 * 32 + 8 * 8 + 128 * 2 * 8 floats that the plan reserves (zero COPY)
+ * and the library fills behind the pack of a forward that takes the fold, from the slots packed above (k_fold_l0, float64 accumulation).  Exact algebra again: the
+ * embedding of the vector stream is linear and has no bias, g0[n][s][:] = sqrt(128) Wge v_s with v_s the node's eight input
+ * three-vectors V [3, 8] (reference SEActor.py:243-247), so at layer 0 every consumer that is linear in g0 is a rank-8 problem:
+ *   M~  [8][32]      Z0 = V M~:  columns 0..29 = sqrt(128) (Wp Wge)' with Wp = layer 0's A_GPROJ, columns 30 / 31 = e1 / e2 (the
+ *                    gravity / direction vectors v_1, v_2 themselves); k_embed writes Z0 and V (zero-padded to 32 columns)
+ *   W1' [256][48]    A_LG1_W of layer 0 taken through M~ (x) M~: Z0'Z0 = M~' C M~ with C = V'V (8 x 8), so linear_g1 acts on the three
+ *                    4x4 blocks (0,0), (1,0), (1,1) of C -- the first three k-tiles of the blocked order above, K = 48 instead of 576.
+ *                    The generator produces whole blocks: inside a diagonal block both positions (a, b), (b, a) of a symmetric pair
+ *                    carry half the pair's weight each, the off-diagonal block carries (a, b) + (b, a) per entry.  The site runs
+ *                    without its projection prologue (k_chain<1, 256, 0, 0> on V)
+ *   Q   [8][8]       M~ M~': the row divisor fn = ||Z0'Z0||_F + 1 = ||V Q V'||_F + 1 (k_embed)
+ *   Wu~ [2][8][128]  Wu~[h][p][c] = (sqrt(128) VG_W_h Wge)[c][p] with A_GD added at p = 1, 2: attention-0's vector output is
+ *                    g1[i][s][c] = sum_h sum_p Wu~[h][p][c] (sum_j w_h[i,j] V[j][s][p]) -- k_attention mixes 8 values per key limb
+ *                    instead of 256; the U product of layer 0 is not launched and its buffer not touched
+ * Like the other folds it is part of the packed state (weight hold, pack form).  It serves the fused tile path (>= 2048 nodes, default
+ * product form) of bound handles; static weights (sgrl_set_weights), the other product forms and the small-batch path keep the
+ * unfolded layer 0.  A plan that binds a 64-float filler there has no fold.  sgrl_set_debug_l0fold switches it per handle. */
+#define SGRL_SET_NEXTRA 3
 int sgrl_set_bind_params(sgrl_set* s, const sgrl_pack_seg* segs, int n_segs, const int64_t* offsets, int n_offsets,
                          int64_t total_floats);
 
@@ -114,7 +132,9 @@ int sgrl_set_bind_params(sgrl_set* s, const sgrl_pack_seg* segs, int n_segs, con
  * that the parameters stay as they are until the next call of this function: the first forward after it packs, the following ones
  * reuse that buffer.  Every call (hold = 1 again, or 0 = back to packing on every forward) also means "the parameters may just have
  * changed".  Forwards recorded into a hipGraph always pack.  `DeviceTrainer` holds across a collection round and calls again after
- * every round's updates / actor broadcast; bench.py's rollout (constant random-init weights) holds throughout. */
+ * every round's updates / actor broadcast; bench.py's rollout (constant random-init weights) holds throughout.  The relation bias
+ * table of a batch structure (rel_encoder over its relation tensors: weights and structure only) is held with the pack: computed once
+ * per hold and structure, not at the top of every forward. */
 int sgrl_set_hold_weights(sgrl_set* s, int hold);
 
 /* Batch structure (SEPolicy.change_morphology for every morphology at once, reference SEActor.py:349-355):
@@ -181,6 +201,9 @@ int sgrl_set_debug_small_nodes(sgrl_set* s, int nodes);
  *   SGRL_SET_SPLIT=3  as 2, and the second half starts only once the first half's first site kernel is done (slower as well).
  * sgrl_set_last_split: nodes in the first half of the handle's last forward; 0 = it ran as a single pass. */
 int sgrl_set_last_split(const sgrl_set* s);
+/* The layer-0 fold (above, at SGRL_SET_NEXTRA): on = 0 makes the following forwards of this handle run layer 0 unfolded, as the other
+ * layers (A/B comparisons, tests); 1 restores the default.  Results agree to float32 rounding, not bit for bit: the summation order differs. */
+int sgrl_set_debug_l0fold(sgrl_set* s, int on);
 /* Form of the 128 x 128 tile products (reference: plain f32 `F.linear`, subequivariant_attentions.py:90-151 / SEActor.py:82-125).
  * Both forms carry the f32 product on the 16-bit matrix cores and measure the same error against float64 as an f32 FMA chain
  * (tests/test_split_products_gpu.py):

@@ -74,13 +74,17 @@ struct NodeTab {
   int TM;
 };
 constexpr int kEmbedNodes = 8;
+// The layer-0 fold block of the flat weight buffer (include/sgrl_set.h, k_fold_l0): W1' [256][48] | M~ [8][32] | Q [8][8] | Wu~ [2][8][128]
+constexpr int kL0fW1 = 0, kL0fMt = 256 * 48, kL0fQ = kL0fMt + 8 * ZD, kL0fWu = kL0fQ + 64, kL0fFloats = kL0fWu + 128 * 2 * 8;
 __global__ __launch_bounds__(128) void k_embed(const float* __restrict__ obs, int obs_ld, const float* __restrict__ action,
                                                int act_ld, int ngf, NodeTab nt, const float* Wge, const float* We,
                                                const float* be, const float* e0, const float* e1, const float* e2, float* g,
-                                               float* cat, float* outg, float* outng, float* gdir, float* zc, float* z2, int N) {
+                                               float* cat, float* outg, float* outng, float* gdir, float* zc, float* z2, int N,
+                                               const float* __restrict__ l0f, float* vpad, float* fn) {
   // per-limb input row: 24 geometric values (8 three-vectors) | ngf non-geometric ones -- 17 from the observation and,
   // for the critic (ngf = 20), the limb's 3 action slots appended (reference SECritic.py:80-83)
   __shared__ float os[kEmbedNodes][44];
+  __shared__ float sq[kEmbedNodes * 9];
   const int n0 = blockIdx.x * kEmbedNodes, c = threadIdx.x;
   for (int idx = c; idx < kEmbedNodes * 44; idx += 128) {
     const int q = idx / 44, k = idx % 44, n = n0 + q;
@@ -98,6 +102,10 @@ __global__ __launch_bounds__(128) void k_embed(const float* __restrict__ obs, in
 #pragma unroll
   for (int j = 0; j < 20; j++) we[j] = j < ngf ? We[c * ngf + j] : 0.f;
   const float bias = be[c];
+  // layer-0 fold (include/sgrl_set.h): column c < 30 of M~ = sqrt(128) (Wp Wge)^T, so that Z0 = V . M~ comes from the eight
+  // input vectors directly
+  __shared__ float mq[8 * ZD + 64];             // M~ | Q
+  if (l0f) for (int k = c; k < 8 * ZD + 64; k += 128) mq[k] = l0f[kL0fMt + k];
   __syncthreads();
   const float sc = sqrtf(128.f);
   for (int q = 0; q < kEmbedNodes; q++) {
@@ -130,6 +138,44 @@ __global__ __launch_bounds__(128) void k_embed(const float* __restrict__ obs, in
       gdir[((size_t)n * 3 + s) * 2 + e] = gv;
       zc[((size_t)n * 3 + s) * ZD + 30 + e] = gv;
       z2[((size_t)n * 3 + s) * ZD + 30 + e] = gv;
+    }
+  }
+  if (l0f) {
+    // V [3, 32] (columns 8..31 zero): the operand the layer-0 site generates C = V'V from and the value rows of attention-0; Z0 = V M~.
+    // The block's 8 x 96 entries of each are contiguous: one pass over them with all threads
+    const int live = min(kEmbedNodes, N - n0) * 96;
+#pragma unroll 1
+    for (int idx = c; idx < live; idx += 128) {
+      const int q = idx / 96, s = (idx >> 5) % 3, col = idx & 31;
+      const float* o = os[q];
+      vpad[(size_t)n0 * 96 + idx] = col < 8 ? o[3 * col + s] : 0.f;
+      if (col < 30) {
+        float z = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; j++) z += o[3 * j + s] * mq[j * ZD + col];
+        zc[(size_t)n0 * 96 + idx] = z;
+      }
+    }
+    // fn = ||V Q V'||_F + 1 with Q = M~ M~' (= ||Z0'Z0||_F + 1): thread = one entry (s, s2) of a node's 3 x 3 matrix
+    const float* Q = mq + 8 * ZD;
+    if (c < kEmbedNodes * 9) {
+      const float* o = os[c / 9];
+      const int s = (c % 9) / 3, s2 = c % 3;
+      float v = 0.f;
+#pragma unroll 1
+      for (int a = 0; a < 8; a++) {
+        float qa = 0.f;
+#pragma unroll
+        for (int b = 0; b < 8; b++) qa += Q[a * 8 + b] * o[3 * b + s2];
+        v += o[3 * a + s] * qa;
+      }
+      sq[c] = v * v;
+    }
+    __syncthreads();
+    if (c < kEmbedNodes && n0 + c < N) {
+      float ss = 0.f;
+      for (int k = 0; k < 9; k++) ss += sq[c * 9 + k];
+      fn[n0 + c] = sqrtf(ss) + 1.f;
     }
   }
 }
@@ -222,6 +268,81 @@ __global__ __launch_bounds__(256) void k_pack(const sgrl_pack_seg* __restrict__ 
   }
 }
 
+// The layer-0 fold (include/sgrl_set.h): at layer 0 the vector stream is g0[n][s][:] = sqrt(128) Wge v_s, rank 8, so every layer-0
+// consumer that is linear in it is folded onto the eight input vectors V [3, 8] of a node.  Runs behind k_pack on the packed buffer
+// (its sources are folds themselves), in float64, once per pack.  With M~ [8][32] = [sqrt(128) (Wp Wge)' | e1 e2] (Z0 = V M~):
+//   W1' [256][48]   linear_g1 on the three 4x4 blocks (0,0), (1,0), (1,1) of C = V'V, in the generator's blocked order: with
+//                   T[a][b] = sum_k W1[k] M~[a][x_k] M~[b][y_k] over the 576 folded columns k <-> (x_k, y_k), an entry (a, b) of a
+//                   diagonal block carries (T[a][b] + T[b][a]) / 2 (both positions of a symmetric pair are generated), an entry of
+//                   the off-diagonal block T[a][b] + T[b][a], a diagonal entry T[a][a]
+//   Q [8][8]        M~ M~' (the row divisor: ||Z0'Z0||_F = ||V Q V'||_F)
+//   Wu~ [2][8][128] Wu~[h][p][c] = (sqrt(128) (Wgo_h Wvg_h) Wge)[c][p] per head h, the gravity / direction columns A_GD added at p = 1, 2
+// blocks 0..255: one row of W1' each; block 256: M~ and Q; blocks 257..264: 256 entries of Wu~ each
+constexpr int kFoldL0Blocks = 256 + 1 + 8;
+__global__ __launch_bounds__(256) void k_fold_l0(const float* __restrict__ Wp, const float* __restrict__ Wge, const float* __restrict__ W1,
+                                                 const float* __restrict__ Wu, const float* __restrict__ GD,
+                                                 const unsigned short* __restrict__ tri, float* out) {
+  __shared__ double mt[8][ZD];
+  __shared__ double tp[4][64];
+  const int t = threadIdx.x, blk = blockIdx.x;
+  const double sc = sqrt(128.0);
+  if (blk <= 256) {
+    const int a = t >> 5, x = t & 31;
+    double v = 0.0;
+    if (x < 30) {
+      double v4[4] = {0.0, 0.0, 0.0, 0.0};        // four independent chains: the loads of one round are in flight together
+      for (int k = 0; k < D; k += 4)
+#pragma unroll
+        for (int u = 0; u < 4; u++) v4[u] += (double)Wp[x * D + k + u] * (double)Wge[(k + u) * 8 + a];
+      v = ((v4[0] + v4[1]) + (v4[2] + v4[3])) * sc;
+    } else {
+      v = (a == x - 29) ? 1.0 : 0.0;            // columns 30 / 31: v_1, v_2 themselves (gravity / direction)
+    }
+    mt[a][x] = v;
+    __syncthreads();
+  }
+  if (blk < 256) {
+    const int ab = t & 63, a = ab >> 3, b = ab & 7, part = t >> 6;
+    const float* row = W1 + (size_t)blk * GK;
+    double a4[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int k = part * (GK / 4); k < (part + 1) * (GK / 4); k += 4)
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const unsigned tt = tri[k + u];
+        if (tt != 0xFFFFu) a4[u] += (double)row[k + u] * mt[a][tt >> 8] * mt[b][tt & 255];
+      }
+    tp[part][ab] = (a4[0] + a4[1]) + (a4[2] + a4[3]);
+    __syncthreads();
+    if (t < 48) {
+      const int kb = t >> 4, i = (t >> 2) & 3, j = t & 3;        // block 0: (0,0), 1: (1,0), 2: (1,1)
+      const int ca = 4 * (kb > 0) + i, cb = 4 * (kb > 1) + j;
+      auto T = [&](int p, int q) { return (tp[0][p * 8 + q] + tp[1][p * 8 + q]) + (tp[2][p * 8 + q] + tp[3][p * 8 + q]); };
+      double v;
+      if (ca == cb) v = T(ca, ca);
+      else if (kb == 1) v = T(ca, cb) + T(cb, ca);
+      else v = 0.5 * (T(ca, cb) + T(cb, ca));
+      out[kL0fW1 + blk * 48 + t] = (float)v;
+    }
+  } else if (blk == 256) {
+    out[kL0fMt + t] = (float)mt[t >> 5][t & 31];
+    if (t < 64) {
+      double q = 0.0;
+      for (int x = 0; x < ZD; x++) q += mt[t >> 3][x] * mt[t & 7][x];
+      out[kL0fQ + t] = (float)q;
+    }
+  } else {
+    const int idx = (blk - 257) * 256 + t, c = idx & 127, p = (idx >> 7) & 7, h = idx >> 10;      // stored [h][p][c]
+    const float* row = Wu + (size_t)(128 * h + c) * D;
+    double v4[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < D; k += 4)
+#pragma unroll
+      for (int u = 0; u < 4; u++) v4[u] += (double)row[k + u] * (double)Wge[(k + u) * 8 + p];
+    double v = ((v4[0] + v4[1]) + (v4[2] + v4[3])) * sc;
+    if (p == 1 || p == 2) v += (double)GD[(h * 128 + c) * 2 + (p - 1)];
+    out[kL0fWu + idx] = (float)v;
+  }
+}
+
 // relation bias per morphology: relb[off + (h*L + i)*L + j] = rel_encoder(relation[i,j])[h]
 __global__ void k_relbias(const float* rel, const float* Wr, const float* br, float* relb, const int32_t* m_off,
                           const int32_t* m_L, int n_morph) {
@@ -247,6 +368,10 @@ struct EnvTab {
   const int32_t* env_L;     // [n_env]
   const int32_t* env_relb;  // [n_env] offset into relb
 };
+// L0 (the layer-0 fold, include/sgrl_set.h): the vector values are the nodes' eight input vectors themselves -- U = V [N, 3, 32]
+// (columns 0..7) and GD = Wu~ [2][8][128]: the kernel mixes 8 values per key limb instead of 256 and applies Wu~ for its four output
+// columns, g1[i][s][c] = sum_h sum_p Wu~[h][p][c] (sum_j w_h[i,j] V[j][s][p]); the gravity / direction term is inside Wu~ (p = 1, 2)
+template <bool L0>
 __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv, const float* __restrict__ U,
                                                    const float* __restrict__ gdir, const float* relb, EnvTab et,
                                                    int use_bias, const float* __restrict__ b_ng, const float* __restrict__ GD,
@@ -254,7 +379,7 @@ __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv
                                                    const float* __restrict__ ln_w, const float* __restrict__ ln_b) {
   constexpr int LMAX = 14;
   __shared__ float sc[2 * LMAX * LMAX];
-  __shared__ float gd[2 * LMAX * 3 * 2];        // [h][i][s][e] = sum_j w_h[i,j] gdir[j][s][e]
+  __shared__ float gd[2 * LMAX * 3 * (L0 ? 8 : 2)];   // [h][i][s][e] = sum_j w_h[i,j] gdir[j][s][e]   (L0: [h][i][s][p], V in gdir's place)
   __shared__ float dl[LMAX][128];               // delta rows, handed from the column threads to the LayerNorm waves
   const int e = blockIdx.x, t = threadIdx.x;
   const int n0 = et.env_off[e], L = et.env_L[e];
@@ -287,12 +412,23 @@ __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv
   }
   __syncthreads();
   // attention-weighted gravity / direction columns: 2 heads x L x 3 x 2 <= 168 values
-  for (int idx = t; idx < 2 * L * 6; idx += 256) {
-    const int h = idx / (L * 6), i = (idx / 6) % L, se = idx % 6;
-    const float* w = sc + (h * L + i) * L;
-    float s = 0.f;
-    for (int j = 0; j < L; j++) s += w[j] * gdir[(size_t)(n0 + j) * 6 + se];
-    gd[idx] = s;
+  if (L0) {
+    for (int idx = t; idx < 2 * L * 24; idx += 256) {
+      const int h = idx / (L * 24), i = (idx / 24) % L, sp = idx % 24;
+      const float* w = sc + (h * L + i) * L;
+      const float* vr = U + (size_t)n0 * 96 + (sp >> 3) * ZD + (sp & 7);
+      float s = 0.f;
+      for (int j = 0; j < L; j++) s += w[j] * vr[(size_t)j * 96];
+      gd[idx] = s;
+    }
+  } else {
+    for (int idx = t; idx < 2 * L * 6; idx += 256) {
+      const int h = idx / (L * 6), i = (idx / 6) % L, se = idx % 6;
+      const float* w = sc + (h * L + i) * L;
+      float s = 0.f;
+      for (int j = 0; j < L; j++) s += w[j] * gdir[(size_t)(n0 + j) * 6 + se];
+      gd[idx] = s;
+    }
   }
   __syncthreads();                               // gd[] complete
   // wave = output quantity (0: scalar stream, 1..3: spatial row quantity - 1), half-wave = head, lane = FOUR output columns:
@@ -301,15 +437,30 @@ __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv
   // count is a compile-time bound per instance (4 or 8 rows at a time) so that the register arrays stay small.
   {
     const int quantity = t >> 6, ln = t & 63, h = ln >> 5, c4 = (ln & 31) * 4;
-    const float* vbase = quantity == 0 ? qkv + (size_t)n0 * 768 + 512 + h * 128 + c4
-                                       : U + ((size_t)n0 * 3 + (quantity - 1)) * 256 + h * 128 + c4;     // 768 floats per node either way
+    const float* vbase = (quantity == 0 || L0) ? qkv + (size_t)n0 * 768 + 512 + h * 128 + c4
+                                               : U + ((size_t)n0 * 3 + (quantity - 1)) * 256 + h * 128 + c4;     // 768 floats per node either way
     auto body = [&](auto ltc, const int i0) __attribute__((always_inline)) {      // output rows i0 .. i0 + LT - 1
       constexpr int LT = decltype(ltc)::value;
       float4 out[LT];
 #pragma unroll
       for (int i = 0; i < LT; i++) out[i] = make_float4(0.f, 0.f, 0.f, 0.f);
       const float* wh = sc + h * L * L;
-      if (L <= 8) {          // value rows four at a time (one 16-byte load per key limb in flight, then the products)
+      if (L0 && quantity != 0) {       // the mixed input vectors of the rows (eight per head, in LDS) through Wu~ (16-byte loads, cached)
+#pragma unroll 1
+        for (int pb = 0; pb < 8; pb += 2) {       // two rows of Wu~ in flight at a time (registers: eight waves per SIMD, as the other form)
+          float4 wu[2];
+#pragma unroll
+          for (int k = 0; k < 2; k++) wu[k] = *reinterpret_cast<const float4*>(GD + (h * 8 + pb + k) * 128 + c4);
+#pragma unroll
+          for (int k = 0; k < 2; k++)
+#pragma unroll
+            for (int i = 0; i < LT; i++)
+              if (i0 + i < L) {
+                const float mv = gd[((h * L + i0 + i) * 3 + (quantity - 1)) * 8 + pb + k];
+                out[i].x += wu[k].x * mv; out[i].y += wu[k].y * mv; out[i].z += wu[k].z * mv; out[i].w += wu[k].w * mv;
+              }
+        }
+      } else if (L <= 8) {          // value rows four at a time (one 16-byte load per key limb in flight, then the products)
 #pragma unroll
         for (int jb = 0; jb < 8; jb += 4) {
           if (jb >= L) break;
@@ -341,7 +492,7 @@ __global__ __launch_bounds__(256) void k_attention(const float* __restrict__ qkv
           v = vn;
         }
       }
-      if (quantity != 0) {
+      if (quantity != 0 && !L0) {
         const float4 ga = *reinterpret_cast<const float4*>(GD + (h * 128 + c4) * 2);        // (gd0, gd1) of columns c4, c4 + 1
         const float4 gb = *reinterpret_cast<const float4*>(GD + (h * 128 + c4) * 2 + 4);    // ... of columns c4 + 2, c4 + 3
 #pragma unroll
@@ -522,6 +673,7 @@ struct GraphCfg {
   int32_t *d_env_off = nullptr, *d_env_L = nullptr, *d_env_relb = nullptr, *d_m_off = nullptr, *d_m_L = nullptr;
   float *d_rel = nullptr, *d_relb = nullptr;
   uint64_t last_use = 0;
+  uint64_t relb_epoch = 0;      // pack_epoch of the handle when d_relb was last computed under a weight hold (0: never)
   void release() {
     void* ptrs[] = {d_node_env, d_node_limb, d_node_mnode, d_trav, d_env_off, d_env_L, d_env_relb, d_m_off, d_m_L, d_rel, d_relb};
     for (void* q : ptrs) if (q) (void)hipFree(q);
@@ -559,9 +711,14 @@ struct sgrl_set {
   // row-scaled words) built by the first forward after the promise serves the following ones
   bool hold = false, packed_ok = false;
   int packed_form = 0;
+  bool packed_l0f = false;         // the held pack includes the layer-0 folds (k_fold_l0 runs only for forwards that take them)
   hipEvent_t ev_pack = nullptr;
   const float* l2mf_w = nullptr;   // live weights: decoder_g folded through linear2_m [32, 256] and its bias [32] (null: unfolded head)
   const float* l2mf_b = nullptr;
+  const float* l0f = nullptr;      // live weights: the layer-0 fold block (k_fold_l0; null: the bound plan has none -> unfolded layer 0)
+  bool l0fold_off = false;         // sgrl_set_debug_l0fold(s, 0)
+  uint64_t pack_epoch = 1;         // bumped by every pack: a batch structure's relation bias is current while its relb_epoch equals it
+  GraphCfg* cur = nullptr;         // the batch structure in use (use_cfg)
   unsigned short* d_tri = nullptr;
   bool stack_dirty = true;
   bool stack_critic = false;   // mode the stacked operands were built for
@@ -607,6 +764,7 @@ void free_graphs(sgrl_set* s) {
   if (s->ws) (void)hipFree(s->ws);
   s->ws = nullptr; s->ws_floats = 0; s->carved_N = 0;
   s->have_graph = false;
+  s->cur = nullptr;
 }
 
 template <class T>
@@ -658,6 +816,7 @@ int use_cfg(sgrl_set* s, GraphCfg* c) {
   s->d_env_off = c->d_env_off; s->d_env_L = c->d_env_L; s->d_env_relb = c->d_env_relb; s->d_m_off = c->d_m_off; s->d_m_L = c->d_m_L;
   s->d_rel = c->d_rel; s->d_relb = c->d_relb;
   c->last_use = ++s->use_clock;
+  s->cur = c;
   s->have_graph = true;
   return SGRL_OK;
 }
@@ -806,6 +965,7 @@ bool chain_enabled() {
 using sgrl_gemm::ChainArgs;
 using sgrl_gemm::k_chain;
 constexpr auto kSiteA = k_chain<1, 256, 0, 1>;                         // attention site: g -> Z -> Gram -> lg1 -> ReLU -> lg2
+constexpr auto kSiteA0 = k_chain<1, 256, 0, 0>;                        // attention site of layer 0, folded: V -> blocks of V'V -> lg1' -> ReLU -> lg2
 constexpr auto kSiteF = k_chain<1, 256, 0, 2>;                         // feed-forward site: g1 -> Z, Z2 -> ...
 constexpr auto kSiteH1 = k_chain<1, 128, 0, 1>;                        // head (critic): outg -> Z -> Gram -> l1g -> ReLU -> l2g
 constexpr auto kSiteH2 = k_chain<1, 128, 0, 2>;                        // head (actor): ... Z, Z2
@@ -813,7 +973,7 @@ constexpr auto kChainLn = k_chain<0, 256, EPI_ROWDIV | EPI_LN, 0>;     // linear
 constexpr auto kChainNg = k_chain<0, 128, 0, 0>;                       // linear1_ng -> ReLU -> linear2_ng
 constexpr auto kChainPlain = k_chain<0, 256, 0, 0>;                    // (test hook: the plain pair at hidden width 256)
 bool chain_raise_lds_limits() {
-  const void* ks[] = {reinterpret_cast<const void*>(kSiteA), reinterpret_cast<const void*>(kSiteF), reinterpret_cast<const void*>(kSiteH1),
+  const void* ks[] = {reinterpret_cast<const void*>(kSiteA0), reinterpret_cast<const void*>(kSiteA), reinterpret_cast<const void*>(kSiteF), reinterpret_cast<const void*>(kSiteH1),
                       reinterpret_cast<const void*>(kSiteH2), reinterpret_cast<const void*>(kChainLn), reinterpret_cast<const void*>(kChainNg),
                       reinterpret_cast<const void*>(kChainPlain)};
   for (const void* k : ks)
@@ -839,6 +999,18 @@ int launch_site(const GemmCtx& gx, hipStream_t st, const float* X, int ldx, int 
     if (z2) hipLaunchKernelGGL(kSiteH2, grid, dim3(512), sgrl_gemm::kChainLds, st, a);
     else hipLaunchKernelGGL(kSiteH1, grid, dim3(512), sgrl_gemm::kChainLds, st, a);
   }
+  return SGRL_OK;
+}
+// site A of layer 0 under the layer-0 fold: V [M, 3, 32] (columns 8..31 zero) -> relu(G3(V) . W1'^T + b1) . W2^T + b2 -> C[:, 0:128], G3 the
+// first three blocks of the Gram generator's order (K1 = 48).  The kernel's ||V'V||_F scales the generated operand; the row divisor
+// fn = ||Z0'Z0||_F + 1 is k_embed's and is not written here (fn_out null).
+int launch_site0(const GemmCtx& gx, hipStream_t st, const float* V, const float* W1, const float* b1, const float* W2, const float* b2, float* C,
+                 int ldc, int M) {
+  ChainArgs a{};
+  a.A = V; a.W1 = words_of(gx, W1); a.ldw1 = 48; a.b1 = b1; a.W2 = words_of(gx, W2); a.ldw2 = 256; a.b2 = b2; a.C = C; a.ldc = ldc; a.M = M; a.K1 = 48;
+  a.ws1 = wsc_of(gx, W1); a.ws2 = wsc_of(gx, W2);
+  if (!a.ws1 || !a.ws2) return sfail(SGRL_ERR_ARG, "site 0: a weight operand is not a matrix of the row-scale table");
+  hipLaunchKernelGGL(kSiteA0, dim3((M + sgrl_gemm::kChainRows - 1) / sgrl_gemm::kChainRows), dim3(512), sgrl_gemm::kChainLds, st, a);
   return SGRL_OK;
 }
 // ln_io[m][:] = LayerNorm(ln_io[m][:] + (relu(A . W1^T + b1) . W2^T + b2)[m][:] / rowdiv[m])      (hidden width 256)
@@ -969,6 +1141,7 @@ struct Forward {
   bool critic; const float* action; int action_ld;
   hipStream_t st, sd;                // the caller's stream, the side stream (one_stream: the caller's again)
   bool capturing, one_stream;
+  bool l0fold = false;               // the layer-0 fold is on for this forward (fused tile path, folds packed, not switched off)
   bool small, chain;                 // small-batch products | tile kernels with back-to-back products as one kernel each (neither: one launch per product)
   int ngf;
   GemmCtx gx;
@@ -1047,27 +1220,41 @@ struct Forward {
     // live weights: flat buffer (and the stacked projection operands in it) rebuilt from the parameters -- by every forward, unless
     // the caller holds the weights (sgrl_set_hold_weights) and this handle has packed them in the same product form since
     const bool want_words = !small && gx.form == SGRL_SET_FORM_F16X3 && gemm_use_split();
-    const bool reuse = s->live && s->hold && s->packed_ok && (!want_words || s->packed_form == SGRL_SET_FORM_F16X3) && !capturing;
+    const bool reuse = s->live && s->hold && s->packed_ok && (!want_words || s->packed_form == SGRL_SET_FORM_F16X3) && (!l0fold || s->packed_l0f) &&
+                       !capturing;
     if (reuse) (void)hipStreamWaitEvent(st, s->ev_pack, 0);      // (a forward on another stream than the one that packed)
     if (s->live && !reuse)
       hipLaunchKernelGGL(k_pack, dim3(s->n_chunks), dim3(256), 0, st, s->d_segs, s->d_chunks, s->d_tri, s->wflat);
+    if (s->live && !reuse && l0fold)        // the layer-0 folds, from the buffer just packed (before its matrices are encoded)
+      hipLaunchKernelGGL(k_fold_l0, dim3(kFoldL0Blocks), dim3(256), 0, st, s->site_ptr[0], s->W(SGRL_SET_GENC), s->WL(0, SGRL_SET_A_LG1_W),
+                         s->WL(0, SGRL_SET_VG_W), s->WL(0, SGRL_SET_A_GD), s->d_tri, s->wflat + (s->l0f - s->wflat));
     const bool encode = s->live && !reuse && want_words;
     if (encode) {          // the product matrices as row-scaled words: beside the embedding, which reads the f32 buffer only
       fork(whole);
       hipLaunchKernelGGL(sgrl_gemm::k_encode_rows, dim3((s->enc_rows + 3) / 4), dim3(256), 0, sd, s->wflat, s->wwords, s->wsc, s->d_enc, s->n_enc,
                          s->enc_rows);
     }
-    hipLaunchKernelGGL(k_relbias, dim3(s->n_morph), dim3(256), 0, st, s->d_rel, s->W(SGRL_SET_REL_W), s->W(SGRL_SET_REL_B),
-                       s->d_relb, s->d_m_off, s->d_m_L, s->n_morph);
+    // The relation bias depends on the relation weights and the batch structure's tables only: under a weight hold it is computed
+    // with the pack -- once per hold for each batch structure (relb_epoch), not at the top of every forward
+    if (s->live && !reuse && !capturing) s->pack_epoch++;
+    const bool holding = s->live && s->hold && !capturing;
+    const bool relb_cur = reuse && s->cur && s->cur->relb_epoch == s->pack_epoch;
+    if (!relb_cur)
+      hipLaunchKernelGGL(k_relbias, dim3(s->n_morph), dim3(256), 0, st, s->d_rel, s->W(SGRL_SET_REL_W), s->W(SGRL_SET_REL_B),
+                         s->d_relb, s->d_m_off, s->d_m_L, s->n_morph);
+    if (s->cur) s->cur->relb_epoch = holding ? s->pack_epoch : 0;
     hipLaunchKernelGGL(k_embed, dim3((N + kEmbedNodes - 1) / kEmbedNodes), dim3(128), 0, st, obs, obs_ld, action, action_ld, ngf, nt,
                        s->W(SGRL_SET_GENC), s->W(SGRL_SET_ENC_W), s->W(SGRL_SET_ENC_B), s->W(SGRL_SET_EMB0), s->W(SGRL_SET_EMB1),
-                       s->W(SGRL_SET_EMB2), s->g, s->cat, s->outg, s->outng, s->gdir, s->zc, s->z2, N);
+                       s->W(SGRL_SET_EMB2), s->g, s->cat, s->outg, s->outng, s->gdir, s->zc, s->z2, N, l0fold ? s->l0f : (const float*)nullptr,
+                       s->mat, s->fn);
     if (encode) join(whole);
     if (s->live && !reuse && !capturing) {
       s->packed_ok = s->hold;
       s->packed_form = want_words ? SGRL_SET_FORM_F16X3 : SGRL_SET_FORM_BF16X6;
-      if (s->hold) (void)hipEventRecord(s->ev_pack, st);
+      s->packed_l0f = l0fold;
     }
+    // (also behind a relation bias computed late in a hold: a forward on another stream waits for it with the pack)
+    if (holding && (!reuse || !relb_cur)) (void)hipEventRecord(s->ev_pack, st);
     s->cat_cur = s->cat;
     if (!s->live && (s->stack_dirty || s->stack_critic != critic)) {     // static weights: the sites' stacked operands, rebuilt on this stream
       s->stack_critic = critic;
@@ -1082,6 +1269,13 @@ struct Forward {
   }
   // attention, products: U = g . (Wgo_h Wvg_h)^T of both heads beside site A -> [inv | ng] -> qkv
   int attn_site(const Part& p, int l) const {
+    if (l == 0 && l0fold) {
+      // layer-0 fold: no projection prologue, linear_g1 over the three blocks of C = V'V (K = 48); fn comes from k_embed; no U product
+      int rc = launch_site0(gx, p.st, p.mat, s->l0f + kL0fW1, s->WL(l, SGRL_SET_A_LG1_B), s->WL(l, SGRL_SET_A_LG2_W), s->WL(l, SGRL_SET_A_LG2_B), p.catc, 256, p.M);
+      if (rc != SGRL_OK) return rc;
+      if (p.ev_site0) (void)hipEventRecord(p.ev_site0, p.st);
+      return gemm(p.st, p.catc, 256, s->WL(l, SGRL_SET_QKV_W), 256, s->WL(l, SGRL_SET_QKV_B), p.qkv, 768, p.M, 768, 256, EPI_ROWDIV, p.fn);
+    }
     fork(p);
     int rc = gemm(p.sd, p.g, D, s->WL(l, SGRL_SET_VG_W), D, nullptr, p.vg, 256, 3 * p.M, 256, D);
     if (rc == SGRL_OK)
@@ -1097,9 +1291,14 @@ struct Forward {
   // (k_attention finds its rows through the environment table: whole-batch base pointers)
   int attention(const Part& p, int l) const {
     const EnvTab etp{et.env_off + p.e0, et.env_L + p.e0, et.env_relb + p.e0};
-    hipLaunchKernelGGL(k_attention, dim3(p.ne), dim3(256), 0, p.st, s->qkv, s->vg, s->gdir, s->d_relb, etp, l == 0 ? 1 : 0,
-                       s->WL(l, SGRL_SET_NGOUT_B), s->WL(l, SGRL_SET_A_GD), s->stop_after == 2 * l ? s->delta : (float*)nullptr,
-                       s->g1, p.catc - 256 * (size_t)p.r0 + 128, 256, s->WL(l, SGRL_SET_N1_W), s->WL(l, SGRL_SET_N1_B));
+    if (l == 0 && l0fold)      // layer-0 fold: the value rows are V (in the rows of `mat`, k_embed), GD is Wu~
+      hipLaunchKernelGGL(k_attention<true>, dim3(p.ne), dim3(256), 0, p.st, s->qkv, s->mat, s->gdir, s->d_relb, etp, 1, s->WL(l, SGRL_SET_NGOUT_B),
+                         s->l0f + kL0fWu, s->stop_after == 2 * l ? s->delta : (float*)nullptr, s->g1, p.catc - 256 * (size_t)p.r0 + 128, 256,
+                         s->WL(l, SGRL_SET_N1_W), s->WL(l, SGRL_SET_N1_B));
+    else
+      hipLaunchKernelGGL(k_attention<false>, dim3(p.ne), dim3(256), 0, p.st, s->qkv, s->vg, s->gdir, s->d_relb, etp, l == 0 ? 1 : 0,
+                         s->WL(l, SGRL_SET_NGOUT_B), s->WL(l, SGRL_SET_A_GD), s->stop_after == 2 * l ? s->delta : (float*)nullptr,
+                         s->g1, p.catc - 256 * (size_t)p.r0 + 128, 256, s->WL(l, SGRL_SET_N1_W), s->WL(l, SGRL_SET_N1_B));
     return s->stop_after == 2 * l ? kStop : SGRL_OK;      // probe: g1 = attention's vector output, delta = its scalar output
   }
   // equivariant feed-forward, site F
@@ -1227,6 +1426,7 @@ int run_forward(sgrl_set* s, const float* obs, int obs_ld, float* act, int act_l
   f.et = EnvTab{s->d_env_off, s->d_env_L, s->d_env_relb};
   f.small = N <= (s->small_nodes >= 0 ? s->small_nodes : kSmallNodesDefault);
   f.chain = !f.small && chain_enabled() && gemm_use_split() && f.gx.form == SGRL_SET_FORM_F16X3;
+  f.l0fold = f.chain && s->live && s->l0f && !s->l0fold_off;
   // While `st` is being captured into a hipGraph (the TD3 update graphs, td3.GraphedUpdates: batches of 100 environments,
   // where every kernel is far too small to gain from overlap) everything stays on ONE stream: a graph with cross-stream
   // forks costs ~7 us of hipGraphLaunch CPU time per node on this ROCm, a single-stream graph ~0.4 us.
@@ -1364,7 +1564,7 @@ int sgrl_set_weights(sgrl_set* s, const float* w, const int64_t* offsets, int n_
   std::memcpy(s->off, offsets, sizeof(int64_t) * SGRL_SET_NW);
   s->have_w = true;
   s->live = false;
-  s->l2mf_w = nullptr; s->l2mf_b = nullptr;
+  s->l2mf_w = nullptr; s->l2mf_b = nullptr; s->l0f = nullptr;
   s->stack_dirty = true;   // the stacked projection operands are rebuilt by the next forward, on its stream
   return SGRL_OK;
 }
@@ -1444,6 +1644,7 @@ int sgrl_set_bind_params(sgrl_set* s, const sgrl_pack_seg* segs, int n_segs, con
       add(o[SGRL_SET_L1_W], 256, 256); add(o[SGRL_SET_L2_W], 128, 256); add(o[SGRL_SET_L5_W], 128, 32);
     }
     for (int k = 0; k < SGRL_SET_NSITES; k++) add(offsets[SGRL_SET_NW + k], 64, k == 6 ? OGLD : 128);
+    if (room(offsets[SGRL_SET_NW + SGRL_SET_NSITES + 2]) >= kL0fFloats) add(offsets[SGRL_SET_NW + SGRL_SET_NSITES + 2] + kL0fW1, 256, 48);   // W1' of the layer-0 fold
     if (s->d_enc) (void)hipFree(s->d_enc);
     if (s->wsc) (void)hipFree(s->wsc);
     s->d_enc = nullptr; s->wsc = nullptr;
@@ -1462,6 +1663,9 @@ int sgrl_set_bind_params(sgrl_set* s, const sgrl_pack_seg* segs, int n_segs, con
     const bool have = room(ow) >= 32 * 256;
     s->l2mf_w = have ? s->wflat + ow : nullptr;
     s->l2mf_b = have ? s->wflat + ob : nullptr;
+    // the layer-0 fold block: zero-filled by the plan, written by k_fold_l0 behind every pack (a 64-float filler: no fold)
+    const int64_t of = offsets[SGRL_SET_NW + SGRL_SET_NSITES + 2];
+    s->l0f = room(of) >= kL0fFloats ? s->wflat + of : nullptr;
   }
   s->live = true;
   s->have_w = true;
@@ -1622,6 +1826,13 @@ int sgrl_set_debug_stop_after(sgrl_set* s, int stage) {
 int sgrl_set_debug_small_nodes(sgrl_set* s, int nodes) {
   if (!s || nodes < -1) return sfail(SGRL_ERR_ARG, "sgrl_set_debug_small_nodes: bad argument");
   s->small_nodes = nodes;
+  return SGRL_OK;
+}
+
+int sgrl_set_debug_l0fold(sgrl_set* s, int on) {
+  if (!s) return sfail(SGRL_ERR_ARG, "sgrl_set_debug_l0fold: null handle");
+  if (s->l0fold_off != (on == 0)) s->generation++;     // a captured graph holds the kernels of the other layer-0 path
+  s->l0fold_off = on == 0;
   return SGRL_OK;
 }
 

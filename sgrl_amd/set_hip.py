@@ -43,6 +43,7 @@ def _bind(L):
     L.sgrl_set_debug_small_nodes.argtypes = [vp, ctypes.c_int]
     L.sgrl_set_last_split.argtypes = [vp]
     L.sgrl_set_gemm_form.argtypes = [vp, ctypes.c_int]
+    L.sgrl_set_debug_l0fold.argtypes = [vp, ctypes.c_int]
     L.sgrl_set_last_error.restype = ctypes.c_char_p
     L.sgrl_set_hold_weights.argtypes = [vp, ctypes.c_int]
     L.sgrl_set_debug_redos.argtypes = [ctypes.c_int]
@@ -142,7 +143,49 @@ def pack_tensors(sd, prefix="actor.", critic=False):
 
 
 NSITES = 7
-NEXTRA = 2          # folded head: decoder_g . linear2_m  [32, 256] and its bias [32] (include/sgrl_set.h)
+NEXTRA = 3          # folded head: decoder_g . linear2_m  [32, 256] and its bias [32]; the layer-0 fold block (include/sgrl_set.h)
+# the layer-0 fold block (csrc/set_actor.hip k_fold_l0): W1' [256, 48] | M~ [8, 32] | Q [8, 8] | Wu~ (stored [2, 8, 128])
+L0F_W1, L0F_MT, L0F_Q, L0F_WU, L0F_FLOATS = 0, 256 * 48, 256 * 48 + 256, 256 * 48 + 320, 256 * 48 + 320 + 2048
+
+
+def layer0_fold(net):
+    """The layer-0 fold matrices of one SET network in float64 NumPy, as k_fold_l0 builds them on the device behind every pack
+    (include/sgrl_set.h): at layer 0 the vector stream is g0 = sqrt(128) Wge v, rank 8, so with V [3, 8] a node's input vectors
+      Mt  [8, 32]      Z0 = V Mt: columns 0..29 = sqrt(128) (Wp Wge)', columns 30 / 31 = e1, e2 (gravity / direction)
+      W1p [256, 48]    linear_g1 of the attention site on the blocks (0,0), (1,0), (1,1) of C = V'V in the generator's order
+                       (k = 16 blk + 4 i + j): both positions of a symmetric pair inside a diagonal block share the pair's weight,
+                       an entry of the off-diagonal block carries (a, b) and (b, a)
+      Q   [8, 8]       Mt Mt' (||Z0'Z0||_F = ||V Q V'||_F)
+      Wu  [128, 2, 8]  sqrt(128) (Wgo_h Wvg_h) Wge per head, g_out's gravity / direction columns added at p = 1, 2"""
+    sd = {k: v.detach().double().cpu().numpy() for k, v in net.named_parameters()}
+    at = "transformer_encoder.layers.0.self_attn."
+    wge, wp = sd["g_encoder.weight"], sd[at + "g_proj.weight"]
+    sc = np.sqrt(128.0)
+    mt = np.zeros((8, 32))
+    mt[:, :30] = sc * (wp @ wge).T
+    mt[1, 30] = mt[2, 31] = 1.0
+    w1 = fold_gram_weight(torch.from_numpy(sd[at + "linear_g1.weight"])).numpy()            # [256, 576]
+    ia, ib, ok = (t.numpy() for t in gram_order())
+    T = np.einsum("rk,ak,bk->rab", w1[:, ok], mt[:, ia[ok]], mt[:, ib[ok]])
+    S = T + T.transpose(0, 2, 1)
+    w1p = np.zeros((256, 48))
+    for blk, (A, B) in enumerate(((0, 0), (1, 0), (1, 1))):
+        for i in range(4):
+            for j in range(4):
+                a, b = 4 * A + i, 4 * B + j
+                w1p[:, 16 * blk + 4 * i + j] = T[:, a, a] if a == b else (S[:, a, b] if A != B else 0.5 * S[:, a, b])
+    wgo, wvg = sd[at + "g_out.weight"], sd[at + "vg_proj.weight"]
+    wu = np.zeros((128, 2, 8))
+    for h in range(2):
+        wu[:, h, :] = sc * (wgo[:, 128 * h:128 * h + 126] @ wvg[126 * h:126 * h + 126]) @ wge
+        wu[:, h, 1] += wgo[:, 128 * h + 126]
+        wu[:, h, 2] += wgo[:, 128 * h + 127]
+    return dict(Mt=mt, W1p=w1p, Q=mt @ mt.T, Wu=wu)
+
+
+def blocks48(C):
+    """[..., 8, 8] -> [..., 48]: the blocks (0,0), (1,0), (1,1) of C in the Gram generator's order (the operand W1p acts on)"""
+    return np.concatenate([C[..., 4 * A:4 * A + 4, 4 * B:4 * B + 4].reshape(C.shape[:-2] + (16,)) for A, B in ((0, 0), (1, 0), (1, 1))], -1)
 PACK_COPY, PACK_PADCOL, PACK_FOLD, PACK_STACK, PACK_MATMUL, PACK_SUBMAT, PACK_PERM32 = 0, 1, 2, 3, 4, 5, 6
 # struct sgrl_pack_seg (include/sgrl_set.h)
 SEG_DTYPE = np.dtype([("dst", "<i8"), ("src0", "<u8"), ("src1", "<u8"), ("n", "<i4"), ("kind", "<i4"), ("a", "<i4"),
@@ -294,6 +337,8 @@ def plan_segments(net, critic=False):
         slot(NW + 7, zero); slot(NW + 8, zero)
     else:
         slot(NW + 7, head_fold, "weight"); slot(NW + 8, head_fold, "bias")
+    # the layer-0 fold block: products of slots packed above, so the library fills it behind the pack (k_fold_l0); the plan reserves it
+    slot(NW + 9, lambda: emit(PACK_COPY, anchor, L0F_FLOATS, a=0))
     align()
     return np.array(segs, dtype=SEG_DTYPE), offs, pos[0], srcs
 
@@ -445,6 +490,10 @@ class HipSetActor(object):
     def debug_small_nodes(self, nodes):
         """Batches of at most `nodes` nodes take the small-batch products (include/sgrl_set.h); 0 = never, -1 = default."""
         _check(self.L, self.L.sgrl_set_debug_small_nodes(self.h, int(nodes)), "sgrl_set_debug_small_nodes")
+
+    def debug_l0fold(self, on):
+        """The layer-0 fold of the fused tile path (include/sgrl_set.h): False = layer 0 runs unfolded like the others (A/B, tests)."""
+        _check(self.L, self.L.sgrl_set_debug_l0fold(self.h, 1 if on else 0), "sgrl_set_debug_l0fold")
 
     def last_split(self):
         """Nodes in the first half of the last forward; 0: it ran as a single pass (include/sgrl_set.h, the two-half forward)."""
