@@ -106,7 +106,8 @@ def resolve_models(env_names, xml_paths=None):
 class BatchedModularVecEnv(VecEnv):
     def __init__(self, env_names, envs_per_morph, obs_max_len=None, seed=0, device=None, max_episode_steps=1000,
                  xml_paths=None, env_id_base=0, max_rows=None,
-                 pgs_iters=model_pack.DEFAULT_PGS_ITERS, pgs_tol=model_pack.DEFAULT_PGS_TOL):
+                 pgs_iters=model_pack.DEFAULT_PGS_ITERS, pgs_tol=model_pack.DEFAULT_PGS_TOL,
+                 solver=model_pack.DEFAULT_SOLVER):
         """env_names: morphology / environment names (e.g. '3d_walker_7_full'), in the order the reference sorts them
         (main.py:99); envs_per_morph: int or list; env i of morphology k has global index sum(counts[:k]) + i."""
         import torch
@@ -141,7 +142,7 @@ class BatchedModularVecEnv(VecEnv):
         # constraint-row cap per morphology: multi-geom bodies (humanoid, cheetah) can touch the floor in many places
         rows_of = lambda m: max_rows if max_rows is not None else _lib.default_max_rows(m)
         self._blobs = [model_pack.pack_model(m, spec=env_spec_for(nm), max_rows=rows_of(m), pgs_iters=pgs_iters,
-                                             pgs_tol=pgs_tol) for m, nm in zip(self.models, self.env_names)]
+                                             pgs_tol=pgs_tol, solver=solver) for m, nm in zip(self.models, self.env_names)]
         L = _lib.lib()
         k = len(self._blobs)
         ibp = (ctypes.POINTER(ctypes.c_int32) * k)(*[b[0].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) for b in self._blobs])

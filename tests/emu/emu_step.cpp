@@ -15,6 +15,8 @@
 namespace {
 bool g_reverse = false;
 bool g_linv = true;   // exercise the explicit-inverse path (what HipWave takes for nv <= 24); 0 = always the L path
+int g_layout = 0;     // 0 = the dieted layout (kernels that read the int tables from global memory: make_layout with n_int = 0),
+                      // 1 = the default layout (the generic kernel and every other family kernel: int tables staged behind the slab)
 
 struct EmuWave {
   static constexpr bool kFixedDims = false;
@@ -107,24 +109,67 @@ struct EmuWave {
   template <class F> uint64_t ballot(int n, F f) { uint64_t m = 0; for (int i = 0; i < n; i++) if (f(i)) m |= (1ull << i); return m; }
   template <class F> double maxabs(int n, F f) { double s = 0; for (int i = 0; i < n; i++) { double v = std::fabs(f(i)); if (v > s) s = v; } return s; }
 };
+
+// the layout of a variant, as engine_kernel.h setup<D>() computes it: dieted = make_layout(hdr, o, 0, 0), default =
+// make_layout(hdr, o, n_int, 0) with n_int from the header
+void layout_of(const int32_t* ib, int variant, sgrl::Layout* o) {
+  int n_int = 0, n_f64 = 0;
+  if (variant) sgrl_model_blob_sizes(ib, &n_int, &n_f64);
+  sgrl::make_layout(ib, o, n_int, 0);
+}
+
+// One environment's "LDS": the layout of the selected variant, the slab poisoned (NaN / -12345), and the model view.  Default
+// variant: the int blob is copied behind the slab (I[o.model_i ...]) and the view's tables point at the copy, as setup<D>() stages
+// them -- every table read then goes through the slab offsets the device uses.
+struct Slab {
+  SgrlModelView m;
+  sgrl::Layout o;
+  std::vector<double> S;
+  std::vector<int32_t> I;
+  int n_int = 0;
+  const int32_t* ib = nullptr;
+  int init(const int32_t* ib_, const double* fb) {
+    ib = ib_;
+    layout_of(ib, g_layout, &o);
+    S.assign(o.s_total, NAN);
+    I.assign(o.i_total + 2, -12345);
+    if (!g_layout) return sgrl_model_view(ib, fb, &m);
+    int n_f64;
+    sgrl_model_blob_sizes(ib, &n_int, &n_f64);
+    for (int k = 0; k < n_int; k++) I[o.model_i + k] = ib[k];
+    return sgrl_model_view_dims(ib, ib, fb, I.data() + o.model_i, fb, &m);
+  }
+  // the staged tables are read-only and the two ints behind the slab are nobody's
+  bool intact() const {
+    for (int k = 0; k < n_int; k++) if (I[o.model_i + k] != ib[k]) return false;
+    return I[o.i_total] == -12345 && I[o.i_total + 1] == -12345;
+  }
+};
 }  // namespace
 
 extern "C" {
 
 void sgrl_emu_set_reverse(int r) { g_reverse = r != 0; }
 void sgrl_emu_set_linv(int v) { g_linv = v != 0; }
+void sgrl_emu_set_layout(int variant) { g_layout = variant != 0; }
 
-int sgrl_emu_layout_doubles(const int32_t* ib) { sgrl::Layout o; sgrl::make_layout(ib, &o); return o.s_total; }
-int sgrl_emu_layout_bytes(const int32_t* ib) { sgrl::Layout o; sgrl::make_layout(ib, &o); return sgrl::layout_bytes(&o); }
+int sgrl_emu_layout_doubles(const int32_t* ib) { sgrl::Layout o; layout_of(ib, g_layout, &o); return o.s_total; }
+int sgrl_emu_layout_bytes(const int32_t* ib) { sgrl::Layout o; layout_of(ib, g_layout, &o); return sgrl::layout_bytes(&o); }
+// out[0..3] = bytes, lrows, fstride, workgroups per CU of the given variant (0 dieted, 1 default)
+void sgrl_emu_layout_info(const int32_t* ib, int variant, int32_t* out) {
+  sgrl::Layout o; layout_of(ib, variant, &o);
+  out[0] = sgrl::layout_bytes(&o); out[1] = o.lrows; out[2] = o.fstride; out[3] = sgrl::workgroups_per_cu(out[0]);
+}
 
 // forward dynamics at (qpos, qvel, ctrl) -> qacc; also returns nrow / ncon
 int sgrl_emu_forward(const int32_t* ib, const double* fb, double* qpos, const double* qvel, const double* ctrl,
                      double* qacc, double* diag) {
-  SgrlModelView m;
-  if (sgrl_model_view(ib, fb, &m)) return -1;
-  sgrl::Layout o; sgrl::make_layout(ib, &o);
-  std::vector<double> S(o.s_total, NAN);
-  std::vector<int32_t> I(o.i_total + 2, -12345);
+  Slab sl;
+  if (sl.init(ib, fb)) return -1;
+  const SgrlModelView& m = sl.m;
+  const sgrl::Layout& o = sl.o;
+  std::vector<double>& S = sl.S;
+  std::vector<int32_t>& I = sl.I;
   EmuWave w;
   sgrl::Engine<EmuWave> e(w, m, o, S.data(), I.data());
   static std::vector<double> fscratch(sgrl::kScratchDoublesMax);
@@ -142,18 +187,19 @@ int sgrl_emu_forward(const int32_t* ib, const double* fb, double* qpos, const do
     for (int s = 0; s < o.ncon; s++) ncon += I[o.con_valid + s];
     diag[0] = ncon; diag[1] = I[o.icnt + sgrl::IC_NROW]; diag[2] = I[o.icnt + sgrl::IC_NROW_WANTED];
   }
-  return 0;
+  return sl.intact() ? 0 : -3;
 }
 
 // generic env call: op 0 = reset, 1 = step, 2 = refresh.  rec/cnt are the persistent record of one env.
 int sgrl_emu_env(int op, const int32_t* ib, const double* fb, double* rec, int32_t* cnt, const float* action,
                  float* obs32, double* obs64, int obs_max_len, uint64_t seed, uint32_t env_id, int max_episode_steps,
                  int auto_reset, double* reward64, uint8_t* done, float* dist, uint8_t* truncated) {
-  SgrlModelView m;
-  if (sgrl_model_view(ib, fb, &m)) return -1;
-  sgrl::Layout o; sgrl::make_layout(ib, &o);
-  std::vector<double> S(o.s_total, NAN);
-  std::vector<int32_t> I(o.i_total + 2, -12345);
+  Slab sl;
+  if (sl.init(ib, fb)) return -1;
+  const SgrlModelView& m = sl.m;
+  const sgrl::Layout& o = sl.o;
+  std::vector<double>& S = sl.S;
+  std::vector<int32_t>& I = sl.I;
   EmuWave w;
   sgrl::StepIO io;
   io.rec = rec; io.cnt = cnt; io.action = action; io.obs32 = obs32; io.obs64 = obs64; io.reward = nullptr;
@@ -164,6 +210,6 @@ int sgrl_emu_env(int op, const int32_t* ib, const double* fb, double* rec, int32
   if (op == 0) sgrl::env_reset(w, m, o, S.data(), I.data(), io, false);
   else if (op == 1) sgrl::env_step(w, m, o, S.data(), I.data(), io);
   else sgrl::env_refresh(w, m, o, S.data(), I.data(), io);
-  return 0;
+  return sl.intact() ? 0 : -3;
 }
 }

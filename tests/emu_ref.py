@@ -60,7 +60,7 @@ class EmuEnv(object):
                                 _p(act, _f32p), _p(obs32, _f32p), _p(obs64, _f64p), self.obs_max_len,
                                 ctypes.c_uint64(self.seed), ctypes.c_uint32(self.env_id), self.max_episode_steps,
                                 int(auto_reset), _p(rew, _f64p), _p(done, _u8p), _p(dist, _f32p), _p(trunc, _u8p))
-        assert rc == 0
+        assert rc == 0, {-1: "bad model", -3: "the staged int tables or the words behind the slab were written"}.get(rc, rc)
         return obs32, obs64, float(rew[0]), bool(done[0]), float(dist[0]), bool(trunc[0])
 
     def reset(self):
@@ -96,6 +96,28 @@ def set_reverse(flag):
 def set_linv(flag):
     """True (default): small systems take the explicit-inverse path, as HipWave does; False: always the L path."""
     lib().sgrl_emu_set_linv(int(bool(flag)))
+
+
+LAYOUTS = {"dieted": 0, "default": 1}
+
+
+def set_layout(name):
+    """The slab layout the emulator runs (step_body.h make_layout): "dieted" = what a kernel that reads the int tables from global
+    memory computes (n_int = 0: the humanoid family kernel), "default" = what the generic kernel and every other family kernel
+    compute (n_int from the header, the int tables staged behind the slab and read through the copy)."""
+    lib().sgrl_emu_set_layout(LAYOUTS[name])
+
+
+def layout_info(ib, variant):
+    """{"bytes", "lrows", "fstride", "workgroups_per_cu"} of a layout variant ("dieted" / "default"), whatever set_layout selected."""
+    ib = np.ascontiguousarray(ib, dtype=np.int32)
+    out = np.zeros(4, dtype=np.int32)
+    lib().sgrl_emu_layout_info(_p(ib, _i32p), LAYOUTS[variant], _p(out, _i32p))
+    return dict(zip(("bytes", "lrows", "fstride", "workgroups_per_cu"), (int(v) for v in out)))
+
+
+def layout_bytes(ib, variant):
+    return layout_info(ib, variant)["bytes"]
 
 
 # ---- two environments per wavefront (sgrl_amd/csrc/wave_half.h) on the SIMT fiber emulator (tests/emu/emu_pair.cpp) --------------
