@@ -115,6 +115,60 @@ int sgrl_mlp_chain_plan(const int32_t* actor_dims, int n_a, const int32_t* criti
 int sgrl_mlp_td_target_launches(void);
 int sgrl_mlp_critic_forward_launches(void);
 
+/* ---- gradient half of the TD3 update ---------------------------------------------------------------------------------------------
+ * Replaces the critics' forward with autograd, the two losses and their backward passes (reference src/agent.py:150-177):
+ *   critic step   loss = mse(Q1(obs, act), target) + mse(Q2(obs, act), target);  d loss / d every critic parameter   agent.py:150-160
+ *   actor step    loss = -mean(Q1(obs, actor(obs)));                             d loss / d every actor parameter    agent.py:167-173
+ * for MlpCritic / MlpPolicy (reference src/MLPCritic.py:40-52, src/MLPActor.py:45-66).  The clipping and the Adam steps
+ * (agent.py:161-164, 174-177) stay with the caller (include/sgrl_train.h sgrl_optim_clip_adam reads the gradients written here).
+ * A step is: the pack of every network it walks (the weights have just been stepped), ONE row-parallel launch (forward with the
+ * hidden activations stashed in a workspace, loss partials, backward down to every layer's pre-activation gradient G_l), and ONE
+ * weight-gradient launch in which a workgroup owns one 32 x 32 tile of one dW_l = G_l^T A_{l-1} and reduces over all rows itself in
+ * a fixed order (no split-K, no float atomics: the gradients are bit-repeatable); the bias gradients (column sums of G_l) and the
+ * reduction of the loss partials to one device float ride in that launch.  Products are exact f32 (v_mfma_f32_32x32x2_f32).  The
+ * gradients are WRITTEN (not accumulated) to the bound .grad tensors, unpadded.  No call synchronises with the host; after the first
+ * call at a batch size none allocates.  Served widths: every padded width up to SGRL_MLP_TRAIN_MAX_WIDTH (sgrl_mlp_train_plan). */
+#define SGRL_MLP_TRAIN_MAX_WIDTH 512
+
+/* HOST ONLY.  What the gradient half uses for an actor / critic pair at `batch` rows: info[0] = column chunks of 256 (1 or 2),
+ * info[1] = panel depth, info[2] = LDS bytes of a row-parallel workgroup, info[3] = activation row stride in floats (4 + the widest
+ * padded width, input or output, of either network), info[4] / info[5] = weight-gradient tiles (= workgroups of the second launch)
+ * of a critic / an actor step, info[6] = row tiles (workgroups of the first launch).  ws_floats[0] / ws_floats[1] = floats of the
+ * critic / actor handle's workspace at this batch: the stashed input tile [batch, kpad[0]], per stack the hidden activations
+ * [batch, npad[l]] and every G_l [batch, npad[l]], the loss partials (4 / 2 per row tile) and, for the actor, tanh(z)
+ * [batch, npad[last]] and the action rows [batch, out].  SGRL_ERR_ARG for what sgrl_mlp_plan refuses, a critic whose last width is
+ * not 1 or whose input is not the actor's input + output, batch outside 1 .. 2^24, and widths this path does not serve (a padded
+ * width above SGRL_MLP_TRAIN_MAX_WIDTH: the row-parallel kernels would need more accumulator registers than there are without
+ * scratch); the message says which. */
+int sgrl_mlp_train_plan(const int32_t* actor_dims, int n_a, const int32_t* critic_dims, int n_c, int batch, int32_t* info,
+                        int64_t* ws_floats);
+
+/* Bind the .grad tensors by address: ptrs is a HOST array of n_ptrs DEVICE addresses in the order (and of the shapes) of the
+ * parameter bind -- dW0, db0, dW1, db1, ... (a critic: stack 1's, then stack 2's).  Contiguous float32, 4-byte aligned.  A later
+ * parameter bind drops them.  SGRL_ERR_ARG for a null argument, a handle with no parameters, a wrong count, a null address. */
+int sgrl_mlp_bind_grads(sgrl_mlp* s, const void* const* ptrs, int n_ptrs);
+
+/* The critic step.  obs: DEV float [n_env, obs_ld]; act: DEV float [n_env, act_ld]; target_q: DEV float [n_env]; loss_out: DEV
+ * float[1] receives sum_s mean((Q_s - target)^2).  Every bound .grad of the critic receives d loss_out / d parameter.
+ * sgrl_mlp_critic_step_launches() launches (pack, row-parallel pass, weight gradients).  The workspace grows on demand (which bumps
+ * sgrl_mlp_generation; a capture cannot grow it).  SGRL_ERR_ARG BEFORE ANY LAUNCH, nothing written, for null pointers, narrow rows,
+ * a handle not bound as a critic or not configured, gradients not bound, widths the path does not serve. */
+int sgrl_mlp_critic_step_grads(sgrl_mlp* critic, const float* obs, int obs_ld, const float* act, int act_ld, const float* target_q,
+                               float* loss_out, void* stream);
+
+/* The actor step.  a = max_action * tanh(actor(obs)); loss_out: DEV float[1] receives -mean(Q1(obs, a)); every bound .grad of the
+ * ACTOR receives d loss_out / d parameter.  The critic's gradients are neither computed nor touched: its .grad tensors keep what
+ * the critic step (and the caller's clipping) left there.  action_out may be NULL; otherwise DEV float [n_env, action_ld], it
+ * receives a (columns beyond the output width are not written).  sgrl_mlp_actor_step_launches() launches (two packs -- the critic
+ * has been stepped since its own -- the row-parallel pass, the weight gradients).  SGRL_ERR_ARG before any launch, nothing written,
+ * for null pointers, narrow rows, handles of the wrong kind, actor gradients not bound, different batch structures, a critic that
+ * does not read the actor's input + output, widths the path does not serve. */
+int sgrl_mlp_actor_step_grads(sgrl_mlp* actor, sgrl_mlp* critic, const float* obs, int obs_ld, float max_action, float* loss_out,
+                              float* action_out, int action_ld, void* stream);
+
+int sgrl_mlp_critic_step_launches(void); /* 3 */
+int sgrl_mlp_actor_step_launches(void);  /* 4 */
+
 #ifdef __cplusplus
 }
 #endif

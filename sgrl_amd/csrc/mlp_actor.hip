@@ -28,33 +28,18 @@
 #include <cstdint>
 #include <string>
 
-#include "../../include/sgrl.h"
-#include "../../include/sgrl_mlp.h"
+#include "mlp_internal.h"
+
+using namespace sgrl_mlp_detail;
 
 namespace {
-
 thread_local std::string g_mlp_err;
-int mfail(int code, const std::string& msg) { g_mlp_err = msg; return code; }
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int NL = SGRL_MLP_MAX_LAYERS;
-constexpr int BM = SGRL_MLP_TILE_ROWS;
-constexpr int CH = 256;                 // output columns per chunk = rows of a weight panel
-constexpr int LDS_LIMIT = 160 * 1024;
-
-struct Plan {
-  int n_layers = 0;
-  int dims[NL + 1] = {0};
-  int kpad[NL] = {0}, npad[NL] = {0};
-  int64_t w_off[NL] = {0}, b_off[NL] = {0};
-  int64_t total = 0;
-  int maxch = 1, bk = 16, lds = 0, sx = 0;
-};
-
 int round_up(int x, int m) { return (x + m - 1) / m * m; }
+}  // namespace
 
-int make_plan(const int32_t* dims, int n_dims, Plan* p, const char* who) {
+int sgrl_mlp_detail::mfail(int code, const std::string& msg) { g_mlp_err = msg; return code; }
+
+int sgrl_mlp_detail::make_plan(const int32_t* dims, int n_dims, Plan* p, const char* who) {
   if (!dims) return mfail(SGRL_ERR_ARG, std::string(who) + ": dims is null");
   if (n_dims < 3 || n_dims > SGRL_MLP_MAX_HIDDEN + 2)
     return mfail(SGRL_ERR_ARG, std::string(who) + ": need 1 .. 4 hidden layers (3 .. 6 widths), got " + std::to_string(n_dims) + " widths");
@@ -84,6 +69,8 @@ int make_plan(const int32_t* dims, int n_dims, Plan* p, const char* who) {
   if (p->lds > LDS_LIMIT) return mfail(SGRL_ERR_LIMIT, std::string(who) + ": the activation tile does not fit in LDS");
   return SGRL_OK;
 }
+
+namespace {
 
 struct PackArgs {
   const float* w[2][NL];             // [stack][layer]: an actor packs one stack, a critic its two Q stacks back to back
@@ -118,23 +105,6 @@ __global__ __launch_bounds__(256) void k_mlp_pack(PackArgs a) {
         }
     }
     a.dst[g] = v;
-  }
-}
-
-struct Net {                         // one packed Linear / ReLU stack
-  const float* wp;
-  int n_layers;
-  int kpad[NL], npad[NL];
-  long long w_off[NL], b_off[NL];
-};
-
-// X[r][col0 + k] for k in [0, fill): src[row0 + r][k] where k < valid and the row exists, zeros elsewhere.
-__device__ __forceinline__ void load_rows(float* X, int sx, int col0, int valid, int fill, const float* __restrict__ src, int ld, int row0,
-                                          int n_env) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int r = wave; r < BM; r += 4) {
-    const int row = row0 + r;
-    for (int k = lane; k < fill; k += 64) X[r * sx + col0 + k] = (row < n_env && k < valid) ? src[(size_t)row * ld + k] : 0.f;
   }
 }
 
@@ -239,8 +209,6 @@ __device__ __forceinline__ void mlp_walk(const Net& a, float* X, float* Ws, int 
     __syncthreads();
   }
 }
-
-__device__ __forceinline__ int tile_row(int e) { return (e & 3) + 8 * (e >> 2) + 4 * ((threadIdx.x & 63) >> 5); }
 
 struct FwdArgs {
   const float* obs; int obs_ld;
@@ -424,24 +392,7 @@ ChainPlan make_chain_plan(const Plan& pa, const Plan& pc) {
 
 }  // namespace
 
-enum { KIND_NONE = 0, KIND_ACTOR = 1, KIND_CRITIC = 2 };
-
-struct sgrl_mlp {
-  Plan plan;
-  int kind = KIND_NONE;              // the last bind decides (sgrl_mlp_set_params / sgrl_mlp_set_critic_params)
-  const float* w[2][NL] = {{nullptr}};
-  const float* b[2][NL] = {{nullptr}};
-  float* packed = nullptr;           // n_stacks * plan.total floats
-  int64_t packed_floats = 0;
-  bool hold = false, dirty = true;
-  int n_env = 0;
-  int obs_w = 0, act_w = 0;          // a configured critic: columns of an observation / action row it reads
-  int64_t generation = 0;
-  fwd_fn kernel = nullptr;
-  critic_fn critic_kernel = nullptr;
-  float* ws = nullptr;               // a critic: the chain's target actions when the caller does not ask for them
-  int64_t ws_floats = 0;
-};
+enum { KIND_NONE = SGRL_MLP_KIND_NONE, KIND_ACTOR = SGRL_MLP_KIND_ACTOR, KIND_CRITIC = SGRL_MLP_KIND_CRITIC };   // struct sgrl_mlp: mlp_internal.h
 
 namespace {
 
@@ -460,26 +411,13 @@ int raise_lds(const void* fn, int family, int variant, int lds, const char* who)
 
 int n_stacks(const sgrl_mlp* s) { return s->kind == KIND_CRITIC ? 2 : 1; }
 
-Net make_net(const Plan& p, const float* wp) {
-  Net n;
-  n.wp = wp;
-  n.n_layers = p.n_layers;
-  for (int l = 0; l < NL; l++) {
-    const bool on = l < p.n_layers;
-    n.kpad[l] = on ? p.kpad[l] : 0;
-    n.npad[l] = on ? p.npad[l] : 0;
-    n.w_off[l] = on ? p.w_off[l] : 0;
-    n.b_off[l] = on ? p.b_off[l] : 0;
-  }
-  return n;
-}
-
-// The pack launch at the top of a forward, unless the handle holds clean weights (a capture always packs).
-int pack_if_needed(sgrl_mlp* s, hipStream_t st) {
+// The pack launch at the top of a forward, unless the handle holds clean weights (a capture always packs; `always`: the gradient
+// half, whose weights have just been stepped).
+int pack_if_needed(sgrl_mlp* s, hipStream_t st, bool always = false) {
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   (void)hipStreamIsCapturing(st, &cap);
   const bool capturing = cap != hipStreamCaptureStatusNone;
-  if (s->hold && !s->dirty && !capturing) return SGRL_OK;
+  if (s->hold && !s->dirty && !capturing && !always) return SGRL_OK;
   const Plan& p = s->plan;
   PackArgs pa;
   for (int l = 0; l < NL; l++) {
@@ -549,8 +487,8 @@ int bind_common(sgrl_mlp* s, const void* const* ptrs, int n_ptrs, const int32_t*
       s->w[k][l] = static_cast<const float*>(ptrs[2 * (k * p.n_layers + l)]);
       s->b[k][l] = static_cast<const float*>(ptrs[2 * (k * p.n_layers + l) + 1]);
     }
-  s->kernel = fn;
-  s->critic_kernel = cfn;
+  s->kernel = stacks == 1 ? reinterpret_cast<const void*>(fn) : reinterpret_cast<const void*>(cfn);
+  s->grads_bound = false;  // the gradient addresses follow the parameter bind: bind them again
   s->kind = stacks == 2 ? KIND_CRITIC : KIND_ACTOR;
   s->dirty = true;
   s->n_env = 0;           // the batch structure is checked against the widths: configure again
@@ -558,6 +496,8 @@ int bind_common(sgrl_mlp* s, const void* const* ptrs, int n_ptrs, const int32_t*
 }
 
 }  // namespace
+
+int sgrl_mlp_detail::pack_now(sgrl_mlp* s, hipStream_t st) { return pack_if_needed(s, st, true); }
 
 extern "C" {
 
@@ -612,6 +552,7 @@ void sgrl_mlp_destroy(sgrl_mlp* s) {
   if (!s) return;
   if (s->packed) (void)hipFree(s->packed);
   if (s->ws) (void)hipFree(s->ws);
+  if (s->tws) (void)hipFree(s->tws);
   delete s;
 }
 
@@ -674,7 +615,7 @@ int sgrl_mlp_forward(sgrl_mlp* s, const float* obs, int obs_ld, float* act, int 
   fa.net = make_net(p, s->packed);
   fa.max_action = max_action;
   const int grid = (s->n_env + BM - 1) / BM;
-  hipLaunchKernelGGL(s->kernel, dim3(grid), dim3(256), p.lds, st, fa);
+  hipLaunchKernelGGL(reinterpret_cast<fwd_fn>(const_cast<void*>(s->kernel)), dim3(grid), dim3(256), p.lds, st, fa);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return mfail(SGRL_ERR_HIP, std::string("MLP forward launch: ") + hipGetErrorString(e));
   return SGRL_OK;
@@ -696,7 +637,7 @@ int sgrl_mlp_critic_forward(sgrl_mlp* s, const float* obs, int obs_ld, const flo
   ca.c1 = make_net(p, s->packed);
   ca.c2 = make_net(p, s->packed + p.total);
   const int grid = (s->n_env + BM - 1) / BM;
-  hipLaunchKernelGGL(s->critic_kernel, dim3(grid), dim3(256), p.lds, st, ca);
+  hipLaunchKernelGGL(reinterpret_cast<critic_fn>(const_cast<void*>(s->kernel)), dim3(grid), dim3(256), p.lds, st, ca);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return mfail(SGRL_ERR_HIP, std::string("MLP critic forward launch: ") + hipGetErrorString(e));
   return SGRL_OK;

@@ -1,5 +1,5 @@
 """Batched HIP forwards of the monolithic MLP agent (csrc/mlp_actor.hip, C ABI in include/sgrl_mlp.h): the actor, the twin critic
-and the TD3 target chain, one launch each.
+and the TD3 target chain, one launch each; and of the gradient half of its TD3 update (csrc/mlp_train.hip, `HipMlpGrads`).
 
 `HipMlpActor` binds the `nn.Linear` parameters of an `MlpPolicy` (mlp_policy.py, reference-compatible state_dict) to a handle BY
 ADDRESS.  The library pads the widths in a packed copy of its own (`plan`), built by one pack launch at the top of a forward;
@@ -48,7 +48,16 @@ def _bind(L):
     L.sgrl_mlp_td_target.restype = ci
     L.sgrl_mlp_chain_plan.argtypes = [vp, ci, vp, ci, vp]
     L.sgrl_mlp_chain_plan.restype = ci
-    for name in ("sgrl_mlp_forward_launches", "sgrl_mlp_pack_launches", "sgrl_mlp_td_target_launches", "sgrl_mlp_critic_forward_launches"):
+    L.sgrl_mlp_train_plan.argtypes = [vp, ci, vp, ci, ci, vp, vp]
+    L.sgrl_mlp_train_plan.restype = ci
+    L.sgrl_mlp_bind_grads.argtypes = [vp, vp, ci]
+    L.sgrl_mlp_bind_grads.restype = ci
+    L.sgrl_mlp_critic_step_grads.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp]
+    L.sgrl_mlp_critic_step_grads.restype = ci
+    L.sgrl_mlp_actor_step_grads.argtypes = [vp, vp, vp, ci, cf, vp, vp, ci, vp]
+    L.sgrl_mlp_actor_step_grads.restype = ci
+    for name in ("sgrl_mlp_forward_launches", "sgrl_mlp_pack_launches", "sgrl_mlp_td_target_launches", "sgrl_mlp_critic_forward_launches",
+                 "sgrl_mlp_critic_step_launches", "sgrl_mlp_actor_step_launches"):
         getattr(L, name).argtypes = []
         getattr(L, name).restype = ci
     L.sgrl_mlp_num_envs.argtypes = [vp]
@@ -111,6 +120,23 @@ def chain_plan(actor_dims, critic_dims):
     vp = lambda x: ctypes.c_void_p(x.ctypes.data)
     _check(L, L.sgrl_mlp_chain_plan(vp(a), len(a), vp(c), len(c), vp(info)), "sgrl_mlp_chain_plan")
     return {"chunks": int(info[0]), "bk": int(info[1]), "lds_bytes": int(info[2]), "sx": int(info[3]), "tile_rows": TILE_ROWS}
+
+
+def train_plan(actor_dims, critic_dims, batch):
+    """What the gradient half of an update uses for an actor / critic pair at `batch` rows (include/sgrl_mlp.h sgrl_mlp_train_plan;
+    host only): dict of `chunks`, panel depth `bk`, `lds_bytes`, activation row stride `sx`, the weight-gradient workgroups of a
+    critic / an actor step (`critic_wgrad_tiles`, `actor_wgrad_tiles`), `row_tiles`, and the floats of the two handles' workspaces
+    (`critic_ws_floats`, `actor_ws_floats`).  Raises for what chain_plan refuses and for widths the path does not serve (a padded
+    layer width above 512)."""
+    L = _lib.lib()
+    _bind(L)
+    a, c = np.asarray(actor_dims, dtype=np.int32), np.asarray(critic_dims, dtype=np.int32)
+    info, ws = np.zeros(7, dtype=np.int32), np.zeros(2, dtype=np.int64)
+    vp = lambda x: ctypes.c_void_p(x.ctypes.data)
+    _check(L, L.sgrl_mlp_train_plan(vp(a), len(a), vp(c), len(c), int(batch), vp(info), vp(ws)), "sgrl_mlp_train_plan")
+    return {"chunks": int(info[0]), "bk": int(info[1]), "lds_bytes": int(info[2]), "sx": int(info[3]), "critic_wgrad_tiles": int(info[4]),
+            "actor_wgrad_tiles": int(info[5]), "row_tiles": int(info[6]), "critic_ws_floats": int(ws[0]), "actor_ws_floats": int(ws[1]),
+            "tile_rows": TILE_ROWS}
 
 
 class _HipMlpHandle(object):
@@ -372,3 +398,96 @@ class HipMlpTargets(object):
                                                  cf(float(noise_clip)), cf(float(discount)), vp(out.data_ptr()), act_ptr, act_ld, stream),
                "sgrl_mlp_td_target")
         return out
+
+
+class HipMlpGrads(object):
+    """The gradient half of a TD3 update of an MLP agent (reference src/agent.py:150-177 without the clipping and the optimizer
+    steps) on the HIP path: handles of its OWN on the online `MlpPolicy` and `MlpCritic` (never the modules' cached inference
+    handles: those may be holding weights for a collection round), persistent contiguous float32 `.grad` tensors for every parameter,
+    bound by address.  `critic_step` and `actor_step` WRITE the gradients (no zero_grad needed, nothing accumulates) and return the
+    loss as a 0-d device tensor; neither synchronises with the host.  Every step packs the live parameters first.
+
+    Stale gradients: `actor_step` computes the actor's gradients only.  Afterwards `critic.*.grad` still holds what `critic_step` and
+    the caller's clipping left there, not the reference's unused accumulation from the actor pass -- the documented state of
+    `Agent.update(skip_unused_critic_grads=True)`."""
+
+    def __init__(self, actor, critic):
+        if not torch.cuda.is_available():
+            raise _lib.SgrlError("HipMlpGrads needs an MI355X (no CPU fallback)")
+        self.actor, self.critic = HipMlpActor(actor), HipMlpCritic(critic)
+        self.L, self.device = self.actor.L, self.actor.device
+        a, c = self.actor, self.critic
+        self.plan(1)                                 # raises for pairs and widths the path does not serve
+        self._gbound = {id(a): None, id(c): None}
+        self._loss = torch.zeros(2, dtype=torch.float32, device=self.device)
+
+    def plan(self, batch=None):
+        return train_plan(self.actor.dims, self.critic.dims, batch or self.actor.n_env or 1)
+
+    def critic_launches(self):
+        """Kernel launches of one critic_step (constant: pack, row-parallel pass, weight gradients)."""
+        return int(self.L.sgrl_mlp_critic_step_launches())
+
+    def actor_launches(self):
+        """Kernel launches of one actor_step (constant: two packs, row-parallel pass, weight gradients)."""
+        return int(self.L.sgrl_mlp_actor_step_launches())
+
+    def _bind_grads(self, h):
+        """Parameters bound, every `.grad` a contiguous float32 tensor on the device (created where it is None or unusable), their
+        addresses bound; again whenever a parameter or a `.grad` has moved."""
+        h.sync_weights()
+        params = h._params()
+        for p in params:
+            g = p.grad
+            if g is None or g.dtype != torch.float32 or g.device != p.device or not g.is_contiguous() or g.shape != p.shape:
+                p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        ptrs = tuple(p.grad.data_ptr() for p in params)
+        if (ptrs, h._bound) != self._gbound[id(h)]:      # a parameter bind drops the gradient addresses (h._bound: what it bound)
+            arr = (ctypes.c_void_p * len(ptrs))(*ptrs)
+            _check(self.L, self.L.sgrl_mlp_bind_grads(h.h, ctypes.cast(arr, ctypes.c_void_p), len(ptrs)), "sgrl_mlp_bind_grads")
+            self._gbound[id(h)] = (ptrs, h._bound)
+        return params
+
+    def _configure(self, n):
+        g = [{"parents": [0] * self.actor.num_limbs}]
+        self.actor.configure(g, [n])
+        self.critic.configure(g, [n])
+
+    def critic_step(self, obs, action, target_q):
+        """mse(Q1(obs, action), target_q) + mse(Q2(obs, action), target_q) -> 0-d device tensor; its gradient in every critic
+        parameter's `.grad`.  obs [B, >= 41 L], action [B, >= 3 L], target_q [B] or [B, 1]: float32 CUDA."""
+        c = self.critic
+        self._configure(obs.shape[0])
+        params = self._bind_grads(c)
+        c.check_rows(obs, c.feature * c.num_limbs, "observation")
+        c.check_rows(action, c.act_feature * c.num_limbs, "action")
+        target_q = target_q.reshape(-1).contiguous()
+        assert target_q.is_cuda and target_q.dtype == torch.float32 and target_q.shape[0] == c.n_env
+        vp = ctypes.c_void_p
+        loss = self._loss[0]
+        stream = vp(torch.cuda.current_stream(self.device).cuda_stream)
+        _check(self.L, self.L.sgrl_mlp_critic_step_grads(c.h, vp(obs.data_ptr()), c._ld(obs), vp(action.data_ptr()), c._ld(action),
+                                                         vp(target_q.data_ptr()), vp(loss.data_ptr()), stream), "sgrl_mlp_critic_step_grads")
+        torch.autograd.graph.increment_version([p.grad for p in params])
+        return loss
+
+    def actor_step(self, obs, action_out=None):
+        """-mean(Q1(obs, actor(obs))) -> 0-d device tensor; its gradient in every ACTOR parameter's `.grad` (the critic's are left as
+        they are, see the class).  action_out: float32 [B, >= 3 L] contiguous, receives actor(obs)."""
+        a, c = self.actor, self.critic
+        self._configure(obs.shape[0])
+        params = self._bind_grads(a)
+        c.sync_weights()
+        a.check_rows(obs, a.dims[0], "observation")
+        vp = ctypes.c_void_p
+        act_ptr, act_ld = vp(None), 0
+        if action_out is not None:
+            assert action_out.is_cuda and action_out.dtype == torch.float32 and action_out.is_contiguous() and action_out.dim() == 2
+            assert action_out.shape[0] == a.n_env and action_out.shape[1] >= a.dims[-1], "action_out rows narrower than the actor's output"
+            act_ptr, act_ld = vp(action_out.data_ptr()), int(action_out.shape[1])
+        loss = self._loss[1]
+        stream = vp(torch.cuda.current_stream(self.device).cuda_stream)
+        _check(self.L, self.L.sgrl_mlp_actor_step_grads(a.h, c.h, vp(obs.data_ptr()), a._ld(obs), ctypes.c_float(float(a.policy.max_action)),
+                                                        vp(loss.data_ptr()), act_ptr, act_ld, stream), "sgrl_mlp_actor_step_grads")
+        torch.autograd.graph.increment_version([p.grad for p in params])
+        return loss

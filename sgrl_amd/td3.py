@@ -288,8 +288,13 @@ def default_train_args(**over):
     return a
 
 
+# Whether an mlp + mlp agent on the GPU takes the HIP gradient half (mlp_hip.HipMlpGrads) when the caller does not say: decided by
+# tools/mlp_update_bench.py (profiles/mlp_update_bench.json)
+MLP_HIP_GRADS_DEFAULT = True
+
+
 class Agent(nn.Module):
-    def __init__(self, args, device=None, use_hip=True):
+    def __init__(self, args, device=None, use_hip=True, mlp_hip_grads=None):
         super().__init__()
         self.args = args
         atype, ctype = getattr(args, "actor_type", "set"), getattr(args, "critic_type", "set")
@@ -353,13 +358,41 @@ class Agent(nn.Module):
         # chain packs from the live target parameters, so soft updates and load_state_dict need no notification
         self.use_mlp_hip = bool(use_hip) and atype == "mlp" and ctype == "mlp"
         self._mlp_targets = None
+        # mlp_hip_grads: the gradient half of an mlp + mlp update (critics' forward, both losses, both backward passes) on the HIP
+        # kernels too (mlp_hip.HipMlpGrads), for float32 batches on the GPU; None: MLP_HIP_GRADS_DEFAULT.  Follows use_hip; ignored by
+        # every other agent type and on the CPU
+        if mlp_hip_grads is None:
+            mlp_hip_grads = getattr(args, "mlp_hip_grads", None)     # so that a trainer's args can ask for it
+        if mlp_hip_grads is None:
+            mlp_hip_grads = MLP_HIP_GRADS_DEFAULT
+        self.use_mlp_hip_grads = self.use_mlp_hip and bool(mlp_hip_grads)
+        self._mlp_grads = None
 
     def __getstate__(self):
         d = self.__dict__.copy()
         d["_swat_targets"] = None     # per-process device handles: never pickled / deep-copied with the agent
         d["_smp_targets"] = None
         d["_mlp_targets"] = None
+        d["_mlp_grads"] = None
         return d
+
+    def _hip_grads(self, data_batch):
+        """mlp_hip.HipMlpGrads when this update's gradient half runs on HIP, else None.  Widths the kernels do not serve
+        (sgrl_mlp_train_plan refuses them, with a message kept in `mlp_hip_grads_refusal`) keep the PyTorch gradient half."""
+        obs = data_batch["obs"]
+        if not (self.use_mlp_hip_grads and obs.is_cuda and obs.dtype == torch.float32 and self.device.type == "cuda"):
+            return None
+        g = self._mlp_grads
+        if g is None or g.actor.policy is not self.actor or g.critic.module is not self.critic:
+            from . import _lib, mlp_hip             # raises SgrlError when the extension is missing (no fallback)
+            _lib.lib()
+            try:
+                mlp_hip.train_plan(mlp_hip.net_dims(self.actor.actor), mlp_hip.net_dims(self.critic.critic1), obs.shape[0])
+            except _lib.SgrlError as e:
+                self.use_mlp_hip_grads, self.mlp_hip_grads_refusal = False, str(e)
+                return None
+            g = self._mlp_grads = mlp_hip.HipMlpGrads(self.actor, self.critic)
+        return g
 
     def _hip_targets(self, next_obs):
         """swat_hip.HipSwatTargets / smp_hip.HipSmpTargets / mlp_hip.HipMlpTargets when this update's target chain runs on HIP, else
@@ -396,10 +429,35 @@ class Agent(nn.Module):
         """One TD3 step on a batch of ONE morphology (reference agent.py:117-183).  `noise` replaces the N(0, policy_noise)
         draw of agent.py:128 (tests: so that a run can be compared with the reference number for number; graph capture: a
         static buffer refilled before every replay).  lazy_stats: keep the two reward statistics as device tensors instead
-        of `.item()` floats (no host sync -- required inside a hipGraph capture)."""
+        of `.item()` floats (no host sync -- required inside a hipGraph capture).
+
+        With `mlp_hip_grads` (mlp + mlp agents, float32 batches on the GPU) everything after the target chain is
+        mlp_hip.HipMlpGrads.critic_step -> clip_and_step -> (policy iterations) actor_step -> clip_and_step -> soft updates: no
+        autograd graph, no zero_grad (the kernels overwrite `.grad`).  Stale gradients: after an actor step `critic.*.grad` holds
+        the CLIPPED critic-loss gradients, not the reference's unused accumulation from the actor pass -- the documented state of
+        skip_unused_critic_grads=True, whatever that argument says."""
+        grads = self._hip_grads(data_batch)
+        if grads is not None:
+            return self._update_hip_grads(grads, data_batch, it, noise, lazy_stats)
         reward_batch, target_Q = self.update_targets(data_batch, noise)
         current_Q1, current_Q2 = self.update_critic_forward(data_batch)
         return self.update_finish(data_batch, it, reward_batch, target_Q, current_Q1, current_Q2, lazy_stats, skip_unused_critic_grads)
+
+    def _update_hip_grads(self, grads, data_batch, it, noise, lazy_stats):
+        args = self.args
+        reward_batch, target_Q = self.update_targets(data_batch, noise)
+        obs_batch = data_batch["obs"].contiguous()
+        critic_loss = grads.critic_step(obs_batch, data_batch["action"].contiguous(), target_Q).clone()
+        clip_and_step(self.critic_optimizer, args.grad_clipping_value)
+        rmean, rvar = torch.mean(reward_batch), torch.var(reward_batch)
+        loss_dict = {"loss/critic_loss": critic_loss, "misc/train_reward_mean": rmean if lazy_stats else rmean.item(),
+                     "misc/train_reward_var": rvar if lazy_stats else rvar.item()}
+        if it % args.policy_freq == 0:       # delayed policy update
+            actor_loss = grads.actor_step(obs_batch).clone()
+            clip_and_step(self.actor_optimizer, args.grad_clipping_value)
+            self.try_update_target_network()
+            loss_dict.update({"loss/actor_loss": actor_loss})
+        return loss_dict
 
     # The three parts of an update.  The first two -- the no-grad target chain (actor_target -> critic_target) and the critics'
     # forward with autograd -- need nothing from each other: GraphedUpdates records them as separate graphs and replays them
