@@ -169,6 +169,52 @@ int sgrl_mlp_actor_step_grads(sgrl_mlp* actor, sgrl_mlp* critic, const float* ob
 int sgrl_mlp_critic_step_launches(void); /* 3 */
 int sgrl_mlp_actor_step_launches(void);  /* 4 */
 
+/* ---- optimizer half of the TD3 update --------------------------------------------------------------------------------------------
+ * Replaces, for ONE handle (an actor, 1 stack, or a critic, 2 stacks) whose parameters and gradients are bound, clip_grad_norm_ +
+ * Adam.step (reference src/agent.py:161-164, 174-177) and, with tau > 0, the soft update of the network's target
+ * (common/functional.py:7-10), in TWO launches:
+ *   coef = max_norm > 0 ? fminf(1, max_norm / (sqrtf(total) + 1e-6f)) : none        total = sum of g^2 over every bound gradient
+ *   g   := g * coef               (written back to .grad when max_norm > 0, as clip_grad_norm_ does)
+ *   t    = the first bound step counter, after every bound counter has been advanced by 1
+ *   m   := b1 m + (1 - b1) g;   v := b2 v + (1 - b2) g g;   p := p - (lr / (1 - b1^t)) * m / (sqrtf(v) / sqrtf(1 - b2^t) + eps)
+ *   tau > 0:  target := target * (1 - tau) + tau * p                                (the p just written)
+ * term for term as sgrl_optim_clip_adam / sgrl_optim_lerp of include/sgrl_train.h compute it (float32 tensors; lr, beta1, beta2, eps
+ * enter as doubles where they do there).  The tensors are cut into chunks of sgrl_mlp_optim_plan's chunk size, one workgroup per
+ * chunk.  Launch 1: partial[c] = sum of g^2 over chunk c, and workgroup 0 advances the counters (max_norm == 0: the counters only,
+ * one workgroup).  Launch 2: every workgroup re-adds all partials itself, then applies the formula to its chunk.  ORDER OF THE SUM,
+ * fixed (a step is bit-repeatable; no atomics): thread t of 256 owns elements 4 t .. 4 t + 3 of its chunk and adds their squares
+ * in order; a wave adds its lanes by a butterfly (6 additions); the four waves are added in order; in launch 2 thread t adds
+ * partials t, t + 256, ... serially, then the same butterfly and wave sum.  The longest chain of float additions from a g^2 to the
+ * total is 22 + ceil(chunks / 256), at most 63 for any handle the plan admits.  Accesses are 16 bytes wide where a tensor's
+ * addresses are 16-byte aligned, scalar in a tensor's ragged tail and for unaligned tensors, with the same bits either way.
+ * A step never synchronises with the host, allocates nothing, reads the step count on the device, and can be recorded into a
+ * hipGraph. */
+
+/* HOST ONLY.  info[0] = tensors of a handle of n_stacks stacks of the widths dims (2 * n_stacks * (n_dims - 1): W0, b0, W1, b1, ...
+ * per stack), info[1] = their elements, info[2] = chunks (= workgroups of either launch; a tensor of n elements has
+ * ceil(n / chunk size), chunks never span tensors), info[3] = the chunk size in elements.  SGRL_ERR_ARG for whatever sgrl_mlp_plan
+ * refuses, n_stacks other than 1 or 2, two stacks whose last width is not 1 (sgrl_mlp_set_critic_params binds no such critic). */
+int sgrl_mlp_optim_plan(const int32_t* dims, int n_dims, int n_stacks, int64_t* info);
+
+/* Bind the optimizer state by address: exp_avg / exp_avg_sq are HOST arrays of n DEVICE addresses in the order (and of the shapes)
+ * of the parameter bind, n = the plan's tensors; steps: n_steps (1 .. n) DEVICE float counters -- a step advances ALL of them by 1
+ * and reads the FIRST; target: n_target = 0, or n addresses of the target network's parameters in the same order.  partials: a
+ * DEVICE buffer of partial_floats >= the plan's chunks floats that stays the caller's (the library allocates nothing; a step
+ * overwrites it).  Everything contiguous float32, 4-byte aligned.  Needs the parameters AND the gradients bound; a later parameter
+ * bind drops this bind as it drops the gradient bind, and so does a later sgrl_mlp_bind_grads.  SGRL_ERR_ARG for a null argument, a
+ * handle without parameters or gradients, a wrong count, a null or unaligned address, a partials buffer that is too small. */
+int sgrl_mlp_bind_optim(sgrl_mlp* s, const void* const* exp_avg, const void* const* exp_avg_sq, int n, const void* const* steps, int n_steps,
+                        const void* const* target, int n_target, float* partials, int64_t partial_floats);
+/* 1 while the bind above stands, else 0. */
+int sgrl_mlp_optim_bound(const sgrl_mlp* s);
+
+/* One step (the formula above), asynchronous on `stream`.  max_norm == 0: no clipping, .grad is not written; tau == 0: the target
+ * is neither read nor written.  SGRL_ERR_ARG BEFORE ANY LAUNCH, nothing written, for a null handle, parameters, gradients or state
+ * not bound, tau > 0 with no target bound, tau outside [0, 1], max_norm < 0, a hyper-parameter that is not finite. */
+int sgrl_mlp_optim_step(sgrl_mlp* s, double lr, double beta1, double beta2, double eps, float max_norm, float tau, void* stream);
+
+int sgrl_mlp_optim_step_launches(void); /* 2 */
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
-// mlp_internal.h -- what the two translation units of the MLP family share (mlp_actor.hip: the no-grad forwards, the pack, the
-// handle; mlp_train.hip: the gradient half of a TD3 update): the width plan, the handle, the packed stack a kernel walks, the
+// mlp_internal.h -- what the three translation units of the MLP family share (mlp_actor.hip: the no-grad forwards, the pack, the
+// handle; mlp_train.hip: the gradient half of a TD3 update; mlp_optim.hip: its optimizer half): the width plan, the handle, the packed stack a kernel walks, the
 // tile loaders, and the few host helpers mlp_actor.hip defines for both.  Not part of the C ABI (include/sgrl_mlp.h).
 #ifndef SGRL_MLP_INTERNAL_H
 #define SGRL_MLP_INTERNAL_H
@@ -72,6 +72,7 @@ int pack_now(sgrl_mlp* s, hipStream_t st);                   // the pack launch,
 }  // namespace sgrl_mlp_detail
 
 enum { SGRL_MLP_KIND_NONE = 0, SGRL_MLP_KIND_ACTOR = 1, SGRL_MLP_KIND_CRITIC = 2 };
+enum { SGRL_MLP_BOUND_GRADS_AND_STATE = 2 };   // sgrl_mlp::grads_bound once sgrl_mlp_bind_optim has run
 
 struct sgrl_mlp {
   sgrl_mlp_detail::Plan plan;
@@ -90,9 +91,20 @@ struct sgrl_mlp {
   // the gradient half (mlp_train.hip): .grad addresses in the order of the parameter bind, and the stash workspace
   float* gw[2][sgrl_mlp_detail::NL] = {{nullptr}};
   float* gb[2][sgrl_mlp_detail::NL] = {{nullptr}};
-  bool grads_bound = false;
+  // 0 after a parameter bind, 1 (true) after sgrl_mlp_bind_grads, SGRL_MLP_BOUND_GRADS_AND_STATE after sgrl_mlp_bind_optim: the
+  // optimizer bind sits on top of the gradient bind, so whatever drops or renews the gradient bind drops it too
+  int grads_bound = 0;
   float* tws = nullptr;
   int64_t tws_floats = 0;
+  // the optimizer half (mlp_optim.hip): Adam state, step counters and target parameters by address, in the order of the parameter
+  // bind (index 2 * (stack * n_layers + layer) + (0 weight / 1 bias)); the partials buffer is the caller's
+  float* opt_m[4 * sgrl_mlp_detail::NL] = {nullptr};
+  float* opt_v[4 * sgrl_mlp_detail::NL] = {nullptr};
+  float* opt_target[4 * sgrl_mlp_detail::NL] = {nullptr};
+  float* opt_step[4 * sgrl_mlp_detail::NL] = {nullptr};
+  int opt_n_steps = 0;
+  bool opt_has_target = false;
+  float* opt_partial = nullptr;
 };
 
 #endif  // SGRL_MLP_INTERNAL_H

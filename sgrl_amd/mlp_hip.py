@@ -1,5 +1,6 @@
 """Batched HIP forwards of the monolithic MLP agent (csrc/mlp_actor.hip, C ABI in include/sgrl_mlp.h): the actor, the twin critic
-and the TD3 target chain, one launch each; and of the gradient half of its TD3 update (csrc/mlp_train.hip, `HipMlpGrads`).
+and the TD3 target chain, one launch each; and of the gradient half of its TD3 update (csrc/mlp_train.hip, `HipMlpGrads`) and its
+optimizer half (csrc/mlp_optim.hip, `HipMlpOptim`: clip, Adam and the soft target update of a network in two launches).
 
 `HipMlpActor` binds the `nn.Linear` parameters of an `MlpPolicy` (mlp_policy.py, reference-compatible state_dict) to a handle BY
 ADDRESS.  The library pads the widths in a packed copy of its own (`plan`), built by one pack launch at the top of a forward;
@@ -56,8 +57,17 @@ def _bind(L):
     L.sgrl_mlp_critic_step_grads.restype = ci
     L.sgrl_mlp_actor_step_grads.argtypes = [vp, vp, vp, ci, cf, vp, vp, ci, vp]
     L.sgrl_mlp_actor_step_grads.restype = ci
+    cd = ctypes.c_double
+    L.sgrl_mlp_optim_plan.argtypes = [vp, ci, ci, vp]
+    L.sgrl_mlp_optim_plan.restype = ci
+    L.sgrl_mlp_bind_optim.argtypes = [vp, vp, vp, ci, vp, ci, vp, ci, vp, ctypes.c_int64]
+    L.sgrl_mlp_bind_optim.restype = ci
+    L.sgrl_mlp_optim_bound.argtypes = [vp]
+    L.sgrl_mlp_optim_bound.restype = ci
+    L.sgrl_mlp_optim_step.argtypes = [vp, cd, cd, cd, cd, cf, cf, vp]
+    L.sgrl_mlp_optim_step.restype = ci
     for name in ("sgrl_mlp_forward_launches", "sgrl_mlp_pack_launches", "sgrl_mlp_td_target_launches", "sgrl_mlp_critic_forward_launches",
-                 "sgrl_mlp_critic_step_launches", "sgrl_mlp_actor_step_launches"):
+                 "sgrl_mlp_critic_step_launches", "sgrl_mlp_actor_step_launches", "sgrl_mlp_optim_step_launches"):
         getattr(L, name).argtypes = []
         getattr(L, name).restype = ci
     L.sgrl_mlp_num_envs.argtypes = [vp]
@@ -137,6 +147,18 @@ def train_plan(actor_dims, critic_dims, batch):
     return {"chunks": int(info[0]), "bk": int(info[1]), "lds_bytes": int(info[2]), "sx": int(info[3]), "critic_wgrad_tiles": int(info[4]),
             "actor_wgrad_tiles": int(info[5]), "row_tiles": int(info[6]), "critic_ws_floats": int(ws[0]), "actor_ws_floats": int(ws[1]),
             "tile_rows": TILE_ROWS}
+
+
+def optim_plan(dims, n_stacks):
+    """How the optimizer half cuts a handle of `n_stacks` stacks (1: an actor, 2: a critic) of the widths `dims` (include/sgrl_mlp.h
+    sgrl_mlp_optim_plan; host only): dict of `tensors`, `elements`, `chunks` (= workgroups of either launch) and `chunk` (elements
+    of a chunk).  Raises for what `plan` refuses, other stack counts, and two stacks whose last width is not 1."""
+    L = _lib.lib()
+    _bind(L)
+    d = np.asarray(dims, dtype=np.int32)
+    info = np.zeros(4, dtype=np.int64)
+    _check(L, L.sgrl_mlp_optim_plan(ctypes.c_void_p(d.ctypes.data), len(d), int(n_stacks), ctypes.c_void_p(info.ctypes.data)), "sgrl_mlp_optim_plan")
+    return {"tensors": int(info[0]), "elements": int(info[1]), "chunks": int(info[2]), "chunk": int(info[3])}
 
 
 class _HipMlpHandle(object):
@@ -491,3 +513,167 @@ class HipMlpGrads(object):
                                                         vp(loss.data_ptr()), act_ptr, act_ld, stream), "sgrl_mlp_actor_step_grads")
         torch.autograd.graph.increment_version([p.grad for p in params])
         return loss
+
+
+class _OptimSide(object):
+    """One network of a HipMlpOptim: the handle, its optimizer and target, and what is bound."""
+
+    def __init__(self, handle, opt, target_nets):
+        self.h, self.opt, self.target_nets = handle, opt, target_nets
+        self.key = None
+        self.partials = None
+        self.counter = None          # plain groups: the device step counter this object owns
+        self.host_step = None        # plain groups: the count `counter` holds
+
+
+class HipMlpOptim(object):
+    """The optimizer half of a TD3 update of an MLP agent (reference src/agent.py:161-164, 174-177 and the soft updates of
+    common/functional.py:7-10) on the HIP path: gradient clipping, the Adam step and, with tau > 0, the Polyak update of the target
+    network, for one network in TWO launches (include/sgrl_mlp.h "optimizer half", csrc/mlp_optim.hip).  Built over the two handles
+    of a `HipMlpGrads`, whose `.grad` tensors it reads; `critic_step(max_norm, tau)` / `actor_step(max_norm, tau)` replace
+    `td3.clip_and_step(opt, max_norm)` followed (tau > 0) by `td3.soft_update_network(net, target, tau)`.
+
+    The Adam state is the optimizers' own `opt.state[p]` (`exp_avg`, `exp_avg_sq`, `step`; created lazily exactly as torch.optim.Adam
+    / `td3.clip_and_step` create it), so `state_dict()` is unchanged and either path continues the other's count.  Groups whose
+    counters live on the device (`capturable`): those counters are bound, and the host-side count `td3.adam_step` keeps is advanced
+    with them.  Plain groups (CPU counters): this object owns ONE device counter per network, filled from the state when it binds
+    (and again only if somebody else has stepped the optimizer since), and advances the state's CPU counters on the host.  All
+    parameters of a network must share one step count.  Neither step synchronises with the host or allocates once bound; a bind
+    happens again when a parameter, gradient, state or target tensor has moved."""
+
+    def __init__(self, grads, actor_optimizer, critic_optimizer, actor_target=None, critic_target=None):
+        self.grads, self.L, self.device = grads, grads.L, grads.device
+        self.actor_optimizer, self.critic_optimizer = actor_optimizer, critic_optimizer
+        self.actor_target, self.critic_target = actor_target, critic_target
+        for opt, h in ((actor_optimizer, grads.actor), (critic_optimizer, grads.critic)):
+            why = self.refusal(opt, h._params())
+            if why:
+                raise _lib.SgrlError("HipMlpOptim: " + why)
+        self._actor = _OptimSide(grads.actor, actor_optimizer, [actor_target.actor] if actor_target is not None else None)
+        self._critic = _OptimSide(grads.critic, critic_optimizer,
+                                  [critic_target.critic1, critic_target.critic2] if critic_target is not None else None)
+
+    @staticmethod
+    def refusal(opt, params=None):
+        """Why this path does not serve the optimizer (None: it does): torch.optim.Adam with ONE group, no weight decay, no amsgrad,
+        not maximising -- the reference's optimizers (agent.py:96-115) -- over exactly `params`."""
+        if not isinstance(opt, torch.optim.Adam) or len(opt.param_groups) != 1:
+            return "one torch.optim.Adam with one parameter group is served"
+        g = opt.param_groups[0]
+        if g.get("weight_decay", 0) != 0 or g.get("amsgrad", False) or g.get("maximize", False) or g.get("differentiable", False):
+            return "weight decay, amsgrad, maximize and differentiable groups are not served"
+        if isinstance(g["lr"], torch.Tensor):
+            return "a tensor learning rate is not served"
+        if params is not None and sorted(id(p) for p in g["params"]) != sorted(id(p) for p in params):
+            return "the optimizer's group must hold exactly the network's parameters"
+        return None
+
+    def launches(self):
+        """Kernel launches of one critic_step or actor_step (constant: 2)."""
+        return int(self.L.sgrl_mlp_optim_step_launches())
+
+    def plan(self):
+        return {"actor": optim_plan(self.grads.actor.dims, 1), "critic": optim_plan(self.grads.critic.dims, 2)}
+
+    def critic_step(self, max_norm, tau=0.0):
+        """Clip the critic's gradients to max_norm (None / 0: no clipping), step its Adam, and with tau > 0 move the target critic."""
+        self._step(self._critic, max_norm, tau)
+
+    def actor_step(self, max_norm, tau=0.0):
+        self._step(self._actor, max_norm, tau)
+
+    def _state(self, side, params):
+        """opt.state[p] of every parameter, created where empty; -> (states, True when the counters live on the device)."""
+        opt = side.opt
+        on_device = bool(opt.param_groups[0].get("capturable", False) or opt.param_groups[0].get("fused", False))
+        states = []
+        for p in params:
+            st = opt.state[p]
+            if len(st) == 0:                  # torch.optim.Adam's lazy state initialisation
+                st["step"] = torch.zeros((), dtype=torch.float32, device=p.device) if on_device else torch.tensor(0.0, dtype=torch.float32)
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            states.append(st)
+        return states, states[0]["step"].is_cuda
+
+    def _step(self, side, max_norm, tau):
+        h, opt = side.h, side.opt
+        why = self.refusal(opt)
+        if why:
+            raise _lib.SgrlError("HipMlpOptim: " + why)
+        tau = float(tau)
+        params = self.grads._bind_grads(h)                 # parameters and .grad bound (again where one has moved)
+        states, on_device = self._state(side, params)
+        targets = [p for net in side.target_nets for l in linears(net) for p in (l.weight, l.bias)] if side.target_nets is not None else []
+        if tau > 0 and not targets:
+            raise _lib.SgrlError("HipMlpOptim: tau > 0 needs the target network")
+        if on_device:
+            host = opt.__dict__.setdefault("_sgrl_step_class", {})      # the count td3.adam_step keeps: advanced with the counters
+            for p, st in zip(params, states):
+                if id(p) not in host:
+                    host[id(p)] = int(st["step"].item())                # once per parameter, never in a steady step
+            counts = [host[id(p)] for p in params]
+        else:
+            counts = [float(st["step"]) for st in states]               # CPU tensors
+        if any(c != counts[0] for c in counts):
+            raise _lib.SgrlError("HipMlpOptim: the parameters of a network must share one step count (got %s)" % sorted(set(counts)))
+        key = (h._bound, tuple(p.grad.data_ptr() for p in params), tuple(st["exp_avg"].data_ptr() for st in states),
+               tuple(st["exp_avg_sq"].data_ptr() for st in states), tuple(st["step"].data_ptr() for st in states) if on_device else None,
+               tuple(t.data_ptr() for t in targets))
+        if key != side.key or not self.L.sgrl_mlp_optim_bound(h.h):
+            self._bind_side(side, params, states, targets, on_device)
+            side.key = key
+            side.host_step = None
+        if not on_device:
+            if side.host_step != counts[0]:                             # at the bind, or somebody else stepped the optimizer since
+                side.counter.fill_(counts[0])
+            side.host_step = counts[0] + 1
+        group = opt.param_groups[0]
+        beta1, beta2 = group["betas"]
+        clip = float(max_norm) if (max_norm and max_norm > 0) else 0.0
+        cdbl, cf = ctypes.c_double, ctypes.c_float
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _check(self.L, self.L.sgrl_mlp_optim_step(h.h, cdbl(float(group["lr"])), cdbl(float(beta1)), cdbl(float(beta2)), cdbl(float(group["eps"])),
+                                                  cf(clip), cf(tau), stream), "sgrl_mlp_optim_step")
+        if on_device:
+            for p in params:
+                host[id(p)] += 1
+        else:
+            for st in states:
+                st["step"] += 1
+        wrote = list(params) + [st["exp_avg"] for st in states] + [st["exp_avg_sq"] for st in states]
+        if clip > 0:
+            wrote += [p.grad for p in params]
+        if on_device:
+            wrote += [st["step"] for st in states]
+        if tau > 0:
+            wrote += targets
+        torch.autograd.graph.increment_version(wrote)
+
+    def _bind_side(self, side, params, states, targets, on_device):
+        h = side.h
+        for t in [st[k] for st in states for k in ("exp_avg", "exp_avg_sq")] + list(targets):
+            if not (t.is_cuda and t.device == self.device and t.dtype == torch.float32 and t.is_contiguous()):
+                raise _lib.SgrlError("HipMlpOptim: Adam state and target parameters must be contiguous float32 tensors on %s (got %s %s on %s)"
+                                     % (self.device, t.dtype, tuple(t.shape), t.device))
+        for p, t in zip(params, targets):
+            if t.shape != p.shape:
+                raise _lib.SgrlError("HipMlpOptim: the target network's parameters must have the network's shapes")
+        n = len(params)
+        chunks = optim_plan(h.dims, len(h.nets))["chunks"]
+        if side.partials is None or side.partials.numel() < chunks:
+            side.partials = torch.zeros(chunks, dtype=torch.float32, device=self.device)
+        if on_device:
+            for st in states:
+                if not (st["step"].is_cuda and st["step"].dtype == torch.float32):
+                    raise _lib.SgrlError("HipMlpOptim: device step counters must be float32")
+            steps = [st["step"].data_ptr() for st in states]
+        else:
+            if side.counter is None:
+                side.counter = torch.zeros(1, dtype=torch.float32, device=self.device)
+            steps = [side.counter.data_ptr()]
+        vp = ctypes.c_void_p
+        arr = lambda ptrs: ctypes.cast((vp * len(ptrs))(*ptrs), vp) if ptrs else vp(None)
+        m, v = arr([st["exp_avg"].data_ptr() for st in states]), arr([st["exp_avg_sq"].data_ptr() for st in states])
+        _check(self.L, self.L.sgrl_mlp_bind_optim(h.h, m, v, n, arr(steps), len(steps), arr([t.data_ptr() for t in targets]), len(targets),
+                                                  vp(side.partials.data_ptr()), int(side.partials.numel())), "sgrl_mlp_bind_optim")

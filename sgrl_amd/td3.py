@@ -291,10 +291,13 @@ def default_train_args(**over):
 # Whether an mlp + mlp agent on the GPU takes the HIP gradient half (mlp_hip.HipMlpGrads) when the caller does not say: decided by
 # tools/mlp_update_bench.py (profiles/mlp_update_bench.json)
 MLP_HIP_GRADS_DEFAULT = True
+# Whether such an agent also takes the HIP optimizer half (mlp_hip.HipMlpOptim: clip, Adam and the soft update of a network in two
+# launches) when the caller does not say: opt-in (tools/mlp_optim_bench.py, profiles/mlp_optim_bench.json)
+MLP_HIP_OPTIM_DEFAULT = False
 
 
 class Agent(nn.Module):
-    def __init__(self, args, device=None, use_hip=True, mlp_hip_grads=None):
+    def __init__(self, args, device=None, use_hip=True, mlp_hip_grads=None, mlp_hip_optim=None):
         super().__init__()
         self.args = args
         atype, ctype = getattr(args, "actor_type", "set"), getattr(args, "critic_type", "set")
@@ -367,6 +370,14 @@ class Agent(nn.Module):
             mlp_hip_grads = MLP_HIP_GRADS_DEFAULT
         self.use_mlp_hip_grads = self.use_mlp_hip and bool(mlp_hip_grads)
         self._mlp_grads = None
+        # mlp_hip_optim: the optimizer half as well (mlp_hip.HipMlpOptim); None: args.mlp_hip_optim, then MLP_HIP_OPTIM_DEFAULT.  Takes
+        # effect only together with the gradient half; ignored otherwise, as mlp_hip_grads is
+        if mlp_hip_optim is None:
+            mlp_hip_optim = getattr(args, "mlp_hip_optim", None)
+        if mlp_hip_optim is None:
+            mlp_hip_optim = MLP_HIP_OPTIM_DEFAULT
+        self.use_mlp_hip_optim = self.use_mlp_hip_grads and bool(mlp_hip_optim)
+        self._mlp_optim = None
 
     def __getstate__(self):
         d = self.__dict__.copy()
@@ -374,6 +385,7 @@ class Agent(nn.Module):
         d["_smp_targets"] = None
         d["_mlp_targets"] = None
         d["_mlp_grads"] = None
+        d["_mlp_optim"] = None
         return d
 
     def _hip_grads(self, data_batch):
@@ -393,6 +405,28 @@ class Agent(nn.Module):
                 return None
             g = self._mlp_grads = mlp_hip.HipMlpGrads(self.actor, self.critic)
         return g
+
+    def _hip_optim(self, grads):
+        """mlp_hip.HipMlpOptim over `grads` when this update's optimizer half runs on HIP, else None: off unless asked for
+        (`mlp_hip_optim`), and optimizers it does not serve (weight decay, amsgrad, maximize, more than one group; the reason is kept
+        in `mlp_hip_optim_refusal`) or a tau outside [0, 1] keep clip_and_step and soft_update_network."""
+        if not self.use_mlp_hip_optim:
+            return None
+        from .mlp_hip import HipMlpOptim
+        o = self._mlp_optim
+        if o is None or o.grads is not grads or o.actor_optimizer is not self.actor_optimizer or o.critic_optimizer is not self.critic_optimizer \
+                or o.actor_target is not self.actor_target or o.critic_target is not self.critic_target:
+            o = self._mlp_optim = None
+        why = HipMlpOptim.refusal(self.actor_optimizer, grads.actor._params() if o is None else None) or \
+            HipMlpOptim.refusal(self.critic_optimizer, grads.critic._params() if o is None else None)
+        if why is None and not 0.0 <= float(self.target_smoothing_tau) <= 1.0:
+            why = "target_smoothing_tau outside [0, 1]"
+        self.mlp_hip_optim_refusal = why
+        if why is not None:
+            return None
+        if o is None:
+            o = self._mlp_optim = HipMlpOptim(grads, self.actor_optimizer, self.critic_optimizer, self.actor_target, self.critic_target)
+        return o
 
     def _hip_targets(self, next_obs):
         """swat_hip.HipSwatTargets / smp_hip.HipSmpTargets / mlp_hip.HipMlpTargets when this update's target chain runs on HIP, else
@@ -435,7 +469,9 @@ class Agent(nn.Module):
         mlp_hip.HipMlpGrads.critic_step -> clip_and_step -> (policy iterations) actor_step -> clip_and_step -> soft updates: no
         autograd graph, no zero_grad (the kernels overwrite `.grad`).  Stale gradients: after an actor step `critic.*.grad` holds
         the CLIPPED critic-loss gradients, not the reference's unused accumulation from the actor pass -- the documented state of
-        skip_unused_critic_grads=True, whatever that argument says."""
+        skip_unused_critic_grads=True, whatever that argument says.  With `mlp_hip_optim` as well, each clip_and_step and the soft
+        update of the same network are one mlp_hip.HipMlpOptim step (two launches); the target critic is then written before the
+        actor pass, which reads the online critic only."""
         grads = self._hip_grads(data_batch)
         if grads is not None:
             return self._update_hip_grads(grads, data_batch, it, noise, lazy_stats)
@@ -447,15 +483,25 @@ class Agent(nn.Module):
         args = self.args
         reward_batch, target_Q = self.update_targets(data_batch, noise)
         obs_batch = data_batch["obs"].contiguous()
+        policy_it = it % args.policy_freq == 0       # delayed policy update
+        optim = self._hip_optim(grads)
         critic_loss = grads.critic_step(obs_batch, data_batch["action"].contiguous(), target_Q).clone()
-        clip_and_step(self.critic_optimizer, args.grad_clipping_value)
+        if optim is not None:
+            # the soft update of the target critic rides in the critic's apply pass: the actor pass below reads the online critic
+            # only, so the parameters end as in the reference's order (agent.py:161-183: both steps, then both soft updates)
+            optim.critic_step(args.grad_clipping_value, self.target_smoothing_tau if policy_it else 0.0)
+        else:
+            clip_and_step(self.critic_optimizer, args.grad_clipping_value)
         rmean, rvar = torch.mean(reward_batch), torch.var(reward_batch)
         loss_dict = {"loss/critic_loss": critic_loss, "misc/train_reward_mean": rmean if lazy_stats else rmean.item(),
                      "misc/train_reward_var": rvar if lazy_stats else rvar.item()}
-        if it % args.policy_freq == 0:       # delayed policy update
+        if policy_it:
             actor_loss = grads.actor_step(obs_batch).clone()
-            clip_and_step(self.actor_optimizer, args.grad_clipping_value)
-            self.try_update_target_network()
+            if optim is not None:
+                optim.actor_step(args.grad_clipping_value, self.target_smoothing_tau)
+            else:
+                clip_and_step(self.actor_optimizer, args.grad_clipping_value)
+                self.try_update_target_network()
             loss_dict.update({"loss/actor_loss": actor_loss})
         return loss_dict
 
