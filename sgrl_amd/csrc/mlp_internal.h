@@ -1,6 +1,7 @@
-// mlp_internal.h -- what the three translation units of the MLP family share (mlp_actor.hip: the no-grad forwards, the pack, the
-// handle; mlp_train.hip: the gradient half of a TD3 update; mlp_optim.hip: its optimizer half): the width plan, the handle, the packed stack a kernel walks, the
-// tile loaders, and the few host helpers mlp_actor.hip defines for both.  Not part of the C ABI (include/sgrl_mlp.h).
+// mlp_internal.h -- the host side the three translation units of the MLP family share (mlp_actor.hip: the no-grad forwards, the pack,
+// the handle; mlp_train.hip: the gradient half of a TD3 update; mlp_optim.hip: its optimizer half): the width plan, the tile variant a
+// kernel is launched with, the handle, the packed stack a kernel walks, and the host helpers every entry point uses, each defined once
+// in mlp_actor.hip.  The device code the row-tile kernels share is in mlp_tile.h.  Not part of the C ABI (include/sgrl_mlp.h).
 #ifndef SGRL_MLP_INTERNAL_H
 #define SGRL_MLP_INTERNAL_H
 
@@ -21,13 +22,17 @@ constexpr int BM = SGRL_MLP_TILE_ROWS;
 constexpr int CH = 256;                 // output columns per chunk = rows of a weight panel
 constexpr int LDS_LIMIT = 160 * 1024;
 
-struct Plan {
+// The variant of a row-tile kernel and its dynamic LDS: chunks of accumulators, panel depth, bytes, activation row stride.
+struct TilePlan {
+  int maxch = 1, bk = 16, lds = 0, sx = 0;
+};
+
+struct Plan : TilePlan {
   int n_layers = 0;
   int dims[NL + 1] = {0};
   int kpad[NL] = {0}, npad[NL] = {0};
   int64_t w_off[NL] = {0}, b_off[NL] = {0};
   int64_t total = 0;
-  int maxch = 1, bk = 16, lds = 0, sx = 0;
 };
 
 struct Net {                         // one packed Linear / ReLU stack
@@ -51,23 +56,29 @@ inline Net make_net(const Plan& p, const float* wp) {
   return n;
 }
 
-// X[r][col0 + k] for k in [0, fill): src[row0 + r][k] where k < valid and the row exists, zeros elsewhere.
-__device__ __forceinline__ void load_rows(float* X, int sx, int col0, int valid, int fill, const float* __restrict__ src, int ld, int row0,
-                                          int n_env) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int r = wave; r < BM; r += 4) {
-    const int row = row0 + r;
-    for (int k = lane; k < fill; k += 64) X[r * sx + col0 + k] = (row < n_env && k < valid) ? src[(size_t)row * ld + k] : 0.f;
-  }
-}
-
-// C/D layout of a 32 x 32 tile: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
-__device__ __forceinline__ int tile_row(int e) { return (e & 3) + 8 * (e >> 2) + 4 * ((threadIdx.x & 63) >> 5); }
-
-// Defined in mlp_actor.hip.
+// Defined in mlp_actor.hip.  `who` is the entry point's name: it opens every message.
 int mfail(int code, const std::string& msg);                 // sets sgrl_mlp_last_error
 int make_plan(const int32_t* dims, int n_dims, Plan* p, const char* who);
 int pack_now(sgrl_mlp* s, hipStream_t st);                   // the pack launch, whatever the hold says
+int lds_bytes(int sx, int bk);                               // the activation tile [BM][sx] and two panel stages [CH][bk + 4]
+TilePlan tile_plan(int maxch, int sx);                       // the deepest panel (16, else 8) that fits beside the activation tile
+void put_tile_plan(const TilePlan& t, int32_t* info);        // info[0 .. 3] of the three plan entry points
+// The dynamic-LDS limit of a kernel is a property of the function, process-wide: the largest size asked for so far is kept per kernel
+// and the attribute only ever goes up (handles of different widths share a variant).
+int raise_lds(const void* fn, int lds, const char* who);
+// A fresh device buffer of `need` floats in place of *buf (`what` names it in the messages): refused while capturing; the old buffer,
+// if any, is freed behind a device synchronise (work in flight may still use it) and the handle's generation is bumped.  The caller
+// decides when: the packed weights whenever the size differs, the workspaces only when it grows.
+int grow(float** buf, int64_t* floats, int64_t need, bool capturing, int64_t* generation, const char* who, const char* what);
+bool is_capturing(hipStream_t st);
+int launched(const char* what);                              // hipGetLastError behind a launch -> "<what> launch: ..."
+int n_stacks(const sgrl_mlp* s);                             // a critic packs its two Q stacks, an actor one
+// Both plans of an actor / critic pair, a critic whose last width is 1 and whose input is the actor's input + output width.
+int make_pair_plans(const int32_t* actor_dims, int n_a, const int32_t* critic_dims, int n_c, Plan* pa, Plan* pc, const char* who);
+// Two configured handles of an actor / critic pair: kinds, batch structure set and equal, the critic reads the actor's input + output.
+int check_pair(const sgrl_mlp* actor, const sgrl_mlp* critic, const char* who);
+// n addresses, none null, all 4-byte aligned; `what` names one in the message ("<who>: <what> <i> is null or not 4-byte aligned")
+int check_addresses(const void* const* ptrs, int n, const char* who, const char* what);
 
 }  // namespace sgrl_mlp_detail
 

@@ -23,6 +23,8 @@
 // The longest chain of float additions from any g^2 to `total` is therefore 22 + ceil(chunks / 256): 24 for the [256, 256] nets,
 // 28 at ~1 500 partials, and at most 22 + 41 = 63 <= 128 for the largest handle the plan admits (two stacks of five 1024-wide layers,
 // 10 250 chunks).
+//
+// The plan, the handle and the host helpers of the family (stack count, address checks, launch check) come from mlp_internal.h.
 #include "mlp_internal.h"
 
 #include <cmath>
@@ -173,12 +175,6 @@ Cut make_cut(const Plan& p, int stacks) {
   return c;
 }
 
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mfail(SGRL_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
-  return SGRL_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -205,8 +201,7 @@ int sgrl_mlp_bind_optim(sgrl_mlp* s, const void* const* exp_avg, const void* con
   if (!s || !exp_avg || !exp_avg_sq || !steps || !partials) return mfail(SGRL_ERR_ARG, std::string(who) + ": null argument");
   if (s->kind == SGRL_MLP_KIND_NONE) return mfail(SGRL_ERR_ARG, std::string(who) + ": parameters not set (sgrl_mlp_set_params / sgrl_mlp_set_critic_params)");
   if (!s->grads_bound) return mfail(SGRL_ERR_ARG, std::string(who) + ": gradients not bound (sgrl_mlp_bind_grads)");
-  const int stacks = s->kind == SGRL_MLP_KIND_CRITIC ? 2 : 1;
-  const Cut c = make_cut(s->plan, stacks);
+  const Cut c = make_cut(s->plan, n_stacks(s));
   if (n != c.tensors) return mfail(SGRL_ERR_ARG, std::string(who) + ": expected " + std::to_string(c.tensors) + " state addresses, got " + std::to_string(n));
   if (n_steps < 1 || n_steps > c.tensors)
     return mfail(SGRL_ERR_ARG, std::string(who) + ": expected 1 .. " + std::to_string(c.tensors) + " step counters, got " + std::to_string(n_steps));
@@ -216,13 +211,12 @@ int sgrl_mlp_bind_optim(sgrl_mlp* s, const void* const* exp_avg, const void* con
   if (partial_floats < c.chunks)
     return mfail(SGRL_ERR_ARG, std::string(who) + ": the partials buffer holds " + std::to_string(partial_floats) + " floats, the handle has " +
                                    std::to_string(c.chunks) + " chunks");
-  auto bad = [](const void* p) { return !p || (reinterpret_cast<uintptr_t>(p) & 3); };
-  if (bad(partials)) return mfail(SGRL_ERR_ARG, std::string(who) + ": the partials buffer is not 4-byte aligned");
-  for (int i = 0; i < n; i++)
-    if (bad(exp_avg[i]) || bad(exp_avg_sq[i]) || (n_target && bad(target[i])))
-      return mfail(SGRL_ERR_ARG, std::string(who) + ": state or target address " + std::to_string(i) + " is null or not 4-byte aligned");
-  for (int i = 0; i < n_steps; i++)
-    if (bad(steps[i])) return mfail(SGRL_ERR_ARG, std::string(who) + ": step counter " + std::to_string(i) + " is null or not 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(partials) & 3) return mfail(SGRL_ERR_ARG, std::string(who) + ": the partials buffer is not 4-byte aligned");
+  int rc = check_addresses(exp_avg, n, who, "state or target address");
+  if (rc == SGRL_OK) rc = check_addresses(exp_avg_sq, n, who, "state or target address");
+  if (rc == SGRL_OK && n_target) rc = check_addresses(target, n, who, "state or target address");
+  if (rc == SGRL_OK) rc = check_addresses(steps, n_steps, who, "step counter");
+  if (rc != SGRL_OK) return rc;
   for (int i = 0; i < n; i++) {
     s->opt_m[i] = static_cast<float*>(const_cast<void*>(exp_avg[i]));
     s->opt_v[i] = static_cast<float*>(const_cast<void*>(exp_avg_sq[i]));
@@ -249,9 +243,8 @@ int sgrl_mlp_optim_step(sgrl_mlp* s, double lr, double beta1, double beta2, doub
   if (max_norm < 0.f) return mfail(SGRL_ERR_ARG, std::string(who) + ": max_norm is negative");
   if (tau < 0.f || tau > 1.f) return mfail(SGRL_ERR_ARG, std::string(who) + ": tau outside [0, 1]");
   if (tau > 0.f && !s->opt_has_target) return mfail(SGRL_ERR_ARG, std::string(who) + ": tau > 0 with no target bound");
-  const int stacks = s->kind == SGRL_MLP_KIND_CRITIC ? 2 : 1;
   const int nl = s->plan.n_layers;
-  const Cut c = make_cut(s->plan, stacks);
+  const Cut c = make_cut(s->plan, n_stacks(s));
   OptArgs a;
   for (int i = 0; i < kMaxT; i++) {
     const bool on = i < c.tensors;

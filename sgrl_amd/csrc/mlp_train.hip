@@ -2,12 +2,13 @@
 // autograd did for the critic loss and the actor loss, as two launches per step on top of the pack.
 //
 //   k_mlp_critic_fb  one workgroup (4 waves) per 32 batch rows, both Q stacks in one launch.  Per stack: the cat([obs, action]) tile
-//                    into the LDS activation tile X[32][sx]; every layer forward as in mlp_actor.hip (whole output row block in
-//                    registers, weights streamed through a double-buffered LDS panel), the post-ReLU rows ALSO stored to the
-//                    workspace (A_l [B][npad_l]); q, dq = 2 (q - target) / B, the tile's partial of sum (q - target)^2; then back:
-//                    G_l = (G_{l+1} . W_{l+1}) (.) (A_l > 0) with G_{l+1} in X as the row operand and ROWS of the packed
-//                    [npad][kpad] weight as panels (reduction over npad, output columns = kpad: contiguous reads, no transposed
-//                    copy); every G_l stored to the workspace.
+//                    into the LDS activation tile X[32][sx]; every layer forward by mlp_walk (mlp_tile.h, the walk of the
+//                    no-grad forwards: whole output row block in registers, weights streamed through a double-buffered LDS
+//                    panel) with a stash, so the post-ReLU rows ALSO go to the workspace (A_l [B][npad_l]); q,
+//                    dq = 2 (q - target) / B, the tile's partial of sum (q - target)^2; then back:
+//                    G_l = (G_{l+1} . W_{l+1}) (.) (A_l > 0) -- the backward form of the same panel product, tile_gemm -- with
+//                    G_{l+1} in X as the row operand and ROWS of the packed [npad][kpad] weight as panels (reduction over npad,
+//                    output columns = kpad: contiguous reads, no transposed copy); every G_l stored to the workspace.
 //   k_mlp_actor_fb   actor forward with stash, a = max_action * tanh(z) (tanh(z) stashed), the critic's input tile from obs and a
 //                    (action columns re-read by the lanes that stored them, as k_mlp_chain), Q1 forward with stash, dq = -1 / B, the
 //                    tile's partial of sum q1, Q1 back down to its input's ACTION columns (K = npad_0, 3 L output columns read at
@@ -26,146 +27,11 @@
 #include <cstdint>
 #include <string>
 
-#include "mlp_internal.h"
+#include "mlp_tile.h"
 
 using namespace sgrl_mlp_detail;
 
 namespace {
-
-// acc (per owned 32-column tile) = X[32][0 : R) . B, then epi(column, acc) per owned tile, then a barrier (X and the panels free).
-//   BWD false: B[k][n] = W[n * ldw + k]  (a layer forward: W the packed [N][ldw] weight, R = kpad, N = npad, a multiple of 32)
-//   BWD true:  B[k][n] = W[k * ldw + n]  (a layer backward: rows k < R of the packed weight, columns n < N of them; any N)
-// The caller has put a barrier behind its writes of X.  R is a multiple of BK.
-template <int MAXCH, int BK, bool BWD, class Epi>
-__device__ __forceinline__ void tile_gemm(const float* __restrict__ W, int ldw, int R, int N, float* X, float* Ws, int sx, Epi&& epi) {
-  constexpr int SK = BK + 4;                   // forward panel: [CH][SK]
-  constexpr int SB = CH + 4;                   // backward panel: [BK][SB]
-  constexpr int STAGE = CH * SK;
-  static_assert(BK * SB <= STAGE, "the backward panel must fit in a forward stage");
-  constexpr int QPR = BK / 4;
-  constexpr int RPP = 256 / QPR;
-  constexpr int NP = CH / RPP;
-  static_assert(4 * NP == BK, "staging registers");
-  constexpr int KH = BK / 2;
-  constexpr int NQ = KH / 4;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 31, lh = lane >> 5;
-  const int kq = t % QPR, r0 = t / QPR;
-  const int Nt = (N + 31) & ~31;
-  const int nkb = R / BK, nch = (Nt + CH - 1) / CH;
-  f32x16 acc[MAXCH][2];
-#pragma unroll
-  for (int c = 0; c < MAXCH; c++)
-#pragma unroll
-    for (int j = 0; j < 2; j++)
-#pragma unroll
-      for (int e = 0; e < 16; e++) acc[c][j][e] = 0.f;
-  float rw[BK];
-  auto gload = [&](int kb, int c) {
-    if (BWD) {
-      const int col = CH * c + t;
-#pragma unroll
-      for (int i = 0; i < BK; i++) rw[i] = (col < N) ? W[(size_t)(kb * BK + i) * ldw + col] : 0.f;
-    } else {
-#pragma unroll
-      for (int i = 0; i < NP; i++) {
-        const int n = CH * c + r0 + RPP * i;
-        const float4 v = (n < N) ? *reinterpret_cast<const float4*>(W + (size_t)n * ldw + kb * BK + 4 * kq) : make_float4(0.f, 0.f, 0.f, 0.f);
-        rw[4 * i] = v.x; rw[4 * i + 1] = v.y; rw[4 * i + 2] = v.z; rw[4 * i + 3] = v.w;
-      }
-    }
-  };
-  auto sstore = [&](int st) {
-    if (BWD) {
-#pragma unroll
-      for (int i = 0; i < BK; i++) Ws[st * STAGE + i * SB + t] = rw[i];
-    } else {
-#pragma unroll
-      for (int i = 0; i < NP; i++)
-        *reinterpret_cast<float4*>(Ws + st * STAGE + (r0 + RPP * i) * SK + 4 * kq) = make_float4(rw[4 * i], rw[4 * i + 1], rw[4 * i + 2], rw[4 * i + 3]);
-    }
-  };
-  gload(0, 0);
-  sstore(0);
-  __syncthreads();
-  int st = 0;
-  const float* arow = X + li * sx + KH * lh;
-  for (int kb = 0; kb < nkb; kb++) {
-#pragma unroll
-    for (int c = 0; c < MAXCH; c++) {
-      if (c < nch) {
-        int nc = c + 1, nk = kb;
-        if (nc == nch) { nc = 0; nk = kb + 1; }
-        const bool more = nk < nkb;
-        if (more) gload(nk, nc);
-        float4 av[NQ];
-#pragma unroll
-        for (int q = 0; q < NQ; q++) av[q] = *reinterpret_cast<const float4*>(arow + kb * BK + 4 * q);
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-          const int colb = 32 * (wave + 4 * j);
-          if (CH * c + colb < Nt) {           // wave-uniform
-            float4 bv[NQ];
-            if (BWD) {
-              const float* bcol = Ws + st * STAGE + (KH * lh) * SB + colb + li;
-#pragma unroll
-              for (int q = 0; q < NQ; q++) bv[q] = make_float4(bcol[(4 * q) * SB], bcol[(4 * q + 1) * SB], bcol[(4 * q + 2) * SB], bcol[(4 * q + 3) * SB]);
-            } else {
-              const float* brow = Ws + st * STAGE + (colb + li) * SK + KH * lh;
-#pragma unroll
-              for (int q = 0; q < NQ; q++) bv[q] = *reinterpret_cast<const float4*>(brow + 4 * q);
-            }
-#pragma unroll
-            for (int q = 0; q < NQ; q++) {
-              acc[c][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q].x, bv[q].x, acc[c][j], 0, 0, 0);
-              acc[c][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q].y, bv[q].y, acc[c][j], 0, 0, 0);
-              acc[c][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q].z, bv[q].z, acc[c][j], 0, 0, 0);
-              acc[c][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q].w, bv[q].w, acc[c][j], 0, 0, 0);
-            }
-          }
-        }
-        if (more) sstore(st ^ 1);
-        __syncthreads();
-        st ^= 1;
-      }
-    }
-  }
-  // every read of X and of the panels is behind the last barrier
-#pragma unroll
-  for (int c = 0; c < MAXCH; c++)
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-      const int colb = CH * c + 32 * (wave + 4 * j);
-      if (colb >= Nt) continue;
-      epi(colb + li, acc[c][j]);
-    }
-  __syncthreads();
-}
-
-// Every layer of `a` forward over X; hidden layers write relu(. + bias) over X and to A[l] (rows < B); the last layer's
-// accumulators go to last(n, acc, bias_n).
-template <int MAXCH, int BK, class Last>
-__device__ __forceinline__ void fwd_stash(const Net& a, float* const* A, float* X, float* Ws, int sx, int row0, int B, Last&& last) {
-  for (int l = 0; l < a.n_layers; l++) {
-    const int K = a.kpad[l], N = a.npad[l];
-    const float* __restrict__ bias = a.wp + a.b_off[l];
-    const bool is_last = l + 1 == a.n_layers;
-    float* Al = A[l];
-    tile_gemm<MAXCH, BK, false>(a.wp + a.w_off[l], K, K, N, X, Ws, sx, [&](int n, const f32x16& acc) {
-      const float bvv = bias[n];
-      if (!is_last) {
-#pragma unroll
-        for (int e = 0; e < 16; e++) {
-          const int m = tile_row(e);
-          const float v = fmaxf(acc[e] + bvv, 0.f);
-          X[m * sx + n] = v;
-          if (row0 + m < B) Al[(size_t)(row0 + m) * N + n] = v;
-        }
-      } else {
-        last(n, acc, bvv);
-      }
-    });
-  }
-}
 
 // X holds G of the last layer (columns [0, npad[last])): G_l = (G_{l+1} . W_{l+1}) (.) (A_l > 0) for every hidden layer, top down,
 // over X in place; stored to G[l] (rows < B) when `store`.
@@ -230,7 +96,7 @@ __global__ __launch_bounds__(256) void k_mlp_critic_fb(CriticFbArgs a) {
     const int last = net.n_layers - 1;
     float* Glast = a.G[s][last];
     const int NLp = net.npad[last];
-    fwd_stash<MAXCH, BK>(net, a.A[s], X, Ws, sx, row0, B, [&](int n, const f32x16& acc, float bvv) {
+    mlp_walk<MAXCH, BK>(net, a.A[s], X, Ws, sx, row0, B, [&](int n, const f32x16& acc, float bvv) {
       float part = 0.f;
 #pragma unroll
       for (int e = 0; e < 16; e++) {
@@ -272,7 +138,7 @@ __global__ __launch_bounds__(256) void k_mlp_actor_fb(ActorFbArgs a) {
   extern __shared__ __attribute__((aligned(16))) float mlp_train_lds[];
   float* X = mlp_train_lds;
   float* Ws = mlp_train_lds + BM * a.sx;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 31, lh = lane >> 5;
+  const int lh = (threadIdx.x & 63) >> 5;
   const int row0 = blockIdx.x * BM, B = a.n_env, sx = a.sx;
   float* abuf = a.abuf;                        // stored and re-read by the same lanes: not restrict
   float* T = a.T;
@@ -281,7 +147,7 @@ __global__ __launch_bounds__(256) void k_mlp_actor_fb(ActorFbArgs a) {
   load_rows(X, sx, 0, a.in_dim, a.actor.kpad[0], a.obs, a.obs_ld, row0, B);
   __syncthreads();
   stash_input(X, sx, a.actor.kpad[0], a.X0, row0, B);
-  fwd_stash<MAXCH, BK>(a.actor, a.A, X, Ws, sx, row0, B, [&](int n, const f32x16& acc, float bvv) {
+  mlp_walk<MAXCH, BK>(a.actor, a.A, X, Ws, sx, row0, B, [&](int n, const f32x16& acc, float bvv) {
     if (n < a.out_dim) {
 #pragma unroll
       for (int e = 0; e < 16; e++) {
@@ -294,24 +160,10 @@ __global__ __launch_bounds__(256) void k_mlp_actor_fb(ActorFbArgs a) {
       }
     }
   });
-  // Q1's input tile: observation columns from global again, zeros behind the action columns up to the padded width, the action
-  // columns by the lanes that stored them (the mapping of the actor's last layer)
-  load_rows(X, sx, 0, a.in_dim, a.in_dim, a.obs, a.obs_ld, row0, B);
-  load_rows(X, sx, a.in_dim + a.out_dim, 0, a.c1.kpad[0] - a.in_dim - a.out_dim, a.obs, 0, row0, B);
-#pragma unroll
-  for (int c = 0; c < MAXCH; c++)
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-      const int n = CH * c + 32 * (wave + 4 * j) + li;
-      if (CH * c + 32 * (wave + 4 * j) >= NA || n >= a.out_dim) continue;
-#pragma unroll
-      for (int e = 0; e < 16; e++) {
-        const int m = tile_row(e);
-        X[m * sx + a.in_dim + n] = (row0 + m < B) ? abuf[(size_t)(row0 + m) * a.abuf_ld + n] : 0.f;
-      }
-    }
+  // Q1's input tile, the action columns re-read by the lanes that stored them
+  load_obs_stored_actions<MAXCH>(X, sx, a.obs, a.obs_ld, a.in_dim, abuf, a.abuf_ld, a.out_dim, NA, a.c1.kpad[0], row0, B);
   __syncthreads();
-  fwd_stash<MAXCH, BK>(a.c1, a.Ac, X, Ws, sx, row0, B, [&](int n, const f32x16& acc, float bvv) {
+  mlp_walk<MAXCH, BK>(a.c1, a.Ac, X, Ws, sx, row0, B, [&](int n, const f32x16& acc, float bvv) {
     float part = 0.f;
 #pragma unroll
     for (int e = 0; e < 16; e++) {
@@ -410,10 +262,8 @@ __global__ __launch_bounds__(256) void k_mlp_wgrad(WgArgs a) {
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
-struct TrainPlan { int maxch, bk, lds, sx; };
-
 // pa may be null (the critic step walks the critic alone)
-int make_train_plan(const Plan* pa, const Plan& pc, TrainPlan* tp, const char* who) {
+int make_train_plan(const Plan* pa, const Plan& pc, TilePlan* tp, const char* who) {
   int wmax = 0, nmax = 0;
   for (int k = 0; k < 2; k++) {
     const Plan* p = k ? &pc : pa;
@@ -427,11 +277,7 @@ int make_train_plan(const Plan* pa, const Plan& pc, TrainPlan* tp, const char* w
   if (nmax > SGRL_MLP_TRAIN_MAX_WIDTH)
     return mfail(SGRL_ERR_ARG, std::string(who) + ": the gradient half serves layer widths up to " + std::to_string(SGRL_MLP_TRAIN_MAX_WIDTH) +
                                    " (padded), got " + std::to_string(nmax) + ": keep the PyTorch gradient half for these networks");
-  tp->maxch = nmax <= CH ? 1 : 2;
-  tp->sx = wmax + 4;
-  auto lds_for = [&](int bk) { return (int)sizeof(float) * (BM * tp->sx + 2 * CH * (bk + 4)); };
-  tp->bk = lds_for(16) <= LDS_LIMIT ? 16 : 8;
-  tp->lds = lds_for(tp->bk);
+  *tp = tile_plan(nmax <= CH ? 1 : 2, wmax + 4);
   if (tp->lds > LDS_LIMIT) return mfail(SGRL_ERR_LIMIT, std::string(who) + ": the activation tile does not fit in LDS");
   return SGRL_OK;
 }
@@ -464,34 +310,15 @@ WsLayout ws_layout(const Plan& p, int stacks, int B) {
   return w;
 }
 
+// the handle's training workspace holds at least `need` floats
 int ensure_tws(sgrl_mlp* s, int64_t need, bool capturing, const char* who) {
   if (need <= s->tws_floats) return SGRL_OK;
-  if (capturing)
-    return mfail(SGRL_ERR_ARG, std::string(who) + ": the workspace must grow, which a capture cannot record: run this batch size eagerly first");
-  float* buf = nullptr;
-  if (hipMalloc(&buf, sizeof(float) * (size_t)need) != hipSuccess) return mfail(SGRL_ERR_HIP, "device allocation failed (MLP training workspace)");
-  if (s->tws) {
-    (void)hipDeviceSynchronize();           // a step in flight may still use the old workspace
-    (void)hipFree(s->tws);
-    s->generation++;
-  }
-  s->tws = buf;
-  s->tws_floats = need;
-  return SGRL_OK;
+  return grow(&s->tws, &s->tws_floats, need, capturing, &s->generation, who, "training workspace");
 }
 
 typedef void (*critic_fb_fn)(CriticFbArgs);
 typedef void (*actor_fb_fn)(ActorFbArgs);
 #define SGRL_MLP_TRAIN_PICK(K, maxch, bk) ((bk) == 16 ? ((maxch) == 1 ? K<1, 16> : K<2, 16>) : ((maxch) == 1 ? K<1, 8> : K<2, 8>))
-int g_train_lds[2][4] = {{0}};
-int raise_train_lds(const void* fn, int family, const TrainPlan& tp, const char* who) {
-  int& raised = g_train_lds[family][(tp.bk == 16 ? 0 : 2) + tp.maxch - 1];
-  if (raised >= tp.lds) return SGRL_OK;
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, tp.lds) != hipSuccess)
-    return mfail(SGRL_ERR_HIP, std::string(who) + ": cannot raise the kernel's dynamic LDS limit");
-  raised = tp.lds;
-  return SGRL_OK;
-}
 
 // the weight-gradient entries of `stacks` stacks of a handle, appended to wa
 void add_wgrad_entries(WgArgs* wa, const sgrl_mlp* s, int stacks, const WsLayout& w, int* tile0) {
@@ -513,18 +340,6 @@ void add_wgrad_entries(WgArgs* wa, const sgrl_mlp* s, int stacks, const WsLayout
     }
 }
 
-bool is_capturing(hipStream_t st) {
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(st, &cap);
-  return cap != hipStreamCaptureStatusNone;
-}
-
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return mfail(SGRL_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
-  return SGRL_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -536,20 +351,13 @@ int sgrl_mlp_train_plan(const int32_t* actor_dims, int n_a, const int32_t* criti
                         int64_t* ws_floats) {
   if (!info || !ws_floats) return mfail(SGRL_ERR_ARG, "sgrl_mlp_train_plan: null argument");
   Plan pa, pc;
-  int rc = make_plan(actor_dims, n_a, &pa, "sgrl_mlp_train_plan (actor)");
+  int rc = make_pair_plans(actor_dims, n_a, critic_dims, n_c, &pa, &pc, "sgrl_mlp_train_plan");
   if (rc != SGRL_OK) return rc;
-  rc = make_plan(critic_dims, n_c, &pc, "sgrl_mlp_train_plan (critic)");
-  if (rc != SGRL_OK) return rc;
-  if (pc.dims[pc.n_layers] != 1)
-    return mfail(SGRL_ERR_ARG, "sgrl_mlp_train_plan: a critic's last width must be 1, got " + std::to_string(pc.dims[pc.n_layers]));
-  if (pc.dims[0] != pa.dims[0] + pa.dims[pa.n_layers])
-    return mfail(SGRL_ERR_ARG, "sgrl_mlp_train_plan: the critic reads " + std::to_string(pc.dims[0]) + " values, not the actor's input + output width " +
-                                   std::to_string(pa.dims[0] + pa.dims[pa.n_layers]));
   if (batch < 1 || batch > (1 << 24)) return mfail(SGRL_ERR_ARG, "sgrl_mlp_train_plan: batch outside 1 .. 2^24");
-  TrainPlan tp;
+  TilePlan tp;
   rc = make_train_plan(&pa, pc, &tp, "sgrl_mlp_train_plan");
   if (rc != SGRL_OK) return rc;
-  info[0] = tp.maxch; info[1] = tp.bk; info[2] = tp.lds; info[3] = tp.sx;
+  put_tile_plan(tp, info);
   info[4] = wgrad_tiles(pc, 2);
   info[5] = wgrad_tiles(pa, 1);
   info[6] = (batch + BM - 1) / BM;
@@ -561,13 +369,12 @@ int sgrl_mlp_train_plan(const int32_t* actor_dims, int n_a, const int32_t* criti
 int sgrl_mlp_bind_grads(sgrl_mlp* s, const void* const* ptrs, int n_ptrs) {
   if (!s || !ptrs) return mfail(SGRL_ERR_ARG, "sgrl_mlp_bind_grads: null argument");
   if (s->kind == SGRL_MLP_KIND_NONE) return mfail(SGRL_ERR_ARG, "sgrl_mlp_bind_grads: parameters not set (sgrl_mlp_set_params / sgrl_mlp_set_critic_params)");
-  const int stacks = s->kind == SGRL_MLP_KIND_CRITIC ? 2 : 1;
+  const int stacks = n_stacks(s);
   const int nl = s->plan.n_layers;
   if (n_ptrs != 2 * stacks * nl)
     return mfail(SGRL_ERR_ARG, "sgrl_mlp_bind_grads: expected " + std::to_string(2 * stacks * nl) + " gradient addresses, got " + std::to_string(n_ptrs));
-  for (int i = 0; i < n_ptrs; i++)
-    if (!ptrs[i] || (reinterpret_cast<uintptr_t>(ptrs[i]) & 3))
-      return mfail(SGRL_ERR_ARG, "sgrl_mlp_bind_grads: gradient " + std::to_string(i) + " is null or not 4-byte aligned");
+  const int rc = check_addresses(ptrs, n_ptrs, "sgrl_mlp_bind_grads", "gradient");
+  if (rc != SGRL_OK) return rc;
   for (int k = 0; k < stacks; k++)
     for (int l = 0; l < nl; l++) {
       s->gw[k][l] = static_cast<float*>(const_cast<void*>(ptrs[2 * (k * nl + l)]));
@@ -587,7 +394,7 @@ int sgrl_mlp_critic_step_grads(sgrl_mlp* s, const float* obs, int obs_ld, const 
   if (obs_ld < s->obs_w || act_ld < s->act_w)
     return mfail(SGRL_ERR_ARG, std::string(who) + ": obs_ld or act_ld below the columns the critic reads (rows too narrow for the network)");
   const Plan& p = s->plan;
-  TrainPlan tp;
+  TilePlan tp;
   int rc = make_train_plan(nullptr, p, &tp, who);
   if (rc != SGRL_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -596,7 +403,7 @@ int sgrl_mlp_critic_step_grads(sgrl_mlp* s, const float* obs, int obs_ld, const 
   rc = ensure_tws(s, w.total, is_capturing(st), who);
   if (rc != SGRL_OK) return rc;
   critic_fb_fn fn = SGRL_MLP_TRAIN_PICK(k_mlp_critic_fb, tp.maxch, tp.bk);
-  rc = raise_train_lds(reinterpret_cast<const void*>(fn), 0, tp, who);
+  rc = raise_lds(reinterpret_cast<const void*>(fn), tp.lds, who);
   if (rc != SGRL_OK) return rc;
   rc = pack_now(s, st);
   if (rc != SGRL_OK) return rc;
@@ -629,23 +436,16 @@ int sgrl_mlp_actor_step_grads(sgrl_mlp* actor, sgrl_mlp* critic, const float* ob
                               float* action_out, int action_ld, void* stream) {
   const char* who = "sgrl_mlp_actor_step_grads";
   if (!actor || !critic || !obs || !loss_out) return mfail(SGRL_ERR_ARG, std::string(who) + ": null argument");
-  if (actor->kind != SGRL_MLP_KIND_ACTOR) return mfail(SGRL_ERR_ARG, std::string(who) + ": the first handle is not bound as an actor");
-  if (critic->kind != SGRL_MLP_KIND_CRITIC) return mfail(SGRL_ERR_ARG, std::string(who) + ": the second handle is not bound as a critic");
-  if (actor->n_env <= 0 || critic->n_env <= 0) return mfail(SGRL_ERR_ARG, std::string(who) + ": batch structure not set");
-  if (actor->n_env != critic->n_env)
-    return mfail(SGRL_ERR_ARG, std::string(who) + ": actor and critic are configured for different batch structures (" + std::to_string(actor->n_env) +
-                                   " / " + std::to_string(critic->n_env) + " environments)");
+  int rc = check_pair(actor, critic, who);
+  if (rc != SGRL_OK) return rc;
   if (!actor->grads_bound) return mfail(SGRL_ERR_ARG, std::string(who) + ": gradients not bound (sgrl_mlp_bind_grads on the actor)");
   const Plan& pa = actor->plan;
   const Plan& pc = critic->plan;
   const int in_dim = pa.dims[0], out_dim = pa.dims[pa.n_layers], B = actor->n_env;
-  if (pc.dims[0] != in_dim + out_dim || critic->obs_w != in_dim || critic->act_w != out_dim)
-    return mfail(SGRL_ERR_ARG, std::string(who) + ": the critic reads " + std::to_string(pc.dims[0]) + " values, not the actor's input + output width " +
-                                   std::to_string(in_dim + out_dim));
   if (obs_ld < in_dim || (action_out && action_ld < out_dim))
     return mfail(SGRL_ERR_ARG, std::string(who) + ": obs_ld or action_ld below the network's width (rows too narrow for the network)");
-  TrainPlan tp;
-  int rc = make_train_plan(&pa, pc, &tp, who);
+  TilePlan tp;
+  rc = make_train_plan(&pa, pc, &tp, who);
   if (rc != SGRL_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bool capturing = is_capturing(st);
@@ -656,7 +456,7 @@ int sgrl_mlp_actor_step_grads(sgrl_mlp* actor, sgrl_mlp* critic, const float* ob
   rc = ensure_tws(critic, wc.total, capturing, who);
   if (rc != SGRL_OK) return rc;
   actor_fb_fn fn = SGRL_MLP_TRAIN_PICK(k_mlp_actor_fb, tp.maxch, tp.bk);
-  rc = raise_train_lds(reinterpret_cast<const void*>(fn), 1, tp, who);
+  rc = raise_lds(reinterpret_cast<const void*>(fn), tp.lds, who);
   if (rc != SGRL_OK) return rc;
   rc = pack_now(actor, st);
   if (rc != SGRL_OK) return rc;

@@ -359,6 +359,15 @@ class HipMlpCritic(_HipMlpHandle):
         return self.forward_q(state.contiguous().float(), action.contiguous().float(), twin=twin)
 
 
+def _action_out_arg(action_out, n_env, width):
+    """(address, leading dimension) of an optional `action_out` [n_env, >= width]; a null address and 0 for None."""
+    if action_out is None:
+        return ctypes.c_void_p(None), 0
+    assert action_out.is_cuda and action_out.dtype == torch.float32 and action_out.is_contiguous() and action_out.dim() == 2
+    assert action_out.shape[0] == n_env and action_out.shape[1] >= width, "action_out rows narrower than the actor's output"
+    return ctypes.c_void_p(action_out.data_ptr()), int(action_out.shape[1])
+
+
 class HipMlpTargets(object):
     """The no-grad half of a TD3 update of an MLP agent (reference src/agent.py:126-148) on the HIP path: the handles of the target
     actor (`MlpPolicy`) and the twin target critic (`MlpCritic`), and `target_q` over sgrl_mlp_td_target -- ONE launch (plus one pack
@@ -409,11 +418,7 @@ class HipMlpTargets(object):
             out = torch.empty((a.n_env, 1), dtype=torch.float32, device=self.device)
         assert out.is_contiguous() and out.shape == (a.n_env, 1) and out.dtype == torch.float32
         vp, cf = ctypes.c_void_p, ctypes.c_float
-        act_ptr, act_ld = vp(None), 0
-        if action_out is not None:
-            assert action_out.is_cuda and action_out.dtype == torch.float32 and action_out.is_contiguous() and action_out.dim() == 2
-            assert action_out.shape[0] == a.n_env and action_out.shape[1] >= a.dims[-1], "action_out rows narrower than the actor's output"
-            act_ptr, act_ld = vp(action_out.data_ptr()), int(action_out.shape[1])
+        act_ptr, act_ld = _action_out_arg(action_out, a.n_env, a.dims[-1])
         stream = vp(torch.cuda.current_stream(self.device).cuda_stream)
         _check(self.L, self.L.sgrl_mlp_td_target(a.h, c.h, vp(next_obs.data_ptr()), a._ld(next_obs), vp(noise.data_ptr()), a._ld(noise),
                                                  vp(reward.data_ptr()), vp(done.data_ptr()), cf(float(a.policy.max_action)),
@@ -502,11 +507,7 @@ class HipMlpGrads(object):
         c.sync_weights()
         a.check_rows(obs, a.dims[0], "observation")
         vp = ctypes.c_void_p
-        act_ptr, act_ld = vp(None), 0
-        if action_out is not None:
-            assert action_out.is_cuda and action_out.dtype == torch.float32 and action_out.is_contiguous() and action_out.dim() == 2
-            assert action_out.shape[0] == a.n_env and action_out.shape[1] >= a.dims[-1], "action_out rows narrower than the actor's output"
-            act_ptr, act_ld = vp(action_out.data_ptr()), int(action_out.shape[1])
+        act_ptr, act_ld = _action_out_arg(action_out, a.n_env, a.dims[-1])
         loss = self._loss[1]
         stream = vp(torch.cuda.current_stream(self.device).cuda_stream)
         _check(self.L, self.L.sgrl_mlp_actor_step_grads(a.h, c.h, vp(obs.data_ptr()), a._ld(obs), ctypes.c_float(float(a.policy.max_action)),

@@ -6,7 +6,8 @@ td3.Agent(mlp_hip_grads=True)) on the MI355X.
    test_mlp_policy.py; g_torch32 = float32 PyTorch autograd on the same inputs), losses 1e-4 relative (+ 2e-6 for the actor's)
 2  tests/golden/td3_update_mlp.npz (the executed reference's Agent.update) through a CUDA agent on the new path, the assertions
    and tolerances of test_mlp_policy.test_update_matches_the_reference_on_cpu
-3  repeatability: bit-identical gradients and losses from the same state
+3  repeatability: bit-identical gradients and losses from the same state; the same action bits from the forward, the gradient half
+   and the target chain (one panel product under all three)
 4  .grad handling: None, replaced, garbage, the critic's after an actor step
 5  argument errors before any launch
 6  DeviceTrainer with the path on; twenty updates against the PyTorch gradient half
@@ -269,6 +270,32 @@ def test_repeatable_bit_for_bit():
         for x, y in zip(runs[0][k], runs[1][k]):
             assert torch.equal(x, y)
     assert all(float(g.abs().max()) > 0 for g in runs[0][2][:2])
+
+
+@pytest.mark.parametrize("hidden", [(256, 256), (40, 72), (512, 500)], ids=lambda h: "x".join(str(x) for x in h))
+@pytest.mark.parametrize("L", (3, 7))
+def test_the_three_actor_walks_give_the_same_bits(L, hidden):
+    """The forward, the gradient half and the target chain walk the actor with one panel product: the same action bits from all
+    three (the chain with zero noise; max_action is 1, so its clamp changes nothing).  The pairing of k values inside a matrix
+    instruction depends on the panel depth, so the three plans must have chosen the same `bk` (16 at these widths) first."""
+    from sgrl_amd import mlp_hip
+    pol, crit = _pair(L, hidden, seed=41)
+    n = 33
+    b = _batch(L, n, seed=33)
+    grads = mlp_hip.HipMlpGrads(pol, crit)
+    targets = mlp_hip.HipMlpTargets(pol, crit)
+    bks = (mlp_hip.plan(targets.actor.dims)["bk"], targets.plan()["bk"], grads.plan(n)["bk"])
+    assert bks == (16, 16, 16), bks
+    g = _graph(L)
+    targets.configure([g], [n])
+    forward = targets.actor.forward_batch(b["obs"])
+    from_grads = torch.full((n, 3 * L), 7.0, device="cuda:0")
+    grads.actor_step(b["obs"], action_out=from_grads)
+    from_chain = torch.full((n, 3 * L), 7.0, device="cuda:0")
+    zeros = torch.zeros((n, 3 * L), device="cuda:0")
+    targets.target_q(b["obs"], zeros, b["target"], torch.zeros((n, 1), device="cuda:0"), g, 0.5, 0.99, action_out=from_chain)
+    assert float(forward.abs().max()) > 0
+    assert torch.equal(forward, from_grads) and torch.equal(forward, from_chain)
 
 
 def test_grad_tensors_none_replaced_garbage_and_stale():
