@@ -215,6 +215,21 @@ int sgrl_mlp_optim_step(sgrl_mlp* s, double lr, double beta1, double beta2, doub
 
 int sgrl_mlp_optim_step_launches(void); /* 2 */
 
+/* ---- batch prologue of the TD3 update ------------------------------------------------------------------------------------------
+ * Replaces the reward scaling `reward_batch = reward_batch * self.reward_scale` (reference src/agent.py:124) and the two statistics
+ * `torch.mean(reward_batch)`, `torch.var(reward_batch)` of "misc/train_reward_mean" / "misc/train_reward_var" (agent.py:160-161):
+ *   reward_out[i] = reward[i] * reward_scale        one float32 product: the bits of `tensor * python_float` in torch
+ *   stats[0]      = (sum of reward_out) / n
+ *   stats[1]      = (sum of (reward_out[i] - stats[0])^2) / (n - 1)        two passes, unbiased, as torch.var; n = 1: NaN
+ * reward: DEV float [n]; reward_out: DEV float [n], may BE reward (in place); stats: DEV float [2]; n in 1 .. 2^24.  ONE launch of
+ * ONE workgroup of 256 threads.  ORDER OF THE SUMS, fixed (a call is bit-repeatable; no atomics, no scratch): thread t adds elements
+ * t, t + 256, ... serially, a wave adds its lanes by a butterfly (xor 32 .. 1), the four waves are added in order -- the order of the
+ * optimizer half's total.  No operation is fused: every product, sum and quotient rounds once to float32.  Asynchronous on `stream`,
+ * allocates nothing, and can be recorded into a hipGraph.  SGRL_ERR_ARG BEFORE ANY LAUNCH, nothing written, for a null or unaligned
+ * pointer, n out of range, a scale that is not finite. */
+int sgrl_mlp_batch_stats(const float* reward, int n, float reward_scale, float* reward_out, float* stats /* [2] */, void* stream);
+int sgrl_mlp_batch_stats_launches(void); /* 1 */
+
 #ifdef __cplusplus
 }
 #endif

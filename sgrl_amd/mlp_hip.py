@@ -11,7 +11,8 @@ every device entry point raises `_lib.SgrlError`; `plan` and `chain_plan` alone 
 
 `HipMlpCritic` binds the two Q stacks of an `MlpCritic` the same way (one packed buffer, one pack launch); `HipMlpTargets` runs the
 no-grad half of a TD3 update (target actor -> clipped noise -> clamp -> twin target critics -> min -> Bellman target) as ONE launch
-of the fused chain kernel over the two handles."""
+of the fused chain kernel over the two handles.  `batch_stats` is the update's prologue (csrc/mlp_batch.hip: the scaled reward and its
+two statistics, one launch); with it td3.GraphedMlpUpdates records a whole update as a chain of this file's launches."""
 import ctypes
 
 import numpy as np
@@ -66,8 +67,10 @@ def _bind(L):
     L.sgrl_mlp_optim_bound.restype = ci
     L.sgrl_mlp_optim_step.argtypes = [vp, cd, cd, cd, cd, cf, cf, vp]
     L.sgrl_mlp_optim_step.restype = ci
+    L.sgrl_mlp_batch_stats.argtypes = [vp, ci, cf, vp, vp, vp]
+    L.sgrl_mlp_batch_stats.restype = ci
     for name in ("sgrl_mlp_forward_launches", "sgrl_mlp_pack_launches", "sgrl_mlp_td_target_launches", "sgrl_mlp_critic_forward_launches",
-                 "sgrl_mlp_critic_step_launches", "sgrl_mlp_actor_step_launches", "sgrl_mlp_optim_step_launches"):
+                 "sgrl_mlp_critic_step_launches", "sgrl_mlp_actor_step_launches", "sgrl_mlp_optim_step_launches", "sgrl_mlp_batch_stats_launches"):
         getattr(L, name).argtypes = []
         getattr(L, name).restype = ci
     L.sgrl_mlp_num_envs.argtypes = [vp]
@@ -480,9 +483,17 @@ class HipMlpGrads(object):
         self.actor.configure(g, [n])
         self.critic.configure(g, [n])
 
-    def critic_step(self, obs, action, target_q):
+    def _loss_arg(self, k, loss_out):
+        """Where step k (0 critic, 1 actor) writes its loss: this object's own element, or the caller's 0-d / 1-element tensor."""
+        if loss_out is None:
+            return self._loss[k]
+        assert loss_out.is_cuda and loss_out.dtype == torch.float32 and loss_out.numel() == 1 and loss_out.device == self.device, "loss_out"
+        return loss_out
+
+    def critic_step(self, obs, action, target_q, loss_out=None):
         """mse(Q1(obs, action), target_q) + mse(Q2(obs, action), target_q) -> 0-d device tensor; its gradient in every critic
-        parameter's `.grad`.  obs [B, >= 41 L], action [B, >= 3 L], target_q [B] or [B, 1]: float32 CUDA."""
+        parameter's `.grad`.  obs [B, >= 41 L], action [B, >= 3 L], target_q [B] or [B, 1]: float32 CUDA.  loss_out: a caller-owned
+        0-d or 1-element float32 device tensor that receives (and is returned as) the loss instead of this object's own."""
         c = self.critic
         self._configure(obs.shape[0])
         params = self._bind_grads(c)
@@ -491,16 +502,16 @@ class HipMlpGrads(object):
         target_q = target_q.reshape(-1).contiguous()
         assert target_q.is_cuda and target_q.dtype == torch.float32 and target_q.shape[0] == c.n_env
         vp = ctypes.c_void_p
-        loss = self._loss[0]
+        loss = self._loss_arg(0, loss_out)
         stream = vp(torch.cuda.current_stream(self.device).cuda_stream)
         _check(self.L, self.L.sgrl_mlp_critic_step_grads(c.h, vp(obs.data_ptr()), c._ld(obs), vp(action.data_ptr()), c._ld(action),
                                                          vp(target_q.data_ptr()), vp(loss.data_ptr()), stream), "sgrl_mlp_critic_step_grads")
         torch.autograd.graph.increment_version([p.grad for p in params])
         return loss
 
-    def actor_step(self, obs, action_out=None):
+    def actor_step(self, obs, action_out=None, loss_out=None):
         """-mean(Q1(obs, actor(obs))) -> 0-d device tensor; its gradient in every ACTOR parameter's `.grad` (the critic's are left as
-        they are, see the class).  action_out: float32 [B, >= 3 L] contiguous, receives actor(obs)."""
+        they are, see the class).  action_out: float32 [B, >= 3 L] contiguous, receives actor(obs).  loss_out: as on critic_step."""
         a, c = self.actor, self.critic
         self._configure(obs.shape[0])
         params = self._bind_grads(a)
@@ -508,12 +519,18 @@ class HipMlpGrads(object):
         a.check_rows(obs, a.dims[0], "observation")
         vp = ctypes.c_void_p
         act_ptr, act_ld = _action_out_arg(action_out, a.n_env, a.dims[-1])
-        loss = self._loss[1]
+        loss = self._loss_arg(1, loss_out)
         stream = vp(torch.cuda.current_stream(self.device).cuda_stream)
         _check(self.L, self.L.sgrl_mlp_actor_step_grads(a.h, c.h, vp(obs.data_ptr()), a._ld(obs), ctypes.c_float(float(a.policy.max_action)),
                                                         vp(loss.data_ptr()), act_ptr, act_ld, stream), "sgrl_mlp_actor_step_grads")
         torch.autograd.graph.increment_version([p.grad for p in params])
         return loss
+
+    def replayed(self, critic=True, actor=False):
+        """A critic_step (and, with actor, an actor_step) ran inside a hipGraph replay, which runs no host code: bump the versions of
+        the `.grad` tensors those kernels wrote, as the eager steps do after their launches."""
+        wrote = [p.grad for on, h in ((critic, self.critic), (actor, self.actor)) if on for p in h._params() if p.grad is not None]
+        torch.autograd.graph.increment_version(wrote)
 
 
 class _OptimSide(object):
@@ -525,6 +542,7 @@ class _OptimSide(object):
         self.partials = None
         self.counter = None          # plain groups: the device step counter this object owns
         self.host_step = None        # plain groups: the count `counter` holds
+        self.clipped = False         # whether the last step clipped (wrote .grad)
 
 
 class HipMlpOptim(object):
@@ -583,6 +601,74 @@ class HipMlpOptim(object):
     def actor_step(self, max_norm, tau=0.0):
         self._step(self._actor, max_norm, tau)
 
+    def replayed(self, critic=True, actor=False, tau=None):
+        """The host half of `_step` for steps that ran inside a hipGraph replay (which runs no host code): for every side named, advance
+        the host-side counts -- the `_sgrl_step_class` mirrors of capturable groups; the CPU `st["step"]` tensors and this object's
+        `host_step` of plain groups -- by one, and bump the version of everything the step wrote: the parameters, `.grad` when the
+        step clipped (as the side's last eager or recorded step did), both moment tensors, the device counters, and the targets when it
+        carried tau > 0.  tau=None: the update's rule -- the critic step carries tau > 0 exactly on policy iterations (actor=True), the
+        actor step always.  Covers the gradient half too (HipMlpGrads.replayed)."""
+        self.grads.replayed(critic=critic, actor=actor)
+        for side in self._sides(critic, actor):
+            params = side.h._params()
+            states = [side.opt.state[p] for p in params]
+            on_device = states[0]["step"].is_cuda
+            if on_device:
+                host = side.opt.__dict__.setdefault("_sgrl_step_class", {})
+                for p in params:
+                    host[id(p)] += 1
+            else:
+                for st in states:
+                    st["step"] += 1
+                side.host_step += 1
+            wrote = list(params) + [st["exp_avg"] for st in states] + [st["exp_avg_sq"] for st in states]
+            if side.clipped:
+                wrote += [p.grad for p in params]
+            wrote += [st["step"] for st in states] if on_device else [side.counter]
+            with_tau = bool(actor) if tau is None else float(tau) > 0
+            if with_tau and side.target_nets is not None:
+                wrote += [p for net in side.target_nets for l in linears(net) for p in (l.weight, l.bias)]
+            torch.autograd.graph.increment_version(wrote)
+
+    def _sides(self, critic, actor):
+        return [side for on, side in ((critic, self._critic), (actor, self._actor)) if on]
+
+    def counts_current(self, critic=True, actor=False):
+        """Whether a step of the sides named would need NO host-to-device traffic for its step count -- what a recorded step relies
+        on: every parameter has state; capturable groups: the host mirror knows every parameter; plain groups: this object's device
+        counter holds the state's CPU count (nobody else has stepped the optimizer since).  Host only."""
+        for side in self._sides(critic, actor):
+            params = side.h._params()
+            states = [side.opt.state.get(p) for p in params]
+            if any(not st for st in states):
+                return False
+            if states[0]["step"].is_cuda:
+                host = side.opt.__dict__.get("_sgrl_step_class", {})
+                if any(id(p) not in host for p in params):
+                    return False
+            elif side.counter is None or any(float(st["step"]) != side.host_step for st in states):
+                return False
+        return True
+
+    def host_counts(self):
+        """The host-side step counts of both sides, for set_host_counts: a capture runs the host half of its steps, not their kernels."""
+        out = []
+        for side in (self._critic, self._actor):
+            states = [side.opt.state.get(p) for p in side.h._params()]
+            host = side.opt.__dict__.get("_sgrl_step_class")
+            out.append((side.host_step, None if host is None else dict(host),
+                        [float(st["step"]) if st and not st["step"].is_cuda else None for st in states]))
+        return out
+
+    def set_host_counts(self, counts):
+        for side, (host_step, host, cpu) in zip((self._critic, self._actor), counts):
+            side.host_step = host_step
+            if host is not None:
+                side.opt.__dict__["_sgrl_step_class"] = host
+            for p, c in zip(side.h._params(), cpu):
+                if c is not None:
+                    side.opt.state[p]["step"].fill_(c)
+
     def _state(self, side, params):
         """opt.state[p] of every parameter, created where empty; -> (states, True when the counters live on the device)."""
         opt = side.opt
@@ -632,6 +718,7 @@ class HipMlpOptim(object):
         group = opt.param_groups[0]
         beta1, beta2 = group["betas"]
         clip = float(max_norm) if (max_norm and max_norm > 0) else 0.0
+        side.clipped = clip > 0
         cdbl, cf = ctypes.c_double, ctypes.c_float
         stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         _check(self.L, self.L.sgrl_mlp_optim_step(h.h, cdbl(float(group["lr"])), cdbl(float(beta1)), cdbl(float(beta2)), cdbl(float(group["eps"])),
@@ -678,3 +765,29 @@ class HipMlpOptim(object):
         m, v = arr([st["exp_avg"].data_ptr() for st in states]), arr([st["exp_avg_sq"].data_ptr() for st in states])
         _check(self.L, self.L.sgrl_mlp_bind_optim(h.h, m, v, n, arr(steps), len(steps), arr([t.data_ptr() for t in targets]), len(targets),
                                                   vp(side.partials.data_ptr()), int(side.partials.numel())), "sgrl_mlp_bind_optim")
+
+
+def batch_stats_launches():
+    L = _lib.lib()
+    _bind(L)
+    return int(L.sgrl_mlp_batch_stats_launches())
+
+
+def batch_stats(reward, scale, out, stats):
+    """The batch prologue of an update (include/sgrl_mlp.h sgrl_mlp_batch_stats; ONE launch): out <- reward * scale (out may be reward
+    itself), stats[0] <- mean(out), stats[1] <- the unbiased variance of out (NaN for one row).  reward, out: float32 CUDA with the
+    same number of elements, contiguous; stats: float32 CUDA, 2 elements.  Asynchronous, allocates nothing.  Returns out."""
+    L = _lib.lib()
+    _bind(L)
+    for t, what in ((reward, "reward"), (out, "out"), (stats, "stats")):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == reward.device):
+            raise _lib.SgrlError("batch_stats: %s must be a contiguous float32 tensor on the reward's GPU" % what)
+    if out.numel() != reward.numel() or stats.numel() != 2:
+        raise _lib.SgrlError("batch_stats: out must have the reward's %d elements and stats 2 (got %d and %d)"
+                             % (reward.numel(), out.numel(), stats.numel()))
+    vp = ctypes.c_void_p
+    stream = vp(torch.cuda.current_stream(reward.device).cuda_stream)
+    _check(L, L.sgrl_mlp_batch_stats(vp(reward.data_ptr()), int(reward.numel()), ctypes.c_float(float(scale)), vp(out.data_ptr()),
+                                     vp(stats.data_ptr()), stream), "sgrl_mlp_batch_stats")
+    torch.autograd.graph.increment_version([out, stats])
+    return out

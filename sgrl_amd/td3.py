@@ -844,3 +844,273 @@ class GraphedUpdates(object):
         _touched(touched)
         # the capture's output tensors are overwritten by the next replay: hand out copies
         return {k: (v.clone() if torch.is_tensor(v) else v) for k, v in sl["out"][flag].items()}
+
+
+def mlp_update_stamp(handles, nets, optimizers, sides, scalars):
+    """Everything a hipGraph of an MLP agent's update has baked -- device addresses and by-value scalars -- as one comparable tuple
+    of PLAIN values (duck-typed: tests/test_mlp_graph_plan.py feeds it stubs).
+      handles     the four mlp_hip handles a replay's kernels were recorded from (target actor, target critic, the gradient half's actor
+                  and critic): `generation()` (bumped whenever the library frees device memory a recorded launch may point into)
+                  and `_bound`, the parameter addresses the library holds
+      nets        per network (target actor, target critic, online actor, online critic) its parameters: where their storage and
+                  their `.grad` are NOW (a moved tensor is bound again by the next eager call, not by a replay)
+      optimizers  per optimizer (actor, critic) `(opt, params)`: the addresses of exp_avg, exp_avg_sq and the step tensor of every
+                  parameter, and lr, betas, eps of the group
+      sides       per optimizer the mlp_hip._OptimSide: its partials and its own device counter (plain groups)
+      scalars     grad_clipping_value, tau, noise_clip, discount, max_action, reward_scale"""
+    ptr = lambda t: None if t is None else int(t.data_ptr())
+    hs = tuple((int(h.generation()), None if h._bound is None else tuple(h._bound)) for h in handles)
+    ps = tuple(tuple((ptr(p), ptr(getattr(p, "grad", None))) for p in params) for params in nets)
+    os_ = []
+    for opt, params in optimizers:
+        g = opt.param_groups[0]
+        st = [opt.state.get(p, {}) for p in params]
+        os_.append((tuple((ptr(s.get("exp_avg")), ptr(s.get("exp_avg_sq")), ptr(s.get("step"))) for s in st),
+                    float(g["lr"]), tuple(float(b) for b in g["betas"]), float(g["eps"])))
+    sd = tuple((ptr(s.partials), ptr(s.counter)) for s in sides)
+    return (hs, ps, tuple(os_), sd, tuple(None if v is None else float(v) for v in scalars))
+
+
+class _EveryKey(object):
+    """`GraphedMlpUpdates.warmed`: the one slot serves every morphology, so every key is warmed once it is."""
+
+    def __init__(self, owner):
+        self._owner = owner
+
+    def __contains__(self, key):
+        return self._owner._warmed
+
+    def __bool__(self):
+        return self._owner._warmed
+
+
+class GraphedMlpUpdates(object):
+    """The TD3 update of an mlp + mlp agent replayed from hipGraphs: the trainer-facing surface of `GraphedUpdates` (`warm`,
+    `warm_from`, `update`, `update_from`, `warmed`, `slots`; fewer rows than B: an eager `agent.update`) over an update that is
+    entirely this library's launches -- mlp_hip.batch_stats -> HipMlpTargets.target_q -> HipMlpGrads.critic_step ->
+    HipMlpOptim.critic_step and, on policy iterations, HipMlpGrads.actor_step -> HipMlpOptim.actor_step: the calls of
+    `Agent._update_hip_grads` in its order with its arguments, so the parameters come out bit-identical to `Agent.update`.  The
+    graph is a plain chain of kernel nodes on ONE stream (`launches(flag)`: 9, or 15 with the policy step): no autograd, no side
+    stream, no allocation, hence no memory pool of its own, and no runtime setting is read or set.
+
+    ONE slot for every morphology (a monolithic network has one limb count): static obs / action / next_obs / reward / done / noise,
+    the scaled reward, the target [B, 1] and the 4-float record {critic_loss, actor_loss, reward_mean, reward_var}; two graphs, with
+    (flag 0) and without (flag 1) the policy step.  `key`, `graph` and `L` are accepted for interface compatibility.
+
+    A graph bakes addresses and by-value scalars: `_stamp()` (mlp_update_stamp) lists them.  `eager_ok[flag]` is the stamp right
+    after the last EAGER run of that kind on the slot; a graph is captured only when it equals the current stamp (the eager run has
+    then bound and grown everything the capture will point at), and a captured graph whose stamp differs from the current one is
+    dropped.  In either case that update runs eagerly on the slot and the capture happens on a later call: no `warm` is needed, the
+    first update of each kind is the eager one.  `stale(flag)` says, launching nothing, whether the next update of that kind would
+    NOT be a replay.  Values are read live: an in-place write into a parameter is seen by the next replay; a changed learning rate
+    is a by-value argument and makes the graphs stale."""
+
+    def __init__(self, agent, batch_size):
+        self.agent, self.B = agent, int(batch_size)
+        atype, ctype = getattr(agent.args, "actor_type", "set"), getattr(agent.args, "critic_type", "set")
+        if atype != "mlp" or ctype != "mlp":
+            raise NotImplementedError("GraphedMlpUpdates serves 'mlp' + 'mlp' agents only (got actor_type %r, critic_type %r): the other "
+                                      "types replay through GraphedUpdates" % (atype, ctype))
+        if agent.device.type != "cuda":
+            raise RuntimeError("GraphedMlpUpdates needs the agent on the GPU")
+        if not agent.use_mlp_hip:
+            raise RuntimeError("GraphedMlpUpdates replays the HIP update of an mlp agent: this one was built with use_hip=False")
+        from . import _lib, mlp_hip
+        self._mlp_hip = mlp_hip
+        try:
+            mlp_hip.train_plan(mlp_hip.net_dims(agent.actor.actor), mlp_hip.net_dims(agent.critic.critic1), self.B)
+        except _lib.SgrlError as e:
+            agent.mlp_hip_grads_refusal = str(e)
+            raise NotImplementedError("GraphedMlpUpdates: the gradient half does not serve these widths: %s" % e)
+        for opt, net in ((agent.actor_optimizer, agent.actor.actor), (agent.critic_optimizer, None)):
+            params = [p for n in ([net] if net is not None else [agent.critic.critic1, agent.critic.critic2])
+                      for l in mlp_hip.linears(n) for p in (l.weight, l.bias)]
+            why = mlp_hip.HipMlpOptim.refusal(opt, params)
+            if why:
+                raise NotImplementedError("GraphedMlpUpdates: the optimizer half does not serve this optimizer: %s" % why)
+        if not 0.0 <= float(agent.target_smoothing_tau) <= 1.0:
+            raise NotImplementedError("GraphedMlpUpdates: target_smoothing_tau outside [0, 1]")
+        agent.use_mlp_hip_grads = agent.use_mlp_hip_optim = True      # the groups stay as they are, plain or capturable
+        self.slots = {}              # one entry, key None: the shared slot
+        self._warmed = False
+        self.warmed = _EveryKey(self)
+        self.eager_ok = {0: None, 1: None}
+        self.replays = 0             # updates served by a graph replay so far
+
+    # ---- the slot -------------------------------------------------------------------------------------
+    def _slot(self):
+        sl = self.slots.get(None)
+        if sl is None:
+            a = self.agent
+            dev, B = a.device, self.B
+            n_in, n_out = self._mlp_hip.net_dims(a.actor.actor)[0], self._mlp_hip.net_dims(a.actor.actor)[-1]
+            z = lambda *sh: torch.zeros(sh, dtype=torch.float32, device=dev)
+            sl = {"batch": {"obs": z(B, n_in), "action": z(B, n_out), "next_obs": z(B, n_in), "reward": z(B, 1), "done": z(B, 1)},
+                  "noise": z(B, n_out), "reward": z(B, 1), "target": z(B, 1), "rec": z(4), "graphs": {}, "stamp": {}}
+            self.slots[None] = sl
+        return sl
+
+    def _load(self, sl, data_batch):
+        for k, t in sl["batch"].items():
+            t.copy_(data_batch[k].reshape(t.shape))
+        sl["noise"].normal_(0, self.agent.args.policy_noise)
+
+    def _load_from(self, sl, buffer, seed, draw):
+        buffer.sample_into(sl["batch"], self.B, seed, draw, noise=sl["noise"], noise_std=self.agent.args.policy_noise)
+
+    def _handles(self, sl):
+        """(HipMlpTargets, HipMlpGrads, HipMlpOptim) of the agent -- its own, so that an eager `agent.update` and this object see the
+        same binds and generations; made on first use as `Agent.update` makes them."""
+        a = self.agent
+        t, g = a._hip_targets(sl["batch"]["next_obs"]), a._hip_grads(sl["batch"])
+        o = a._hip_optim(g) if g is not None else None
+        if t is None or g is None or o is None:
+            raise RuntimeError("GraphedMlpUpdates: the agent no longer takes the HIP update (%s)"
+                               % (getattr(a, "mlp_hip_optim_refusal", None) or getattr(a, "mlp_hip_grads_refusal", None) or "use_mlp_hip* turned off"))
+        return t, g, o
+
+    def launches(self, flag):
+        """Kernel launches (= graph nodes) of an update with (flag 0) or without (flag 1) the policy step, from the ABI's counts: the
+        prologue, the chain with its two packs, the critic's gradient and optimizer steps; then the actor's."""
+        m = self._mlp_hip
+        L = m._lib.lib()
+        m._bind(L)
+        n = L.sgrl_mlp_batch_stats_launches() + 2 * L.sgrl_mlp_pack_launches() + L.sgrl_mlp_td_target_launches() + \
+            L.sgrl_mlp_critic_step_launches() + L.sgrl_mlp_optim_step_launches()
+        if flag == 0:
+            n += L.sgrl_mlp_actor_step_launches() + L.sgrl_mlp_optim_step_launches()
+        return int(n)
+
+    # ---- one update on the slot, eagerly or under capture ---------------------------------------------------
+    def _run(self, sl, hs, policy_it):
+        a, args = self.agent, self.agent.args
+        targets, grads, optim = hs
+        batch, rec = sl["batch"], sl["rec"]
+        tau = a.target_smoothing_tau
+        self._mlp_hip.batch_stats(batch["reward"], a.reward_scale, sl["reward"], rec[2:4])
+        targets.target_q(batch["next_obs"], sl["noise"], sl["reward"], batch["done"], a.actor_target.graph, args.noise_clip, args.discount,
+                         out=sl["target"])
+        grads.critic_step(batch["obs"], batch["action"], sl["target"], loss_out=rec[0])
+        optim.critic_step(args.grad_clipping_value, tau if policy_it else 0.0)
+        if policy_it:
+            grads.actor_step(batch["obs"], loss_out=rec[1])
+            optim.actor_step(args.grad_clipping_value, tau)
+
+    def _stamp(self, hs):
+        a, args = self.agent, self.agent.args
+        targets, grads, optim = hs
+        handles = (targets.actor, targets.critic, grads.actor, grads.critic)
+        return mlp_update_stamp(handles, [h._params() for h in handles],
+                                ((a.actor_optimizer, grads.actor._params()), (a.critic_optimizer, grads.critic._params())),
+                                (optim._actor, optim._critic),
+                                (args.grad_clipping_value, a.target_smoothing_tau, args.noise_clip, args.discount, a.actor_target.max_action,
+                                 a.reward_scale))
+
+    def stale(self, flag):
+        """True when the next update of this kind (0: with the policy step, 1: without) would NOT be a replay: no graph yet, or one
+        whose baked addresses or scalars are no longer the current ones.  Launches nothing."""
+        sl = self.slots.get(None)
+        if sl is None or flag not in sl["graphs"]:
+            return True
+        hs = self._handles(sl)
+        return sl["stamp"][flag] != self._stamp(hs) or not hs[2].counts_current(critic=True, actor=flag == 0)
+
+    def _result(self, sl, policy_it):
+        out = sl["rec"].clone()      # ONE copy: the record is overwritten by the next update
+        d = {"loss/critic_loss": out[0], "misc/train_reward_mean": out[2], "misc/train_reward_var": out[3]}
+        if policy_it:
+            d["loss/actor_loss"] = out[1]
+        return d
+
+    def _eager(self, sl, hs, flag):
+        self._run(sl, hs, flag == 0)
+        self.eager_ok[flag] = self._stamp(hs)
+        self._warmed = True
+        return self._result(sl, flag == 0)
+
+    def _update(self, sl, graph, it):
+        """Everything of an update after the slot's static tensors have been filled."""
+        a = self.agent
+        if graph is not None:
+            a.change_morphology(graph)
+        flag = 0 if it % a.args.policy_freq == 0 else 1
+        hs = self._handles(sl)
+        optim = hs[2]
+        stamp = self._stamp(hs)
+        current = optim.counts_current(critic=True, actor=flag == 0)
+        if flag in sl["graphs"] and (sl["stamp"][flag] != stamp or not current):
+            del sl["graphs"][flag]               # it points at what has moved, or carries a scalar that has changed
+        if flag not in sl["graphs"]:
+            if self.eager_ok[flag] != stamp or not current:
+                return self._eager(sl, hs, flag)     # binds and grows whatever moved; the capture happens on a later call
+            g = torch.cuda.CUDAGraph()
+            counts = optim.host_counts()
+            try:
+                with _no_finalizers_during_capture(), torch.cuda.graph(g):
+                    self._run(sl, hs, flag == 0)
+            except self._mlp_hip._lib.SgrlError:
+                g = None                             # e.g. "must grow": nothing was recorded that will ever run
+            finally:
+                optim.set_host_counts(counts)        # the recorded steps have not run: their host-side counts are taken back
+            if g is None or self._stamp(hs) != stamp:
+                return self._eager(sl, hs, flag)
+            sl["graphs"][flag], sl["stamp"][flag] = g, stamp
+        sl["graphs"][flag].replay()
+        self.replays += 1
+        # a replay runs no host code: the steps' host-side counts and the writes of their kernels are announced here
+        optim.replayed(critic=True, actor=flag == 0)
+        touched = list(a.critic.parameters())
+        if flag == 0:
+            for mod in (a.actor, a.actor_target, a.critic_target):
+                touched.extend(mod.parameters())
+        _touched(touched)
+        return self._result(sl, flag == 0)
+
+    # ---- the surface of GraphedUpdates ----------------------------------------------------------------------
+    def warm(self, key, graph, L, data_batch, iters=3, first_it=0):
+        """`iters` REAL updates run eagerly on the slot (optional here: the first update of each kind is eager anyway).  data_batch
+        may be a callable returning a fresh batch per iteration.  Returns the loss dicts."""
+        return self._warm(graph, lambda sl, n: self._load(sl, data_batch() if callable(data_batch) else data_batch), iters, first_it)
+
+    def warm_from(self, key, graph, L, buffer, seed, draw, iters=3, first_it=0):
+        """`warm` with the slot filled by `buffer.sample_into`: iteration n uses draw number `draw + n`."""
+        if buffer.max_sample_size < self.B:
+            raise RuntimeError("warm_from needs at least %d rows in the buffer" % self.B)
+        return self._warm(graph, lambda sl, n: self._load_from(sl, buffer, seed, draw + n), iters, first_it)
+
+    def _warm(self, graph, load, iters, first_it):
+        sl = self._slot()
+        if graph is not None:
+            self.agent.change_morphology(graph)
+        outs = []
+        for n, it in enumerate(range(first_it, first_it + iters)):
+            load(sl, n)
+            outs.append(self._eager(sl, self._handles(sl), 0 if it % self.agent.args.policy_freq == 0 else 1))
+        return outs
+
+    def update(self, key, graph, L, data_batch, it):
+        """Same contract as Agent.update(data_batch, it, lazy_stats=True)."""
+        if data_batch["obs"].shape[0] != self.B:
+            if graph is not None:
+                self.agent.change_morphology(graph)     # short batch (buffer not yet filled): eager
+            return self.agent.update(data_batch, it)
+        sl = self._slot()
+        self._load(sl, data_batch)
+        return self._update(sl, graph, it)
+
+    def update_from(self, key, graph, L, buffer, it, seed, draw):
+        """`update` with the batch and the noise drawn by ONE `buffer.sample_into(..., seed, draw, noise=...)` into the slot's static
+        tensors, launched before the replay (seed and draw are by-value arguments: not part of the graph)."""
+        if buffer.max_sample_size < self.B:             # short batch (buffer not yet filled): eager, on the k rows there are
+            if graph is not None:
+                self.agent.change_morphology(graph)
+            k, dev = buffer.max_sample_size, self.agent.device
+            sl = self._slot()
+            e = lambda t: torch.empty((k, t.shape[1]), dtype=torch.float32, device=dev)
+            batch = {name: e(t) for name, t in sl["batch"].items()}
+            noise = torch.zeros((k, sl["noise"].shape[1]), dtype=torch.float32, device=dev)
+            buffer.sample_into(batch, k, seed, draw, noise=noise, noise_std=self.agent.args.policy_noise)
+            return self.agent.update(batch, it, noise=noise)
+        sl = self._slot()
+        self._load_from(sl, buffer, seed, draw)
+        return self._update(sl, graph, it)

@@ -25,7 +25,8 @@ class DeviceTrainer(object):
     def __init__(self, env_names, envs_per_morph, args=None, seed=0, device="cuda:0", max_buffer_size=1000000,
                  batch_size=None, dst=0, graph_updates=False, tune_gemms=False, rollout=None, lag_flag=True, device_sampler=False,
                  device_noise=False, **env_kw):
-        """graph_updates: replay the TD3 update from hipGraphs (td3.GraphedUpdates); tune_gemms: let PyTorch's TunableOp pick
+        """graph_updates: replay the TD3 update from hipGraphs (td3.GraphedUpdates; td3.GraphedMlpUpdates
+        for an `mlp` agent); tune_gemms: let PyTorch's TunableOp pick
         the rocBLAS / hipBLASLt algorithm per GEMM shape on first use (the defaults choose 256 x 256 tiles for the 700-row
         weight-gradient GEMMs of a 100-row update: 50 -> 38 ms per update, round 1).  batch_size: rows per TD3 update, default
         args.agent_batch_size = 256 (the reference's trainer.py:289-291).  lag_flag (GPU ranks): the round-finished flag is read one
@@ -52,8 +53,6 @@ class DeviceTrainer(object):
         self.eval_rollouts = {}      # tuple of names -> (settings, Rollout, DeviceEvaluator) of evaluate()
         self.demo_rollouts = {}      # tuple of names -> (settings, Rollout, max_episode_steps) of save_video_demo()
         if getattr(self.args, "actor_type", "set") == "mlp":
-            if graph_updates:
-                raise NotImplementedError("graph_updates is not built for 'mlp' agents: their updates run eagerly")
             if getattr(self.args, "mlp_num_limbs", None) is None and getattr(self.args, "graphs", None) is None:
                 # the reference sizes the network for the LAST training morphology (MLPActor.py:42)
                 from .vec_env import resolve_models
@@ -103,9 +102,14 @@ class DeviceTrainer(object):
         self._eager_slots = {}       # morphology -> (batch tensors, noise) of the eager device-sampled updates
         self.last_losses = {}
         self.graphed = None
+        self._graphed_lazy = False   # td3.GraphedMlpUpdates: needs no warm() before its first update
         if graph_updates and self.is_learner:
-            from .td3 import GraphedUpdates
-            self.graphed = GraphedUpdates(self.agent, self.batch_size)
+            from .td3 import GraphedMlpUpdates, GraphedUpdates
+            # an mlp agent's update is entirely library launches: one shared slot, no warm-up of its own (the first update of each
+            # kind runs eagerly inside the ordinary schedule), so the (morphology, it, draw) sequence is the eager trainer's
+            mlp = getattr(self.args, "actor_type", "set") == "mlp"
+            self.graphed = (GraphedMlpUpdates if mlp else GraphedUpdates)(self.agent, self.batch_size)
+            self._graphed_lazy = mlp
         self.begin_round()
 
     @property
@@ -177,7 +181,7 @@ class DeviceTrainer(object):
         if self.is_learner:
             self.agent.models2train()
             start = [0] * len(self.env_names)
-            if self.graphed is not None:
+            if self.graphed is not None and not self._graphed_lazy:
                 # every morphology runs eagerly before any graph bakes a pointer (capture protocol of td3.GraphedUpdates): the
                 # FIRST iterations of its schedule serve as those eager runs -- same number of updates as the reference's
                 # schedule, in the first such round the morphologies' first two iterations come before everybody's remaining ones
@@ -202,7 +206,7 @@ class DeviceTrainer(object):
                         self._updates += 1
                         continue
                     batch = self.buffers[k].sample(self.batch_size, generator=self.gen)
-                    if self.graphed is not None and k in self.graphed.warmed:
+                    if self.graphed is not None and (self._graphed_lazy or k in self.graphed.warmed):
                         self.last_losses[name] = self.graphed.update(k, self.graph_dicts[k], self.ro.env.num_limbs[k], batch, it)
                     else:
                         self.last_losses[name] = self.agent.update(batch, it)
@@ -219,7 +223,7 @@ class DeviceTrainer(object):
         """One update of morphology k on a batch drawn by sample_into with (sample_seed, draw); the counter moves once per update."""
         draw, buf, L = self.draw, self.buffers[k], self.ro.env.num_limbs[k]
         self.draw += 1
-        if self.graphed is not None and k in self.graphed.warmed:
+        if self.graphed is not None and (self._graphed_lazy or k in self.graphed.warmed):
             return self.graphed.update_from(k, self.graph_dicts[k], L, buf, it, self.sample_seed, draw)
         sl = self._eager_slots.get(k)
         if sl is None:               # per-morphology tensors kept by the trainer: nothing is allocated per update

@@ -16,7 +16,7 @@ larger of the two arms' spreads -- the condition under which td3.MLP_HIP_OPTIM_D
 MLP_HIP_GRADS_DEFAULT).  The code stays opt-in either way.
 
 Device events per update are COUNTED (torch.profiler, one update with and one without the actor step, after the timing).  Not
-measured here: kernel times in isolation, and hipGraph replay."""
+measured here: kernel times in isolation, and hipGraph replay (tools/mlp_graph_bench.py)."""
 import json
 import os
 import sys

@@ -13,7 +13,7 @@ Decision recorded in the output: the new path becomes td3.MLP_HIP_GRADS_DEFAULT 
 the parent arm's by more than the larger of the two arms' spreads.
 
 Eager launches per update are COUNTED (torch.profiler device events of one update with and one without the actor step, after the
-timing).  Not measured here: kernel times in isolation (they need a profiler run of their own), and hipGraph replay."""
+timing).  Not measured here: kernel times in isolation (they need a profiler run of their own), and hipGraph replay (tools/mlp_graph_bench.py)."""
 import json
 import os
 import sys
