@@ -169,6 +169,20 @@ int sgrl_attention_forward(const float* qkv, const float* vgp, const float* gdir
 int sgrl_attention_backward(const float* qkv, const float* vgp, const float* gdir, float scale, const float* w, const float* d_o,
                             const float* d_og, float* dqkv, float* dvgp, float* dgdh, float* ds, int B, int L, void* stream);
 
+/* Limb attention of the SWAT networks (swat_policy._SelfAttention between in_proj and out_proj): B environments with 1 <= L <= 15
+ * limbs (SGRL_SWAT_MAX_LIMBS), 2 heads x 64 channels.  qkv [B, L, 384] = q | k | v as in_proj leaves them (q in columns 0..127, k
+ * in 128..255, v in 256..383; head h owns columns 64 h .. 64 h + 63 of each; q is multiplied by `scale` inside); bias [2, L, L] or
+ * null.
+ *   w[b][h][i][:] = softmax_j(scale q_i . k_j + bias[h][i][j]),  o[b][i][64 h + d] = sum_j w[b][h][i][j] v[b][j][64 h + d]
+ * w [B, 2, L, L] is returned for the backward, which takes d_o [B, L, 128] and yields dqkv [B, L, 384] and ds [B, 2, L, L] (the score
+ * gradient: its sum over the environments is the gradient of `bias`):
+ *   dw = d_o v',  ds = w (dw - sum_j w dw),  dq = scale ds k,  dk = ds' (scale q),  dv = w' d_o.
+ * One launch per call, no atomics, fixed summation order (bit-reproducible).  B <= 0, L outside 1..15 or a null pointer (other
+ * than bias) returns SGRL_ERR_ARG before anything is launched. */
+int sgrl_swat_attention_forward(const float* qkv, const float* bias, float scale, float* w, float* o, int B, int L, void* stream);
+int sgrl_swat_attention_backward(const float* qkv, float scale, const float* w, const float* d_o, float* dqkv, float* ds, int B, int L,
+                                 void* stream);
+
 const char* sgrl_train_last_error(void);
 
 #ifdef __cplusplus

@@ -857,6 +857,147 @@ __global__ __launch_bounds__(128) void k_attn_bwd(const float* __restrict__ qkv,
     }
 }
 
+// Limb attention of the SWAT networks (swat_policy._SelfAttention between in_proj and out_proj): the ordinary 2 heads x 64 channels
+// over L <= SL = 15 limbs (SGRL_SWAT_MAX_LIMBS).  qkv [B, L, 384] = q | k | v as in_proj leaves them, head h owns columns
+// 64 h .. 64 h + 63 of each; bias [2, L, L] or null.
+//   w = softmax_j(scale q_i . k_j + bias[h][i][j]);   o[b][i][64 h + d] = sum_j w[h][i][j] v[j][64 h + d]
+// Built on what k_attn_fwd / k_attn_bwd learned: ONE wavefront per (environment, head) with a thread per channel; every global load
+// issued in one batch at the top (3 L values per thread forward, 4 L backward, plus the thread's share of bias / w); q (scaled) and k
+// -- backward: do and v -- in LDS rows of pitch 65, so that the rows of different limbs start on different banks; one thread per
+// (i, j) score entry (64 products in four partial sums), one thread per softmax row with the row maximum subtracted; outputs by a
+// thread per channel from its registers.  Plain loads and stores, fixed summation order: the same input gives the same bits.
+constexpr int SL = 15, SQ = 65;
+__device__ __forceinline__ float swat_dot64(const float* a, const float* k) {
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int x = 0; x < 64; x += 4) {
+#pragma unroll
+    for (int u = 0; u < 4; u++) acc[u] += a[x + u] * k[x + u];
+  }
+  return (acc[0] + acc[1]) + (acc[2] + acc[3]);
+}
+__global__ __launch_bounds__(64) void k_swat_attn_fwd(const float* __restrict__ qkv, const float* __restrict__ bias, float scale,
+                                                      float* wout, float* o, int L) {
+  __shared__ float qs[SL * SQ], ks[SL * SQ];
+  __shared__ float sc[SL * SL];
+  const int b = blockIdx.x >> 1, h = blockIdx.x & 1, d = threadIdx.x, c = 64 * h + d;
+  const size_t n0 = (size_t)b * L;
+  const int LL = L * L;
+  float qv[SL], kv[SL], vv[SL], bz[4];
+#pragma unroll
+  for (int i = 0; i < SL; i++)
+    if (i < L) {
+      const float* row = qkv + (n0 + i) * 384 + c;
+      qv[i] = row[0]; kv[i] = row[128]; vv[i] = row[256];
+    }
+#pragma unroll
+  for (int t = 0; t < 4; t++) {                      // L L <= 225 entries: at most four per thread
+    const int e = d + 64 * t;
+    bz[t] = (bias && e < LL) ? bias[h * LL + e] : 0.f;
+  }
+#pragma unroll
+  for (int i = 0; i < SL; i++)
+    if (i < L) { qs[i * SQ + d] = qv[i] * scale; ks[i * SQ + d] = kv[i]; }
+  __syncthreads();
+#pragma unroll
+  for (int t = 0; t < 4; t++) {
+    const int e = d + 64 * t;
+    if (e < LL) sc[e] = swat_dot64(qs + (e / L) * SQ, ks + (e % L) * SQ) + bz[t];
+  }
+  __syncthreads();
+  if (d < L) {
+    float* row = sc + d * L;
+    float mx = row[0];
+    for (int j = 1; j < L; j++) mx = fmaxf(mx, row[j]);
+    float sum = 0.f;
+    for (int j = 0; j < L; j++) { row[j] = expf(row[j] - mx); sum += row[j]; }
+    for (int j = 0; j < L; j++) row[j] = row[j] / sum;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int t = 0; t < 4; t++) {
+    const int e = d + 64 * t;
+    if (e < LL) wout[((size_t)b * 2 + h) * LL + e] = sc[e];
+  }
+#pragma unroll
+  for (int i = 0; i < SL; i++)
+    if (i < L) {
+      float acc = 0.f;
+#pragma unroll
+      for (int j = 0; j < SL; j++) if (j < L) acc += sc[i * L + j] * vv[j];
+      o[(n0 + i) * 128 + c] = acc;
+    }
+}
+// Backward: dw = do v' (per head), ds = w (dw - sum_j w dw), dq = scale ds k, dk = ds' (scale q), dv = w' do.  dqkv [B, L, 384] is
+// written packed, ds [B, 2, L, L] is written out as well (its sum over the environments is the gradient of the relation bias).
+__global__ __launch_bounds__(64) void k_swat_attn_bwd(const float* __restrict__ qkv, float scale, const float* __restrict__ win,
+                                                      const float* __restrict__ dout, float* dqkv, float* ds_out, int L) {
+  __shared__ float as[SL * SQ], vs[SL * SQ];
+  __shared__ float w[SL * SL], dw[SL * SL];
+  const int b = blockIdx.x >> 1, h = blockIdx.x & 1, d = threadIdx.x, c = 64 * h + d;
+  const size_t n0 = (size_t)b * L;
+  const int LL = L * L;
+  float qv[SL], kv[SL], vv[SL], av[SL], wz[4];
+#pragma unroll
+  for (int i = 0; i < SL; i++)
+    if (i < L) {
+      const float* row = qkv + (n0 + i) * 384 + c;
+      qv[i] = row[0]; kv[i] = row[128]; vv[i] = row[256];
+      av[i] = dout[(n0 + i) * 128 + c];
+    }
+#pragma unroll
+  for (int t = 0; t < 4; t++) {
+    const int e = d + 64 * t;
+    wz[t] = e < LL ? win[((size_t)b * 2 + h) * LL + e] : 0.f;
+  }
+#pragma unroll
+  for (int i = 0; i < SL; i++)
+    if (i < L) { as[i * SQ + d] = av[i]; vs[i * SQ + d] = vv[i]; }
+#pragma unroll
+  for (int t = 0; t < 4; t++) {
+    const int e = d + 64 * t;
+    if (e < LL) w[e] = wz[t];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int t = 0; t < 4; t++) {                      // dw[i][j] = do[i] . v[j]
+    const int e = d + 64 * t;
+    if (e < LL) dw[e] = swat_dot64(as + (e / L) * SQ, vs + (e % L) * SQ);
+  }
+  __syncthreads();
+  if (d < L) {                                       // softmax backward, one thread per row i; dw becomes ds in place
+    const float* wr = w + d * L;
+    float* dr = dw + d * L;
+    float dot = 0.f;
+    for (int j = 0; j < L; j++) dot += wr[j] * dr[j];
+    for (int j = 0; j < L; j++) dr[j] = wr[j] * (dr[j] - dot);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int t = 0; t < 4; t++) {
+    const int e = d + 64 * t;
+    if (e < LL) ds_out[((size_t)b * 2 + h) * LL + e] = dw[e];
+  }
+#pragma unroll
+  for (int i = 0; i < SL; i++)
+    if (i < L) {                                     // dq[i] = scale sum_j ds[i][j] k[j]
+      float acc = 0.f;
+#pragma unroll
+      for (int j = 0; j < SL; j++) if (j < L) acc += dw[i * L + j] * kv[j];
+      dqkv[(n0 + i) * 384 + c] = acc * scale;
+    }
+#pragma unroll
+  for (int j = 0; j < SL; j++)
+    if (j < L) {                                     // dk[j] = sum_i ds[i][j] (scale q[i]);  dv[j] = sum_i w[i][j] do[i]
+      float ak = 0.f, avv = 0.f;
+#pragma unroll
+      for (int i = 0; i < SL; i++)
+        if (i < L) { ak += dw[i * L + j] * (qv[i] * scale); avv += w[i * L + j] * av[i]; }
+      dqkv[(n0 + j) * 384 + 128 + c] = ak;
+      dqkv[(n0 + j) * 384 + 256 + c] = avv;
+    }
+}
+
 // Equivariant contraction of a node's three 32-vectors with its 32 x 32 matrix (reference SEActor.py:108-110, 262-264):
 //   t[s][c] = sum_a z[s][a] mat[a][c]       backward:  dz[s][a] = sum_c dt[s][c] mat[a][c],  dmat[a][c] = sum_s z[s][a] dt[s][c]
 // One 128-thread half-workgroup per node (two nodes per workgroup).
@@ -1335,6 +1476,23 @@ int sgrl_attention_forward(const float* qkv, const float* vgp, const float* gdir
   if (!qkv || !vgp || !gdir || !w || !o || !og || B <= 0 || L < 1 || L > AL) return tfail(SGRL_ERR_ARG, "sgrl_attention_forward: bad argument");
   hipLaunchKernelGGL(k_attn_fwd, dim3(2 * B), dim3(128), 0, (hipStream_t)stream, qkv, vgp, gdir, bias, scale, w, o, og, L);
   { int lrc = SGRL_OK; if (!launched("k_attn_fwd launch failed", &lrc)) return lrc; }
+  return SGRL_OK;
+}
+
+int sgrl_swat_attention_forward(const float* qkv, const float* bias, float scale, float* w, float* o, int B, int L, void* stream) {
+  if (!qkv || !w || !o || B <= 0 || B > (1 << 30) || L < 1 || L > SL)
+    return tfail(SGRL_ERR_ARG, "sgrl_swat_attention_forward: bad argument (null pointer, B <= 0 or L outside 1..15)");
+  hipLaunchKernelGGL(k_swat_attn_fwd, dim3(2 * B), dim3(64), 0, (hipStream_t)stream, qkv, bias, scale, w, o, L);
+  { int lrc = SGRL_OK; if (!launched("k_swat_attn_fwd launch failed", &lrc)) return lrc; }
+  return SGRL_OK;
+}
+
+int sgrl_swat_attention_backward(const float* qkv, float scale, const float* w, const float* d_o, float* dqkv, float* ds, int B, int L,
+                                 void* stream) {
+  if (!qkv || !w || !d_o || !dqkv || !ds || B <= 0 || B > (1 << 30) || L < 1 || L > SL)
+    return tfail(SGRL_ERR_ARG, "sgrl_swat_attention_backward: bad argument (null pointer, B <= 0 or L outside 1..15)");
+  hipLaunchKernelGGL(k_swat_attn_bwd, dim3(2 * B), dim3(64), 0, (hipStream_t)stream, qkv, scale, w, d_o, dqkv, ds, L);
+  { int lrc = SGRL_OK; if (!launched("k_swat_attn_bwd launch failed", &lrc)) return lrc; }
   return SGRL_OK;
 }
 

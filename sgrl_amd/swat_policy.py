@@ -6,8 +6,9 @@ limbs (embedding size 128, 2 heads, 3 layers) with the three traversal-index pos
 relation bias (PPR, symmetric Laplacian, distance -> one additive bias per head) on the first layer only.  Plain
 differentiable PyTorch; outputs are pinned to fixtures produced by executing the reference's own modules
 (tests/golden/swat_forward.npz, tools/capture_golden_swat.py).  The batched rollout runs the actor's no-grad forward on the HIP
-kernels of swat_hip.HipSwatActor (csrc/swat_actor.hip), which read this module's parameters in place; `forward` itself stays
-PyTorch (the TD3 update back-props through it).  The no-grad target chain of an update (td3.Agent.update_targets) runs on the
+kernels of swat_hip.HipSwatActor (csrc/swat_actor.hip), which read this module's parameters in place; `forward` itself is what
+the TD3 update back-props through: PyTorch operations by default, the training kernels of train_ops with `train_kernels` on
+(_TrainKernelsSwitch; td3.Agent(swat_train_kernels=True)).  The no-grad target chain of an update (td3.Agent.update_targets) runs on the
 same kernels through `hip_handle()`: the handle a module caches is per-process device state and is dropped whenever the
 module is pickled or deep-copied.
 """
@@ -18,10 +19,29 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import train_ops
 from .set_policy import ConcatPositionalEmbedding
 
 
-class _SelfAttention(nn.Module):
+class _TrainKernelsSwitch(object):
+    """`train_kernels` (default False): the differentiable passes of the module on the library's own training kernels
+    (train_ops: linear, swat_attention, add_layer_norm) instead of PyTorch's operations.  Setting it on a module sets it on every
+    module below it.  A plain attribute: no parameter, not in state_dict(), kept by pickle / deepcopy.  Every train_ops entry falls
+    back to the operations of the switch-off forward wherever its kernels do not run (CPU, float64, torch.no_grad()), so there
+    the switch changes no bit."""
+
+    @property
+    def train_kernels(self):
+        return self.__dict__.get("_train_kernels", False)
+
+    @train_kernels.setter
+    def train_kernels(self, on):
+        for m in self.modules():
+            if isinstance(m, _TrainKernelsSwitch):
+                m.__dict__["_train_kernels"] = bool(on)
+
+
+class _SelfAttention(_TrainKernelsSwitch, nn.Module):
     """Parameters of torch.nn.MultiheadAttention (in_proj_weight / in_proj_bias / out_proj), forward of the reference's
     attentions.multi_head_attention_forward: q scaled by head_dim^-0.5, additive float mask [B * H, L, L]."""
 
@@ -34,11 +54,15 @@ class _SelfAttention(nn.Module):
         nn.init.xavier_uniform_(self.in_proj_weight)
         nn.init.zeros_(self.out_proj.bias)
 
-    def forward(self, x, bias=None):
-        """x [B, L, E]; bias [H, L, L] or None."""
+    def forward(self, x, bias=None, slot=None):
+        """x [B, L, E]; bias [H, L, L] or None.  slot (train_kernels): x is an alias handed out by train_ops.fan_out."""
         B, L, E = x.shape
         H = self.num_heads
         hd = E // H
+        if self.train_kernels:
+            qkv = train_ops.linear(x, self.in_proj_weight, self.in_proj_bias, slot=slot)
+            o = train_ops.swat_attention(qkv, bias, float(hd) ** -0.5, H)
+            return train_ops.linear(o, self.out_proj.weight, self.out_proj.bias)
         q, k, v = F.linear(x, self.in_proj_weight, self.in_proj_bias).chunk(3, dim=-1)
         q = (q * float(hd) ** -0.5).view(B, L, H, hd)
         k, v = k.view(B, L, H, hd), v.view(B, L, H, hd)
@@ -50,7 +74,7 @@ class _SelfAttention(nn.Module):
         return self.out_proj(o)
 
 
-class _EncoderLayer(nn.Module):
+class _EncoderLayer(_TrainKernelsSwitch, nn.Module):
     """reference MyTransformerEncoderLayer (StructureActor.py:48-66): post-norm, ReLU feed-forward, dropout = identity at
     the reference's dropout_rate 0."""
 
@@ -63,11 +87,20 @@ class _EncoderLayer(nn.Module):
         self.norm2 = nn.LayerNorm(d_model)
 
     def forward(self, x, bias=None):
+        if self.train_kernels:
+            # x feeds in_proj and the residual, the first norm's output linear1 and the residual: handed out as aliases
+            # (train_ops.fan_out), so that the two products add their input gradients onto the residual's instead of leaving an
+            # element-wise addition each to autograd.  The hidden activation feeds linear2 only: the masked pair of train_ops.linear
+            sa, (xa, xb) = train_ops.fan_out(x, 2)
+            x = train_ops.add_layer_norm(xb, self.self_attn(xa, bias, slot=sa), self.norm1)
+            sf, (xa, xb) = train_ops.fan_out(x, 2)
+            h = train_ops.linear(xa, self.linear1.weight, self.linear1.bias, relu=True, premasked=True, slot=sf)
+            return train_ops.add_layer_norm(xb, train_ops.linear(h, self.linear2.weight, self.linear2.bias, x_relu=True), self.norm2)
         x = self.norm1(x + self.self_attn(x, bias))
         return self.norm2(x + self.linear2(F.relu(self.linear1(x))))
 
 
-class _Encoder(nn.Module):
+class _Encoder(_TrainKernelsSwitch, nn.Module):
     """reference RepeatTransformerEncoder (StructureActor.py:68-107)."""
 
     def __init__(self, layer, num_layers, nhead, norm=None, d_rel=3):
@@ -82,10 +115,12 @@ class _Encoder(nn.Module):
         bias = self.rel_encoder(rel).permute(2, 0, 1)          # [H, i, j]
         for i, layer in enumerate(self.layers):
             x = layer(x, bias if i == 0 else None)
+        if self.norm is not None and self.train_kernels:
+            return train_ops.add_layer_norm(x, None, self.norm)
         return self.norm(x) if self.norm is not None else x
 
 
-class TransformerModel(nn.Module):
+class TransformerModel(_TrainKernelsSwitch, nn.Module):
     """reference StructureActor.TransformerModel (StructureActor.py:110-168)."""
 
     def __init__(self, feature_size, output_size, ninp, nhead, nhid, nlayers, dropout=0.0, condition_decoder=False,
@@ -106,11 +141,12 @@ class TransformerModel(nn.Module):
 
     def forward(self, x, graph):
         """x [B, L, feature] (node-major) -> [B, L, output_size]."""
-        h = self.encoder(x) * math.sqrt(self.ninp)
+        kernels = self.train_kernels
+        h = (train_ops.linear(x, self.encoder.weight, self.encoder.bias) if kernels else self.encoder(x)) * math.sqrt(self.ninp)
         h = self.transformer_encoder(h, self.pos_encoder(graph["traversals"]), graph["relation"])
         if self.condition_decoder:
             h = torch.cat([h, x], dim=2)
-        return self.decoder(h)
+        return train_ops.linear(h, self.decoder.weight, self.decoder.bias) if kernels else self.decoder(h)
 
 
 def _model(feature, out, args):
@@ -120,7 +156,7 @@ def _model(feature, out, args):
                             rel_size=args.rel_size)
 
 
-class StructurePolicy(nn.Module):
+class StructurePolicy(_TrainKernelsSwitch, nn.Module):
     """Drop-in for reference StructureActor.StructurePolicy (constructor of StructureActor.py:179-191)."""
 
     def __init__(self, state_dim, action_dim, msg_dim, batch_size, max_action, max_children, disable_fold, td, bu,
@@ -165,7 +201,7 @@ class StructurePolicy(nn.Module):
         self.num_limbs = len(self.parents)
 
 
-class CriticStructurePolicy(nn.Module):
+class CriticStructurePolicy(_TrainKernelsSwitch, nn.Module):
     """Drop-in for reference StructureCritic.CriticStructurePolicy (per-limb twin Q values [B, L])."""
 
     def __init__(self, state_dim, action_dim, msg_dim, batch_size, max_children, disable_fold, td, bu, args=None,

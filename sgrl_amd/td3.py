@@ -294,10 +294,14 @@ MLP_HIP_GRADS_DEFAULT = True
 # Whether such an agent also takes the HIP optimizer half (mlp_hip.HipMlpOptim: clip, Adam and the soft update of a network in two
 # launches) when the caller does not say: opt-in (tools/mlp_optim_bench.py, profiles/mlp_optim_bench.json)
 MLP_HIP_OPTIM_DEFAULT = False
+# Whether a swat + swat agent on the GPU runs the differentiable passes of its update (both critics' forward and backward, the actor
+# loss through critic.Q1(actor(obs))) on the training kernels of train_ops (swat_policy `train_kernels`) when the caller does not say:
+# opt-in until a SWAT learning curve has been re-run with it (tools/swat_update_bench.py)
+SWAT_TRAIN_KERNELS_DEFAULT = False
 
 
 class Agent(nn.Module):
-    def __init__(self, args, device=None, use_hip=True, mlp_hip_grads=None, mlp_hip_optim=None):
+    def __init__(self, args, device=None, use_hip=True, mlp_hip_grads=None, mlp_hip_optim=None, swat_train_kernels=None):
         super().__init__()
         self.args = args
         atype, ctype = getattr(args, "actor_type", "set"), getattr(args, "critic_type", "set")
@@ -354,6 +358,14 @@ class Agent(nn.Module):
         # created by the first update on a CUDA batch); anything else keeps the PyTorch chain of update_targets
         self.use_swat_hip = bool(use_hip) and atype == "swat" and ctype == "swat"
         self._swat_targets = None
+        # swat_train_kernels: the ONLINE swat actor and critic differentiate on the training kernels (swat_policy `train_kernels`;
+        # the targets run the HIP chain above); None: args.swat_train_kernels, then SWAT_TRAIN_KERNELS_DEFAULT.  Follows use_hip;
+        # ignored by every other agent type, as mlp_hip_grads is
+        if swat_train_kernels is None:
+            swat_train_kernels = getattr(args, "swat_train_kernels", None)
+        if swat_train_kernels is None:
+            swat_train_kernels = SWAT_TRAIN_KERNELS_DEFAULT
+        self.set_swat_train_kernels(self.use_swat_hip and bool(swat_train_kernels))
         # the same for SMP actor AND critic in the published mode (td and bu; smp_hip.HipSmpTargets); the td-only mode stays PyTorch
         self.use_smp_hip = bool(use_hip) and atype == "smp" and ctype == "smp" and bool(args.td) and bool(args.bu)
         self._smp_targets = None
@@ -378,6 +390,14 @@ class Agent(nn.Module):
             mlp_hip_optim = MLP_HIP_OPTIM_DEFAULT
         self.use_mlp_hip_optim = self.use_mlp_hip_grads and bool(mlp_hip_optim)
         self._mlp_optim = None
+
+    def set_swat_train_kernels(self, on):
+        """Turn the training kernels of the online swat networks on or off (no other agent type has the switch)."""
+        self.use_swat_train_kernels = bool(on) and getattr(self.args, "actor_type", "set") == "swat" and \
+            getattr(self.args, "critic_type", "set") == "swat"
+        for net in (self.actor, self.critic):
+            if hasattr(type(net), "train_kernels"):
+                net.train_kernels = self.use_swat_train_kernels
 
     def __getstate__(self):
         d = self.__dict__.copy()
@@ -672,6 +692,7 @@ class GraphedUpdates(object):
                                "updates eagerly (DeviceTrainer(graph_updates=False))")
         # the workspace stamps below follow the SET handles only: a SWAT or SMP agent's graphs record the PyTorch target chain
         agent.use_swat_hip = False
+        agent.set_swat_train_kernels(False)      # graphed SWAT agents stay plain PyTorch throughout, as before
         agent.use_smp_hip = False
         for opt in (agent.actor_optimizer, agent.critic_optimizer):
             if opt.state:

@@ -46,6 +46,8 @@ def _L():
         L.sgrl_zmat_backward.argtypes = [vp, vp, vp, vp, vp, ci, vp]
         L.sgrl_attention_forward.argtypes = [vp, vp, vp, vp, ctypes.c_float, vp, vp, vp, ci, ci, vp]
         L.sgrl_attention_backward.argtypes = [vp, vp, vp, ctypes.c_float, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp]
+        L.sgrl_swat_attention_forward.argtypes = [vp, vp, ctypes.c_float, vp, vp, ci, ci, vp]
+        L.sgrl_swat_attention_backward.argtypes = [vp, ctypes.c_float, vp, vp, vp, vp, ci, ci, vp]
         L.sgrl_linear_forward_fused.argtypes = [vp, ci, vp, ci, vp, vp, vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, vp]
         L.sgrl_linear_forward_twin_fused.argtypes = [vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, ci, ci, ci, ci, ci, vp]
         L.sgrl_embed3_forward.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, ci, vp]
@@ -557,6 +559,38 @@ class _AttnFn(torch.autograd.Function):
         return dqkv, dvgp, dgdir, dbias, None
 
 
+class _SwatAttnFn(torch.autograd.Function):
+    """qkv [B, L, 384], bias [2, L, L] or None -> o [B, L, 128]: the SWAT networks' attention, 2 heads x 64 channels, L <= 15
+    (csrc/train_gemm.hip k_swat_attn_fwd / k_swat_attn_bwd), one launch forward and one backward."""
+
+    @staticmethod
+    def forward(ctx, qkv, bias, scale):
+        L = _L()
+        B, Ln = qkv.shape[0], qkv.shape[1]
+        qkv = qkv if qkv.is_contiguous() else qkv.contiguous()
+        bz = None if bias is None else (bias if bias.is_contiguous() else bias.contiguous())
+        w = torch.empty((B, 2, Ln, Ln), dtype=torch.float32, device=qkv.device)
+        o = torch.empty((B, Ln, 128), dtype=torch.float32, device=qkv.device)
+        st = ctypes.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream)
+        _check(L, L.sgrl_swat_attention_forward(_p(qkv), _p(bz), ctypes.c_float(scale), _p(w), _p(o), B, Ln, st), "sgrl_swat_attention_forward")
+        ctx.save_for_backward(qkv, w)
+        ctx.has_bias, ctx.scale = bias is not None, float(scale)
+        return o
+
+    @staticmethod
+    def backward(ctx, d_o):
+        L = _L()
+        qkv, w = ctx.saved_tensors
+        B, Ln = qkv.shape[0], qkv.shape[1]
+        d_o = d_o if d_o.is_contiguous() else d_o.contiguous()
+        dqkv, ds = torch.empty_like(qkv), torch.empty_like(w)
+        st = ctypes.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream)
+        _check(L, L.sgrl_swat_attention_backward(_p(qkv), ctypes.c_float(ctx.scale), _p(w), _p(d_o), _p(dqkv), _p(ds), B, Ln, st),
+               "sgrl_swat_attention_backward")
+        dbias = ds.sum(0) if (ctx.has_bias and ctx.needs_input_grad[1]) else None
+        return (dqkv if ctx.needs_input_grad[0] else None), dbias, None
+
+
 class _AddLNFn(torch.autograd.Function):
     """y = LayerNorm(x + res) * w + b over 128 columns, one launch forward and one backward (csrc/train_gemm.hip k_add_ln_*);
     w1 / b1 given: x stacks TWO networks along dim 0, each with its own affine pair."""
@@ -821,6 +855,29 @@ def set_attention(qkv, vgp, gdir, bias, scale):
     o = torch.einsum("bhij,bjhd->bihd", w, vh).reshape(B, Ln, 256)
     og = torch.einsum("bhij,bjshd->bishd", w, vg).reshape(B, Ln, 3, 256)
     return o, og
+
+
+SWAT_MAX_LIMBS = 15      # SGRL_SWAT_MAX_LIMBS (include/sgrl_swat.h): what k_swat_attn_* hold in registers
+
+
+def swat_attention(qkv, bias, scale, num_heads=2):
+    """Limb attention of the SWAT networks (swat_policy._SelfAttention between in_proj and out_proj): qkv [B, L, 3 E] = q | k | v
+    (q is multiplied by `scale` here), bias [H, L, L] or None -> o [B, L, E] with w = softmax_j(scale q_i . k_j + bias) per head.
+    One launch forward and one backward when autograd records on the GPU, E = 128, H = 2 and L <= 15; the module's own operations,
+    one for one, otherwise."""
+    B, Ln = qkv.shape[:2]
+    if qkv.dim() == 3 and qkv.shape[-1] == 384 and num_heads == 2 and 1 <= Ln <= SWAT_MAX_LIMBS and B > 0 and _on_device_with_grad(qkv, bias):
+        return _SwatAttnFn.apply(qkv, bias, float(scale))
+    E = qkv.shape[-1] // 3
+    H, hd = num_heads, E // num_heads
+    q, k, v = qkv.chunk(3, dim=-1)
+    q = (q * scale).view(B, Ln, H, hd)
+    k, v = k.view(B, Ln, H, hd), v.view(B, Ln, H, hd)
+    s = torch.einsum("bihd,bjhd->bhij", q, k)
+    if bias is not None:
+        s = s + bias.unsqueeze(0)
+    w = F.softmax(s, dim=-1)
+    return torch.einsum("bhij,bjhd->bihd", w, v).reshape(B, Ln, E)
 
 
 def zmat(z, mat):

@@ -2,7 +2,7 @@
 """Timing of the HIP SWAT twin critic forward and of an eager TD3 update of a SWAT agent with / without the HIP target chain.
 
 usage: swat_update_bench.py forward [config3|config5] [reps=60]
-       swat_update_bench.py update [morphology=3d_walker_7_full] [hip|pytorch|auto] [updates=40] [streams=1]
+       swat_update_bench.py update [morphology=3d_walker_7_full] [hip|pytorch|auto|kernels] [updates=40] [streams=1]
   forward  twin critic forward (swat_hip.HipSwatCritic, both networks) over the 8 walker variants x 1024 environments (config3)
            or one GPU's share of 3D_CWHH++ (config5: 23 morphologies, 8188 environments), against the PyTorch path (per
            morphology: change_morphology + CriticStructurePolicy.forward under no_grad).  With two streams and with the second
@@ -11,7 +11,8 @@ usage: swat_update_bench.py forward [config3|config5] [reps=60]
   update   one eager Agent.update (td3.py) of a SWAT agent at batch 256 on one morphology: 8 untimed updates, then `updates`
            timed ones (host clock around update + device synchronisation; every second update includes the delayed actor
            step, as in training).  `hip`: the target chain on HIP (Agent(use_hip=True)); `pytorch`: Agent(use_hip=False);
-           `auto`: the build's default.  The pytorch / auto arms use no API newer than Agent.update, so this mode also runs
+           `auto`: the build's default; `kernels`: the HIP target chain AND the differentiable passes on the training kernels
+           (Agent(swat_train_kernels=True)).  The pytorch / auto arms use no API newer than Agent.update, so this mode also runs
            on a checkout that has no HIP target chain.  streams=0: the chain's second critic on the caller's stream.
 Prints one JSON line per run.
 """
@@ -111,7 +112,10 @@ def update(name, arm, updates, streams):
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     args = default_train_args(actor_type="swat", critic_type="swat")
-    agent = Agent(args, device=dev) if arm == "auto" else Agent(args, device=dev, use_hip=(arm == "hip"))
+    if arm == "kernels":
+        agent = Agent(args, device=dev, swat_train_kernels=True)
+    else:
+        agent = Agent(args, device=dev) if arm == "auto" else Agent(args, device=dev, use_hip=(arm == "hip"))
     g = G.getGraphDict(mjcf.load_asset(name).parents, TRAV, [], device=dev)
     L, B = len(g["parents"]), 256
     agent.change_morphology(g)
@@ -140,6 +144,7 @@ def update(name, arm, updates, streams):
     ms = np.asarray(ms)
     print(json.dumps({"mode": "update", "morphology": name, "limbs": L, "batch": B, "arm": arm,
                       "hip_target_chain": getattr(agent, "_swat_targets", None) is not None, "twin_streams": bool(streams),
+                      "train_kernels": bool(getattr(agent, "use_swat_train_kernels", False)),
                       "update_ms_mean": round(float(ms.mean()), 4), "update_ms_median": round(float(np.median(ms)), 4),
                       "update_ms_min": round(float(ms.min()), 4), "critic_only_ms_median": round(float(np.median(ms[1::2])), 4),
                       "with_actor_ms_median": round(float(np.median(ms[0::2])), 4), "updates": int(updates),
