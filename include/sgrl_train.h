@@ -183,6 +183,46 @@ int sgrl_swat_attention_forward(const float* qkv, const float* bias, float scale
 int sgrl_swat_attention_backward(const float* qkv, float scale, const float* w, const float* d_o, float* dqkv, float* ds, int B, int L,
                                  void* stream);
 
+/* ---- SMP networks (sgrl_amd/smp_policy.py `train_kernels`; csrc/smp_train.hip) --------------------------------------------------
+ * What lies between the linear layers of the message-passing networks' differentiable passes, one launch per call, float32, on
+ * `stream`, no host synchronisation, no atomics, no scratch; every output element is written exactly once in a fixed order
+ * (bit-reproducible).  Limits as in sgrl_smp.h: SGRL_SMP_MAX_LIMBS = 16 nodes per level, SGRL_SMP_MAX_CHILDREN = 8, messages 32 wide.
+ * An argument error returns SGRL_ERR_ARG with the function's name in the message BEFORE anything is launched: a null required
+ * pointer, B (R) <= 0, a node count outside 1..16, `S` (the child slots: max_children) outside 1..8, a width outside the ranges
+ * below, a table entry outside its source.
+ *
+ * Message gather of the n limbs of one tree level, rows [n, B, .]:
+ *   out[j][b] = act([ own'(j, b) | seg_0 | ... | seg_{S-1} ])                                   out [n, B, W0 + 32 S]
+ *   own [n, B, W0], W0 = 0 (no own part, own may be null), 32 or 64; own' = own / max(||own||, 1e-12) if normalize != 0 (F.normalize;
+ *     inv [n, B] then receives 1 / max(||own||, 1e-12) for the backward), own otherwise;
+ *   seg_s = 32 columns of src [n_src, B, Wsrc] (Wsrc a multiple of 32, <= 256) at row block node[j * S + s], columns off[j * S + s] ..
+ *     + 31 (a multiple of 32); node = -1: zeros; src == null: all segments zero (n_src, Wsrc and the table's values are not read);
+ *   act = tanh if act_tanh != 0, the identity otherwise.
+ * node / off are HOST arrays of n * S int32 (sgrl_amd/smp_policy._Tree decides them: children bottom-up, the parent's slot top-down):
+ * they are checked here and travel in the kernel's arguments -- no call copies anything to the device.
+ * Backward, from d_out [n, B, W0 + 32 S] (and `out` when act_tanh, `own` and `inv` when normalize):
+ *   d_own [n, B, W0] through tanh' and the normalisation's Jacobian (null: not wanted; must be null when W0 = 0);
+ *   d_src [n_src, B, Wsrc], ALL of it: the 32-column group a segment read receives that segment's gradient, a group nobody read
+ *     zeros (null: not wanted).  Two table entries reading the same group are refused (SGRL_ERR_ARG): plain stores, one writer. */
+int sgrl_smp_gather_forward(const float* own, int W0, int normalize, const float* src, int n_src, int Wsrc, const int32_t* node,
+                            const int32_t* off, int S, int act_tanh, float* out, float* inv, int n, int B, void* stream);
+int sgrl_smp_gather_backward(const float* d_out, const float* out, const float* own, const float* inv, int W0, int normalize, int n_src,
+                             int Wsrc, const int32_t* node, const int32_t* off, int S, int act_tanh, float* d_own, float* d_src, int n,
+                             int B, void* stream);
+
+/* Tail of the bottom-up module (smp_policy._up_message behind fc2; reference ModularActor.py:35-47): a [R, 64] = fc2's output,
+ * w3 [32, 64], b3 [32]:  t = tanh(a) [R, 64] (stored),  z = w3 t + b3,  u = z / max(||z||, 1e-12) [R, 32],  inv [R] = 1 / max(||z||, 1e-12).
+ * Backward from du [R, 32]: dz [R, 32] (the gradient at fc3's output: du through the normalisation) and da [R, 64] = (dz w3)(1 - t^2).
+ * fc3's weight / bias gradients are dz^T t and the column sums of dz: sgrl_linear_wgrad_group with dy = dz, x = t. */
+int sgrl_smp_up_tail_forward(const float* a, const float* w3, const float* b3, float* t, float* u, float* inv, int R, void* stream);
+int sgrl_smp_up_tail_backward(const float* du, const float* u, const float* inv, const float* t, const float* w3, float* dz, float* da, int R,
+                              void* stream);
+
+/* F.normalize over the rows of x [R, W], 1 <= W <= 256: y = x / max(||x||, 1e-12), inv [R] = 1 / max(||x||, 1e-12).  Backward:
+ * dx = (dy - y (y . dy)) inv; a row shorter than 1e-12 was divided by 1e-12 and its gradient is dy / 1e-12, as torch's is. */
+int sgrl_row_normalize_forward(const float* x, float* y, float* inv, int R, int W, void* stream);
+int sgrl_row_normalize_backward(const float* dy, const float* y, const float* inv, float* dx, int R, int W, void* stream);
+
 const char* sgrl_train_last_error(void);
 
 #ifdef __cplusplus

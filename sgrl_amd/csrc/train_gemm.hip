@@ -29,6 +29,7 @@
 
 #include "../../include/sgrl.h"
 #include "../../include/sgrl_train.h"
+#include "train_internal.h"
 
 namespace {
 
@@ -1272,6 +1273,10 @@ int launch_bwd(SArgs d, SArgs w, float* ws, hipStream_t st) {
 }
 
 }  // namespace
+
+// the same two helpers for the other sources of this ABI (train_internal.h; csrc/smp_train.hip)
+int sgrl_train_detail::fail(int code, const std::string& msg) { return tfail(code, msg); }
+bool sgrl_train_detail::launched(const char* what, int* rc) { return ::launched(what, rc); }
 
 extern "C" {
 

@@ -9,9 +9,12 @@ dynamic batching is replaced by what it was a workaround for: the limbs of one t
 call of the shared module -- bottom-up from the deepest level, top-down from the root).  Message passing modes: `bu and td`
 (both ways, the published SMP) and `td` only -- the two the reference's `disable_fold` path can run (without top-down
 messages its forward raises at ModularActor.py:244, `torch.stack` of a list of None).
-Plain differentiable PyTorch: this is what the TD3 updates run through.  Collection in the device loop runs the actor in its
-published mode (`bu and td`) through the batched HIP forward instead (smp_hip.HipSmpActor, csrc/smp_actor.hip; `_Tree` below
-stays the one source of its schedule).  The no-grad target chain of an update (td3.Agent.update_targets: target actor and twin
+Plain differentiable PyTorch by default: this is what the TD3 updates run through.  With `train_kernels` on (default False;
+td3.Agent(smp_train_kernels=True)) the differentiable passes of the published mode keep whole [limbs of a level, B, .] tensors per tree
+level and run on the training kernels of train_ops (linear, smp_gather, smp_up_tail, normalize_rows: `_level_plan`, `_up_levels`,
+`_down_levels` below) wherever those kernels run; everywhere else the switch changes no bit.
+Collection in the device loop runs the actor in its published mode (`bu and td`) through the batched HIP forward instead
+(smp_hip.HipSmpActor, csrc/smp_actor.hip; `_Tree` below stays the one source of its schedule).  The no-grad target chain of an update (td3.Agent.update_targets: target actor and twin
 target critic, both `bu and td`) runs on the same kernels through `hip_handle()` (smp_hip.HipSmpTargets): the handle a module
 caches is per-process device state and is dropped whenever the module is pickled or deep-copied.  The `td`-only ablation has no
 HIP path.  Outputs are pinned to fixtures produced by executing the reference's own modules (tests/golden/smp_forward.npz,
@@ -20,6 +23,9 @@ tools/capture_golden_smp.py).
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from . import train_ops
+from .swat_policy import _TrainKernelsSwitch
 
 
 class MLPBase(nn.Module):
@@ -119,7 +125,53 @@ class _Tree(object):
         self.parents = parents
 
 
-class _GraphModule(nn.Module):
+class _LevelPlan(object):
+    """What the level-tensor path (`train_kernels`) reads off a _Tree, built once per morphology (_GraphModule._level_plan):
+    `perm` (the limbs in level order) and `inv` (where limb i stands in it), `sizes` (limbs per level), and per level the two gather tables of
+    train_ops.smp_gather over positions WITHIN the neighbouring level -- every child of a level-d limb lies in level d + 1, every parent
+    in level d - 1, so both directions gather from ONE tensor per level:
+      up[d]    [n_d, max_children]: the children's up messages (source: level d + 1, 32 wide), -1 where _Tree.children has -1;
+      down[d]  [n_d, 1]: the parent's outgoing message (source: level d - 1), columns slot * msg_dim .. of it, -1 at a root."""
+
+    def __init__(self, tree, msg_dim, max_children):
+        self.sizes = [len(lv) for lv in tree.levels]
+        self.perm = [i for lv in tree.levels for i in lv]
+        pos = {}
+        for lv in tree.levels:
+            for k, i in enumerate(lv):
+                pos[i] = k
+        self.inv = [0] * tree.L
+        for k, i in enumerate(self.perm):
+            self.inv[i] = k
+        self.up, self.down = [], []
+        for lv in tree.levels:
+            self.up.append(train_ops.SmpTable([[pos[c] if c >= 0 else -1 for c in tree.children[i]] for i in lv],
+                                              [[0] * max_children for _ in lv]))
+            self.down.append(train_ops.SmpTable([[pos[tree.parents[i]] if tree.parents[i] >= 0 else -1] for i in lv],
+                                                [[tree.slot[i] * msg_dim if tree.parents[i] >= 0 else 0] for i in lv]))
+        # what the kernels hold (include/sgrl_train.h); a morphology outside it keeps the PyTorch path
+        self.fits = msg_dim == train_ops.SMP_MSG and 1 <= max_children <= train_ops.SMP_MAX_CHILDREN and \
+            max(self.sizes) <= train_ops.SMP_MAX_LIMBS and all(t.one_reader for t in self.up + self.down) and \
+            all(t.max_off + msg_dim <= msg_dim * max_children for t in self.down)
+        self._index = {}
+
+    def index(self, device):
+        """(perm, inv) as index tensors on `device`, made once."""
+        key = str(device)
+        if key not in self._index:
+            self._index[key] = (torch.tensor(self.perm, dtype=torch.long, device=device), torch.tensor(self.inv, dtype=torch.long, device=device))
+        return self._index[key]
+
+
+def _mlp_base(base, x, slot=None):
+    """MLPBase.forward on train_ops.linear: each ReLU output feeds one layer, so its mask is applied once, in the epilogue of that
+    layer's input gradient (train_ops.linear premasked / x_relu)."""
+    h = train_ops.linear(x, base.l1.weight, base.l1.bias, relu=True, premasked=True, slot=slot)
+    h = train_ops.linear(h, base.l2.weight, base.l2.bias, relu=True, premasked=True, x_relu=True)
+    return train_ops.linear(h, base.l3.weight, base.l3.bias, x_relu=True)
+
+
+class _GraphModule(_TrainKernelsSwitch, nn.Module):
     def _init_common(self, state_dim, action_dim, msg_dim, batch_size, max_children, disable_fold, td, bu):
         if not disable_fold:
             raise NotImplementedError("the torchfold path of the reference is not rebuilt: construct with disable_fold=True "
@@ -134,11 +186,61 @@ class _GraphModule(nn.Module):
         self.parents = [-1]
         self._tree = _Tree(self.parents, max_children)
         self._smp_hip = None
+        self._plan = None
 
     def __getstate__(self):
         d = self.__dict__.copy()
         d["_smp_hip"] = None      # per-process device handle: never pickled / deep-copied with the module
+        d["_plan"] = None         # derived from the trees (holds per-device index tensors): rebuilt on first use
         return d
+
+    def _level_plan(self):
+        """The _LevelPlan of the current morphology; kept per parents list, so that a trainer cycling through its morphologies builds
+        each plan (and uploads its two index tensors) once."""
+        plans = self.__dict__.get("_plan")
+        if plans is None or len(plans) > 64:
+            plans = self._plan = {}
+        key = tuple(self.parents)
+        if key not in plans:
+            plans[key] = _LevelPlan(self._tree, self.msg_dim, self.max_children)
+        return plans[key]
+
+    def _kernel_pass(self, *inputs):
+        """True when this pass takes the level-tensor path: the switch is on, the mode is the published one, the training kernels run
+        for these inputs (GPU, float32, autograd recording) and hold this morphology."""
+        if not (self.train_kernels and self.bu and self.td):
+            return False
+        return train_ops._on_device_with_grad(*inputs, *self.parameters()) and self._level_plan().fits
+
+    def _up_levels(self, h1, plan):
+        """Bottom-up over whole levels: h1 [L, B, 64] = fc1 of every limb, in level order -> the up messages per level [n_d, B, 32]."""
+        mod = self.sNet[0]
+        parts = h1.split(plan.sizes)
+        ups = [None] * len(parts)
+        for d in reversed(range(len(parts))):
+            g = train_ops.smp_gather(parts[d], ups[d + 1] if d + 1 < len(parts) else None, plan.up[d], normalize=True, act_tanh=True)
+            ups[d] = train_ops.smp_up_tail(train_ops.linear(g, mod.fc2.weight, mod.fc2.bias), mod.fc3.weight, mod.fc3.bias)
+        return ups
+
+    def _down_levels(self, ups, plan, heads, heads_read_xm):
+        """Top-down over whole levels.  heads(d, xm, slot, down) is called per level with the previous level's outgoing messages
+        `down` [n_(d-1), B, 32 max_children] (None at the root level) and, if heads_read_xm, xm = tanh([up | parent message slot])
+        [n_d, B, 64], the input of msg_base: an alias for ONE train_ops.linear consumer, with its fan-out slot.  The last level's
+        outgoing messages are never read and not computed (nor is xm there when only msg_base reads it)."""
+        down = None
+        D = len(ups)
+        for d in range(D):
+            last = d == D - 1
+            xm = slot = None
+            if heads_read_xm or not last:
+                xm = train_ops.smp_gather(ups[d], down, plan.down[d], normalize=False, act_tanh=True)
+            if heads_read_xm and not last:          # two consumers, both linear layers: their input gradients meet in one buffer
+                slot, (xm, xm_msg) = train_ops.fan_out(xm, 2)
+            else:
+                xm_msg = xm
+            heads(d, xm, slot, down)
+            if not last:
+                down = train_ops.normalize_rows(_mlp_base(self._msg_base(), xm_msg, slot))
 
     def hip_handle(self):
         """The module's smp_hip.HipSmpActor / HipSmpCritic, created on first use (raises _lib.SgrlError without an MI355X, and
@@ -214,7 +316,26 @@ class ActorGraphPolicy(_GraphModule):
     def clear_buffer(self):
         self.action = None
 
+    def _msg_base(self):
+        return self.actor[0].msg_base
+
+    def _forward_levels(self, state):
+        """forward() on whole level tensors (train_kernels): fc1 once over all limbs, per level one gather, fc2 and the tail going up,
+        one gather and the two MLPBase chains going down; the actions return to limb order through the plan's one permutation."""
+        plan = self._level_plan()
+        perm, inv = plan.index(state.device)
+        x = self._split(state, self.state_dim).index_select(0, perm)                     # [L, B, state_dim], level order
+        up = self.sNet[0]
+        ups = self._up_levels(train_ops.linear(x, up.fc1.weight, up.fc1.bias), plan)
+        acts = []
+        self._down_levels(ups, plan, lambda d, xm, slot, down: acts.append(_mlp_base(self.actor[0].action_base, xm, slot)), True)
+        a = self.max_action * torch.tanh(torch.cat(acts).index_select(0, inv))       # [L, B, A], limb order
+        return a.transpose(0, 1).reshape(state.shape[0], -1)
+
     def forward(self, state, mode="train"):
+        if self._kernel_pass(state):
+            self.action = self._forward_levels(state)
+            return self.action
         x = self._split(state, self.state_dim)
         self._B, self._dev, self._dt = state.shape[0], state.device, state.dtype
         act = [None] * self.num_limbs
@@ -251,7 +372,37 @@ class CriticGraphPolicy(_GraphModule):
     def clear_buffer(self):
         self.x1 = self.x2 = None
 
+    def _msg_base(self):
+        return self.critic[0].msg_base
+
+    def _run_levels(self, state, action, twin):
+        """_run() on whole level tensors (train_kernels).  The Q heads read the RAW [up | action | parent message slot]: the parent's slot
+        comes from the same gather without an own part or tanh; the per-limb values are summed in level order."""
+        plan = self._level_plan()
+        perm, _ = plan.index(state.device)
+        x = self._split(state, self.state_dim).index_select(0, perm)
+        u = self._split(action, self.action_dim).index_select(0, perm)
+        up, crit = self.sNet[0], self.critic[0]
+        ups = self._up_levels(train_ops.linear(torch.cat([x, u], dim=-1), up.fc1.weight, up.fc1.bias), plan)
+        us = u.split(plan.sizes)
+        q1, q2 = [], []
+
+        def heads(d, xm, slot, down):
+            m = train_ops.smp_gather(None, down, plan.down[d], batch=state.shape[0]) if down is not None else \
+                torch.zeros((plan.sizes[d], state.shape[0], self.msg_dim), device=state.device, dtype=state.dtype)
+            xum = torch.cat([ups[d], us[d], m], dim=-1)
+            q1.append(_mlp_base(crit.baseQ1, xum))
+            if twin:
+                q2.append(_mlp_base(crit.baseQ2, xum))
+        self._down_levels(ups, plan, heads, False)
+        B = state.shape[0]
+        self.x1 = torch.cat(q1).sum(dim=0).reshape(B, -1)
+        self.x2 = torch.cat(q2).sum(dim=0).reshape(B, -1) if twin else None
+        return self.x1, self.x2
+
     def _run(self, state, action, twin):
+        if self._kernel_pass(state, action):
+            return self._run_levels(state, action, twin)
         x, u = self._split(state, self.state_dim), self._split(action, self.action_dim)
         self._B, self._dev, self._dt = state.shape[0], state.device, state.dtype
         L = self.num_limbs

@@ -298,10 +298,14 @@ MLP_HIP_OPTIM_DEFAULT = False
 # loss through critic.Q1(actor(obs))) on the training kernels of train_ops (swat_policy `train_kernels`) when the caller does not say:
 # opt-in until a SWAT learning curve has been re-run with it (tools/swat_update_bench.py)
 SWAT_TRAIN_KERNELS_DEFAULT = False
+# The same for an smp + smp agent in its published mode (td and bu; smp_policy `train_kernels`): opt-in, no SMP learning curve has
+# been run with it (tools/smp_update_bench.py)
+SMP_TRAIN_KERNELS_DEFAULT = False
 
 
 class Agent(nn.Module):
-    def __init__(self, args, device=None, use_hip=True, mlp_hip_grads=None, mlp_hip_optim=None, swat_train_kernels=None):
+    def __init__(self, args, device=None, use_hip=True, mlp_hip_grads=None, mlp_hip_optim=None, swat_train_kernels=None,
+                 smp_train_kernels=None):
         super().__init__()
         self.args = args
         atype, ctype = getattr(args, "actor_type", "set"), getattr(args, "critic_type", "set")
@@ -369,6 +373,14 @@ class Agent(nn.Module):
         # the same for SMP actor AND critic in the published mode (td and bu; smp_hip.HipSmpTargets); the td-only mode stays PyTorch
         self.use_smp_hip = bool(use_hip) and atype == "smp" and ctype == "smp" and bool(args.td) and bool(args.bu)
         self._smp_targets = None
+        # smp_train_kernels: the ONLINE smp actor and critic differentiate on the training kernels (smp_policy `train_kernels`); None:
+        # args.smp_train_kernels, then SMP_TRAIN_KERNELS_DEFAULT.  Takes effect only where the HIP target chain does (use_smp_hip);
+        # applied after set_swat_train_kernels above, which leaves every switch of a non-swat agent off
+        if smp_train_kernels is None:
+            smp_train_kernels = getattr(args, "smp_train_kernels", None)
+        if smp_train_kernels is None:
+            smp_train_kernels = SMP_TRAIN_KERNELS_DEFAULT
+        self.set_smp_train_kernels(smp_train_kernels)
         # and for the monolithic MLP pair: the whole chain is ONE launch (mlp_hip.HipMlpTargets).  The handles do not hold: every
         # chain packs from the live target parameters, so soft updates and load_state_dict need no notification
         self.use_mlp_hip = bool(use_hip) and atype == "mlp" and ctype == "mlp"
@@ -398,6 +410,15 @@ class Agent(nn.Module):
         for net in (self.actor, self.critic):
             if hasattr(type(net), "train_kernels"):
                 net.train_kernels = self.use_swat_train_kernels
+
+    def set_smp_train_kernels(self, on):
+        """Turn the training kernels of the online smp networks on or off: only an smp + smp agent with the HIP target chain (td and
+        bu, use_hip) has them; the targets stay off."""
+        from .smp_policy import _GraphModule
+        self.use_smp_train_kernels = bool(on) and bool(self.use_smp_hip)
+        for net in (self.actor, self.critic):
+            if isinstance(net, _GraphModule):
+                net.train_kernels = self.use_smp_train_kernels
 
     def __getstate__(self):
         d = self.__dict__.copy()
@@ -694,6 +715,7 @@ class GraphedUpdates(object):
         agent.use_swat_hip = False
         agent.set_swat_train_kernels(False)      # graphed SWAT agents stay plain PyTorch throughout, as before
         agent.use_smp_hip = False
+        agent.set_smp_train_kernels(False)       # and graphed SMP agents: the switch goes off together with the HIP target chain
         for opt in (agent.actor_optimizer, agent.critic_optimizer):
             if opt.state:
                 raise RuntimeError("switch to graphed updates before the first optimizer step (Adam's step counters must be device tensors)")

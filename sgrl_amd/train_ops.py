@@ -54,6 +54,12 @@ def _L():
         L.sgrl_embed3_backward.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
         L.sgrl_add_ln_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ctypes.c_float, vp]
         L.sgrl_add_ln_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp]
+        L.sgrl_smp_gather_forward.argtypes = [vp, ci, ci, vp, ci, ci, vp, vp, ci, ci, vp, vp, ci, ci, vp]
+        L.sgrl_smp_gather_backward.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, ci, ci, vp, vp, ci, ci, vp]
+        L.sgrl_smp_up_tail_forward.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp]
+        L.sgrl_smp_up_tail_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, vp]
+        L.sgrl_row_normalize_forward.argtypes = [vp, vp, vp, ci, ci, vp]
+        L.sgrl_row_normalize_backward.argtypes = [vp, vp, vp, vp, ci, ci, vp]
         L.sgrl_train_ws_floats.restype = ctypes.c_int64
         L.sgrl_train_last_error.restype = ctypes.c_char_p
         _bound = True
@@ -923,3 +929,202 @@ def embed3(embeddings, positional_indices):
             ent = _idx3_cache[key] = (torch.stack(list(positional_indices)).contiguous(), list(positional_indices))
         return _Embed3Fn.apply(ent[0], ws[0], ws[1], ws[2])
     return torch.cat([emb(idx) for emb, idx in zip(embeddings, positional_indices)], dim=1)
+
+
+# ---- SMP networks (smp_policy `train_kernels`; csrc/smp_train.hip) -----------------------------------------------------------------
+SMP_MAX_LIMBS, SMP_MAX_CHILDREN, SMP_MSG = 16, 8, 32      # SGRL_SMP_MAX_LIMBS / SGRL_SMP_MAX_CHILDREN (include/sgrl_smp.h), message width
+
+
+class SmpTable(object):
+    """The gather table of one tree level (include/sgrl_train.h sgrl_smp_gather_forward): node [n, S] = the row block of the source
+    segment s of limb j comes from (-1: zeros), off [n, S] = its first column.  Host int32 arrays, built once per morphology by
+    smp_policy from its _Tree; the kernels receive them in their arguments.  `one_reader`: no two entries read the same 32 columns
+    of the same node -- what lets the backward write the source's gradient with plain stores (the kernels run only then)."""
+
+    def __init__(self, node, off):
+        self.node = np.ascontiguousarray(np.asarray(node, dtype=np.int32))
+        self.off = np.ascontiguousarray(np.asarray(off, dtype=np.int32))
+        assert self.node.ndim == 2 and self.node.shape == self.off.shape
+        self.n, self.S = self.node.shape
+        read = [(int(a), int(o)) for a, o in zip(self.node.ravel(), self.off.ravel()) if a >= 0]
+        self.one_reader = len(set(read)) == len(read)
+        self.max_node = max([a for a, _ in read], default=-1)
+        self.max_off = max([o for _, o in read], default=0)
+        self.aligned = all(o >= 0 and o % SMP_MSG == 0 for _, o in read)
+
+
+class _SmpGatherFn(torch.autograd.Function):
+    """own [n, B, W0] or None, src [n_src, B, Wsrc] or None -> act([own' | segments]) [n, B, W0 + 32 S]: one launch forward, one
+    backward (csrc/smp_train.hip k_smp_gather_fwd / k_smp_gather_bwd)."""
+
+    @staticmethod
+    def forward(ctx, own, src, tab, normalize, act_tanh, B):
+        L = _L()
+        ref = own if own is not None else src
+        n, S = tab.n, tab.S
+        W0 = 0 if own is None else own.shape[-1]
+        own_c = None if own is None else (own if own.is_contiguous() else own.contiguous())
+        src_c = None if src is None else (src if src.is_contiguous() else src.contiguous())
+        n_src, Wsrc = (0, 0) if src is None else (src.shape[0], src.shape[-1])
+        normalize = bool(normalize) and W0 > 0
+        out = torch.empty((n, B, W0 + SMP_MSG * S), dtype=torch.float32, device=ref.device)
+        inv = torch.empty((n, B), dtype=torch.float32, device=ref.device) if normalize else None
+        st = ctypes.c_void_p(torch.cuda.current_stream(ref.device).cuda_stream)
+        _check(L, L.sgrl_smp_gather_forward(_p(own_c), W0, 1 if normalize else 0, _p(src_c), n_src, Wsrc, ctypes.c_void_p(tab.node.ctypes.data),
+                                            ctypes.c_void_p(tab.off.ctypes.data), S, 1 if act_tanh else 0, _p(out), _p(inv), n, B, st),
+               "sgrl_smp_gather_forward")
+        ctx.save_for_backward(own_c if normalize else None, inv, out if act_tanh else None)
+        ctx.tab, ctx.normalize, ctx.act, ctx.B, ctx.W0 = tab, normalize, bool(act_tanh), B, W0
+        ctx.own_shape = None if own is None else own.shape
+        ctx.src_shape = None if src is None else src.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        L = _L()
+        own, inv, out = ctx.saved_tensors
+        tab, B, W0 = ctx.tab, ctx.B, ctx.W0
+        d = d_out if d_out.is_contiguous() else d_out.contiguous()
+        need_own = ctx.own_shape is not None and ctx.needs_input_grad[0]
+        need_src = ctx.src_shape is not None and ctx.needs_input_grad[1]
+        d_own = torch.empty((tab.n, B, W0), dtype=torch.float32, device=d.device) if need_own else None
+        d_src = torch.empty(tuple(ctx.src_shape), dtype=torch.float32, device=d.device) if need_src else None
+        n_src, Wsrc = (0, 0) if ctx.src_shape is None else (ctx.src_shape[0], ctx.src_shape[-1])
+        st = ctypes.c_void_p(torch.cuda.current_stream(d.device).cuda_stream)
+        if need_own or need_src:
+            _check(L, L.sgrl_smp_gather_backward(_p(d), _p(out), _p(own), _p(inv), W0, 1 if ctx.normalize else 0, n_src, Wsrc,
+                                                 ctypes.c_void_p(tab.node.ctypes.data), ctypes.c_void_p(tab.off.ctypes.data), tab.S,
+                                                 1 if ctx.act else 0, _p(d_own), _p(d_src), tab.n, B, st), "sgrl_smp_gather_backward")
+        return (None if d_own is None else d_own.view(ctx.own_shape)), d_src, None, None, None, None
+
+
+def smp_gather(own, src, tab, normalize=False, act_tanh=False, batch=None):
+    """The input of one tree level's shared module, rows [n, B, .] (n = tab.n limbs): act([own' | seg_0 | ... | seg_{S-1}]) with
+    own' = F.normalize(own) or own (own None: no own part), seg_s = src[tab.node[j, s], :, tab.off[j, s] : + 32] or zeros (node -1, or
+    src None), act = tanh or the identity.  One launch forward and one backward when autograd records on the GPU and the shapes are the
+    kernels' (own 32 or 64 wide, at most 16 limbs and 8 segments, src a multiple of 32 up to 256 wide, every source segment read at
+    most once); smp_policy's own operations -- zeros, slices, cat, stack, F.normalize, cat, tanh, in that order -- otherwise."""
+    ref = own if own is not None else src
+    n, S = tab.n, tab.S
+    B = int(batch) if ref is None else ref.shape[1]
+    if ref is not None and B > 0 and 1 <= n <= SMP_MAX_LIMBS and 1 <= S <= SMP_MAX_CHILDREN and tab.one_reader and tab.aligned \
+            and (own is None or (own.dim() == 3 and own.shape[0] == n and own.shape[-1] in (32, 64))) \
+            and (src is None or (src.dim() == 3 and src.shape[1] == B and 1 <= src.shape[0] <= SMP_MAX_LIMBS and src.shape[-1] % SMP_MSG == 0
+                                 and SMP_MSG <= src.shape[-1] <= SMP_MSG * SMP_MAX_CHILDREN and tab.max_node < src.shape[0]
+                                 and tab.max_off + SMP_MSG <= src.shape[-1])) \
+            and (src is None or own is None or (src.dtype == own.dtype and src.device == own.device)) and _on_device_with_grad(ref, own, src):
+        return _SmpGatherFn.apply(own, src, tab, bool(normalize), bool(act_tanh), B)
+    rows = []
+    if ref is None:
+        raise ValueError("smp_gather: neither an own part nor a source")
+    zero = torch.zeros((B, SMP_MSG), device=ref.device, dtype=ref.dtype)
+    for j in range(n):
+        segs = []
+        for s in range(S):
+            a, o = int(tab.node[j, s]), int(tab.off[j, s])
+            segs.append(src[a][:, o:o + SMP_MSG] if (a >= 0 and src is not None) else zero)
+        rows.append(torch.cat(segs, dim=-1) if S > 1 else segs[0])
+    m = torch.stack(rows)
+    if own is not None:
+        m = torch.cat([F.normalize(own, dim=-1) if normalize else own, m], dim=-1)
+    return torch.tanh(m) if act_tanh else m
+
+
+class _SmpUpTailFn(torch.autograd.Function):
+    """a [..., 64] -> F.normalize(fc3(tanh(a))) [..., 32]: one launch forward, one backward (csrc/smp_train.hip k_smp_up_tail_*); fc3's
+    weight / bias gradients go through sgrl_linear_wgrad_group with (dy = dz, x = tanh(a)), postponed under deferred_wgrads exactly as
+    a leaf _LinearFn layer's."""
+
+    @staticmethod
+    def forward(ctx, a, weight, bias):
+        L = _L()
+        a2 = a.reshape(-1, 64)
+        a2 = a2 if a2.is_contiguous() else a2.contiguous()
+        w = weight if weight.is_contiguous() else weight.contiguous()
+        R = a2.shape[0]
+        t = torch.empty((R, 64), dtype=torch.float32, device=a.device)
+        u = torch.empty((R, 32), dtype=torch.float32, device=a.device)
+        inv = torch.empty((R,), dtype=torch.float32, device=a.device)
+        st = ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
+        _check(L, L.sgrl_smp_up_tail_forward(_p(a2), _p(w), _p(bias), _p(t), _p(u), _p(inv), R, st), "sgrl_smp_up_tail_forward")
+        ctx.save_for_backward(t, u, inv, w)
+        ctx.leaf = (weight, bias) if (weight.is_leaf and bias.is_leaf) else None
+        ctx.a_shape = a.shape
+        return u.view(*a.shape[:-1], 32)
+
+    @staticmethod
+    def backward(ctx, du):
+        L = _L()
+        t, u, inv, w = ctx.saved_tensors
+        R = t.shape[0]
+        d = du.reshape(R, 32)
+        d = d if d.is_contiguous() else d.contiguous()
+        dev = d.device
+        dz = torch.empty((R, 32), dtype=torch.float32, device=dev)
+        da = torch.empty((R, 64), dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(L, L.sgrl_smp_up_tail_backward(_p(d), _p(u), _p(inv), _p(t), _p(w), _p(dz), _p(da), R, ctypes.c_void_p(stream)),
+               "sgrl_smp_up_tail_backward")
+        need_w, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        dw = db = None
+        deferred = False
+        if need_w or need_b:
+            dw = torch.empty((32, 64), dtype=torch.float32, device=dev)
+            db = torch.empty((32,), dtype=torch.float32, device=dev) if need_b else None
+            deferred = _pending is not None and ctx.leaf is not None
+            rec = {"dy": dz, "y": None, "rowdiv": None, "x": t, "dw": dw, "db": db, "M": R, "N": 32, "K": 64, "relu": False, "dev": dev,
+                   "stream": stream, "ldy": 32, "w_param": (ctx.leaf[0] if need_w else None) if deferred else None, "fold_param": None,
+                   "b_param": (ctx.leaf[1] if need_b else None) if deferred else None}
+            if deferred:
+                _pending.append(rec)
+            else:
+                flush_wgrads([rec])
+        return (da.view(ctx.a_shape) if ctx.needs_input_grad[0] else None), (None if deferred or not need_w else dw), (None if deferred else db)
+
+
+def smp_up_tail(a, weight, bias):
+    """F.normalize(F.linear(torch.tanh(a), weight, bias), dim=-1) for fc3 [32, 64] of the SMP bottom-up modules (a = fc2's output): one
+    launch forward and one backward when autograd records on the GPU; those three operations otherwise."""
+    if a.shape[-1] == 64 and tuple(weight.shape) == (32, 64) and bias is not None and tuple(bias.shape) == (32,) and a.numel() > 0 \
+            and _on_device_with_grad(a, weight, bias):
+        return _SmpUpTailFn.apply(a, weight, bias)
+    return F.normalize(F.linear(torch.tanh(a), weight, bias), dim=-1)
+
+
+class _NormalizeRowsFn(torch.autograd.Function):
+    """F.normalize(x, dim=-1) for rows up to 256 wide: one launch forward, one backward (csrc/smp_train.hip k_row_norm_*)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        L = _L()
+        W = x.shape[-1]
+        x2 = x.reshape(-1, W)
+        x2 = x2 if x2.is_contiguous() else x2.contiguous()
+        R = x2.shape[0]
+        y = torch.empty((R, W), dtype=torch.float32, device=x.device)
+        inv = torch.empty((R,), dtype=torch.float32, device=x.device)
+        st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        _check(L, L.sgrl_row_normalize_forward(_p(x2), _p(y), _p(inv), R, W, st), "sgrl_row_normalize_forward")
+        ctx.save_for_backward(y, inv)
+        ctx.x_shape = x.shape
+        return y.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        L = _L()
+        y, inv = ctx.saved_tensors
+        R, W = y.shape
+        d = dy.reshape(R, W)
+        d = d if d.is_contiguous() else d.contiguous()
+        dx = torch.empty_like(y)
+        st = ctypes.c_void_p(torch.cuda.current_stream(d.device).cuda_stream)
+        _check(L, L.sgrl_row_normalize_backward(_p(d), _p(y), _p(inv), _p(dx), R, W, st), "sgrl_row_normalize_backward")
+        return dx.view(ctx.x_shape)
+
+
+def normalize_rows(x):
+    """F.normalize(x, dim=-1): one launch forward and one backward when autograd records on the GPU and the rows are at most 256
+    (32 x SGRL_SMP_MAX_CHILDREN) wide; F.normalize itself otherwise."""
+    if x.dim() >= 2 and 1 <= x.shape[-1] <= SMP_MSG * SMP_MAX_CHILDREN and x.numel() > 0 and _on_device_with_grad(x):
+        return _NormalizeRowsFn.apply(x)
+    return F.normalize(x, dim=-1)

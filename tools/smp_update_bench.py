@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Timing of the HIP SMP twin critic forward and of an eager TD3 update of an SMP agent with / without the HIP target chain.
+"""Timing of the HIP SMP twin critic forward and of an eager TD3 update of an SMP agent with / without the HIP target chain and
+with its differentiable passes on the training kernels.
 
 usage: smp_update_bench.py forward [config3|config5] [reps=60]
-       smp_update_bench.py update [morphology=3d_walker_7_full] [hip|pytorch|auto] [updates=40]
+       smp_update_bench.py update [morphology=3d_walker_7_full] [hip|pytorch|auto|kernels] [updates=40]
   forward  twin critic forward (smp_hip.HipSmpCritic, both heads, max_children 5) over the 8 walker variants x 1024 environments
            (config3) or one GPU's share of 3D_CWHH++ (config5: 23 morphologies, 8188 environments), against the PyTorch path
            (per morphology: change_morphology + CriticGraphPolicy.forward under no_grad).  Device events around each forward,
@@ -10,7 +11,8 @@ usage: smp_update_bench.py forward [config3|config5] [reps=60]
   update   one eager Agent.update (td3.py) of an SMP agent (td and bu, max_children 5) at batch 256 on one morphology: 8 untimed
            updates, then `updates` timed ones (host clock around update + device synchronisation; every second update includes
            the delayed actor step, as in training).  `hip`: the target chain on HIP (Agent(use_hip=True)); `pytorch`:
-           Agent(use_hip=False); `auto`: the build's default.  The pytorch / auto arms use no API newer than Agent.update, so
+           Agent(use_hip=False); `auto`: the build's default; `kernels`: the HIP target chain AND the differentiable passes on the
+           training kernels (Agent(smp_train_kernels=True)).  The pytorch / auto arms use no API newer than Agent.update, so
            this mode also runs on a checkout that has no HIP target chain (SGRL_BENCH_TREE=<checkout> times its package).
 Prints one JSON line per run.
 """
@@ -106,7 +108,10 @@ def update(name, arm, updates):
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     args = default_train_args(actor_type="smp", critic_type="smp", td=True, bu=True, max_children=MC)
-    agent = Agent(args, device=dev) if arm == "auto" else Agent(args, device=dev, use_hip=(arm == "hip"))
+    if arm == "kernels":
+        agent = Agent(args, device=dev, smp_train_kernels=True)
+    else:
+        agent = Agent(args, device=dev) if arm == "auto" else Agent(args, device=dev, use_hip=(arm == "hip"))
     g = G.getGraphDict(mjcf.load_asset(name).parents, TRAV, [], device=dev)
     L, B = len(g["parents"]), 256
     agent.change_morphology(g)
@@ -131,6 +136,7 @@ def update(name, arm, updates):
     print(json.dumps({"mode": "update", "morphology": name, "limbs": L, "batch": B, "arm": arm,
                       "tree": os.environ.get("SGRL_BENCH_TREE", "this"),
                       "hip_target_chain": getattr(agent, "_smp_targets", None) is not None,
+                      "train_kernels": bool(getattr(agent, "use_smp_train_kernels", False)),
                       "update_ms_mean": round(float(ms.mean()), 4), "update_ms_median": round(float(np.median(ms)), 4),
                       "update_ms_min": round(float(ms.min()), 4), "update_ms_max": round(float(ms.max()), 4),
                       "critic_only_ms_median": round(float(np.median(ms[1::2])), 4),
