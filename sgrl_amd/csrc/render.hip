@@ -1,6 +1,7 @@
 // render.hip -- ray caster behind BatchedModularVecEnv.get_images() (C ABI: include/sgrl_render.h).  One thread per pixel,
 // 16 x 16 pixel workgroups, the image's geom list (<= 64 records) staged in LDS; nearest hit over plane / spheres / capsules,
-// Lambert shading from a head light plus ambient, checker pattern on the ground plane.  A visualisation aid: no parity claim.
+// Lambert shading from a head light plus ambient, checker pattern on the ground plane.  A visualisation aid: no parity claim with
+// MuJoCo's renderer; held to its own definition by tests/render_restate.py (float64) in tests/test_render_gpu.py.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -19,7 +20,7 @@ __global__ __launch_bounds__(256) void k_render(const float* __restrict__ geoms,
   __shared__ float G[kMaxGeoms * SGRL_RENDER_GEOM_FLOATS];
   __shared__ float C[SGRL_RENDER_CAM_FLOATS];
   const int img = blockIdx.z, t = threadIdx.y * 16 + threadIdx.x;
-  const int ng = min(n_geoms[img], kMaxGeoms);
+  const int ng = min(n_geoms[img], min(max_geoms, kMaxGeoms));   // the counts live on the device: never past the image's own records
   for (int i = t; i < ng * SGRL_RENDER_GEOM_FLOATS; i += 256) G[i] = geoms[((size_t)img * max_geoms) * SGRL_RENDER_GEOM_FLOATS + i];
   if (t < SGRL_RENDER_CAM_FLOATS) C[t] = cams[(size_t)img * SGRL_RENDER_CAM_FLOATS + t];
   __syncthreads();
