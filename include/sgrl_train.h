@@ -223,6 +223,26 @@ int sgrl_smp_up_tail_backward(const float* du, const float* u, const float* inv,
 int sgrl_row_normalize_forward(const float* x, float* y, float* inv, int R, int W, void* stream);
 int sgrl_row_normalize_backward(const float* dy, const float* y, const float* inv, float* dx, int R, int W, void* stream);
 
+/* ---- the losses of a TD3 update (sgrl_amd/td3.py Agent `loss_kernels`; csrc/td3_loss.hip) ---------------------------------------
+ * Replaces, with one launch per call, the loss expressions of reference src/agent.py:150-176 and the autograd nodes behind them:
+ *   critic_loss = F.mse_loss(current_Q1, target_Q) + F.mse_loss(current_Q2, target_Q)     (two reductions, an addition; five
+ *                                                                                           element-wise launches going back)
+ *   actor_loss  = -self.critic.Q1(obs_batch, self.actor(obs_batch)).mean()                 (a reduction, a negation; three back)
+ * over n contiguous float32 elements each, n >= 1 (64-bit indices):
+ *   d_k[i] = (double) q_k[i] - (double) target[i],  loss = (float)((sum d_1^2 + sum d_2^2) / n),
+ *   dq_k[i] = (float)((double) g[0] * 2 d_k[i] / n);       neg_mean: loss = (float)(-sum q / n),  dq[i] = (float)(-(double) g[0] / n).
+ * The forward reductions run in ONE workgroup of 256 threads: each sums its elements i = t (mod 256) in ascending order in
+ * float64, a fixed-shape tree in LDS adds the 256 partial sums: no atomics, no scratch, the same bits run to run.  The backward
+ * kernels are element-wise and write dq[0 .. n) only.  loss and g are DEVICE scalars: the host reads neither, so every call can be
+ * recorded into a hipGraph.  A null pointer, n <= 0, or q1 / q2 / dq1 / dq2 overlapping target return SGRL_ERR_ARG before anything
+ * touches the device. */
+int sgrl_td3_twin_mse_forward(const float* q1, const float* q2, const float* target, int64_t n, float* loss, void* stream);
+int sgrl_td3_twin_mse_backward(const float* q1, const float* q2, const float* target, int64_t n, const float* g, float* dq1, float* dq2,
+                               void* stream);
+int sgrl_td3_neg_mean_forward(const float* q, int64_t n, float* loss, void* stream);
+int sgrl_td3_neg_mean_backward(int64_t n, const float* g, float* dq, void* stream);
+int sgrl_td3_loss_launches(void);   /* 1 per call */
+
 const char* sgrl_train_last_error(void);
 
 #ifdef __cplusplus

@@ -301,18 +301,23 @@ SWAT_TRAIN_KERNELS_DEFAULT = False
 # The same for an smp + smp agent in its published mode (td and bu; smp_policy `train_kernels`): opt-in, no SMP learning curve has
 # been run with it (tools/smp_update_bench.py)
 SMP_TRAIN_KERNELS_DEFAULT = False
+# Whether a set, swat or smp agent on the GPU computes its two losses and their gradients with the loss kernels (train_ops.twin_mse /
+# neg_mean: one launch each way instead of about a dozen; float64 sums, so the last bit of a loss may differ from PyTorch's) when the
+# caller does not say: opt-in, no learning curve has been run with it
+LOSS_KERNELS_DEFAULT = False
 
 
 class Agent(nn.Module):
     def __init__(self, args, device=None, use_hip=True, mlp_hip_grads=None, mlp_hip_optim=None, swat_train_kernels=None,
-                 smp_train_kernels=None):
+                 smp_train_kernels=None, loss_kernels=None):
         super().__init__()
         self.args = args
         atype, ctype = getattr(args, "actor_type", "set"), getattr(args, "critic_type", "set")
         if atype not in ("set", "swat", "smp", "mlp") or ctype not in ("set", "swat", "smp", "mlp"):
             raise NotImplementedError("actor / critic types 'set', 'swat', 'smp' and 'mlp' are built (the actors with a batched HIP forward for "
-                                      "collection, smp in its td and bu mode; the target chain of a swat, an smp (td and bu) or an mlp update on HIP, the "
-                                      "rest of those updates in PyTorch); got actor_type %r, critic_type %r"
+                                      "collection, smp in its td and bu mode; the target chain of a swat, an smp (td and bu) or an mlp update on HIP, "
+                                      "the differentiable passes of those updates on the training kernels where `swat_train_kernels` / "
+                                      "`smp_train_kernels` / `mlp_hip_grads` say so, in PyTorch otherwise); got actor_type %r, critic_type %r"
                                       % (atype, ctype))
         if (atype == "mlp") != (ctype == "mlp"):
             raise NotImplementedError("an 'mlp' actor goes with an 'mlp' critic only (got actor_type %r, critic_type %r): the monolithic "
@@ -402,6 +407,15 @@ class Agent(nn.Module):
             mlp_hip_optim = MLP_HIP_OPTIM_DEFAULT
         self.use_mlp_hip_optim = self.use_mlp_hip_grads and bool(mlp_hip_optim)
         self._mlp_optim = None
+        # loss_kernels: the critic loss and the actor loss of update_finish, and their gradients, on the loss kernels (train_ops.twin_mse
+        # / neg_mean); None: args.loss_kernels, then LOSS_KERNELS_DEFAULT.  Follows use_hip; an mlp agent ignores it (its gradient half
+        # has losses of its own).  An Agent switch, not one of GraphedUpdates: an eager and a graphed agent with the same switches run
+        # the same arithmetic
+        if loss_kernels is None:
+            loss_kernels = getattr(args, "loss_kernels", None)
+        if loss_kernels is None:
+            loss_kernels = LOSS_KERNELS_DEFAULT
+        self.use_loss_kernels = bool(use_hip) and atype != "mlp" and bool(loss_kernels)
 
     def set_swat_train_kernels(self, on):
         """Turn the training kernels of the online swat networks on or off (no other agent type has the switch)."""
@@ -575,7 +589,10 @@ class Agent(nn.Module):
                       skip_unused_critic_grads=False):
         args = self.args
         obs_batch = data_batch["obs"]
-        critic_loss = F.mse_loss(current_Q1, target_Q) + F.mse_loss(current_Q2, target_Q)
+        if self.use_loss_kernels:
+            critic_loss = train_ops.twin_mse(current_Q1, current_Q2, target_Q)
+        else:
+            critic_loss = F.mse_loss(current_Q1, target_Q) + F.mse_loss(current_Q2, target_Q)
         self.critic_optimizer.zero_grad()
         # (graphed path) the weight gradients are not on the backward pass's critical path: collected, issued together at the end
         with train_ops.deferred_wgrads(enabled=skip_unused_critic_grads):
@@ -597,7 +614,8 @@ class Agent(nn.Module):
             for p in critic_params:
                 p.requires_grad_(False)
             try:
-                actor_loss = -self.critic.Q1(obs_batch, self.actor(obs_batch)).mean()
+                actor_q = self.critic.Q1(obs_batch, self.actor(obs_batch))
+                actor_loss = train_ops.neg_mean(actor_q) if self.use_loss_kernels else -actor_q.mean()
                 self.actor_optimizer.zero_grad()
                 with train_ops.deferred_wgrads(enabled=skip_unused_critic_grads):
                     actor_loss.backward()
@@ -687,6 +705,23 @@ def _no_finalizers_during_capture():
             gc.enable()
 
 
+def target_handles(targets):
+    """The library handles behind a swat_hip.HipSwatTargets (target actor, critic.q1, critic.q2) or an smp_hip.HipSmpTargets (target
+    actor, target critic); none for None."""
+    if targets is None:
+        return []
+    c = targets.critic
+    return [targets.actor] + ([c.q1, c.q2] if hasattr(c, "q1") else [c])
+
+
+def handles_stamp(handles):
+    """What a hipGraph has baked of these handles, as a comparable tuple of plain values (duck-typed, like mlp_update_stamp): per
+    handle its `generation()` -- bumped whenever the library frees device memory a recorded forward may point into: an evicted batch
+    structure, a regrown workspace (include/sgrl_swat.h sgrl_swat_generation, include/sgrl_smp.h sgrl_smp_generation) -- and `_bound`,
+    the parameter addresses it holds: a rebinding frees nothing, but a graph carries the old addresses in its kernels' arguments."""
+    return tuple((int(h.generation()), None if h._bound is None else tuple(h._bound)) for h in handles)
+
+
 class GraphedUpdates(object):
     """`Agent.update` captured into hipGraphs (MI355X: the update is ~3 400 small launches -- PyTorch autograd through three
     SET networks at batch 100 plus the HIP target kernels -- and launch-bound when issued eagerly: 50 ms; a replay is
@@ -697,10 +732,21 @@ class GraphedUpdates(object):
     `capturable=True`, the reward statistics stay on the device.
 
     Capture rules honoured here: every (morphology, batch size) is run eagerly first (so the SET handles have cached the
-    batch structure and grown their workspace to its final size before any pointer is baked into a graph)."""
+    batch structure and grown their workspace to its final size before any pointer is baked into a graph).
 
-    def __init__(self, agent, batch_size):
+    hip_kernels=False: a SWAT or SMP agent is switched to plain PyTorch throughout (HIP target chain and training kernels off) and
+    its graphs record that.  hip_kernels=True: the agent's switches are left exactly as it was built -- a swat + swat or an smp + smp
+    (td and bu) agent then records its HIP target chain (swat_hip.HipSwatTargets / smp_hip.HipSmpTargets: every chain of the
+    former forks onto the handle's side stream, which the warm-up creates) and, with `swat_train_kernels` / `smp_train_kernels`,
+    its differentiable passes on the training kernels.  The stamp of a graph then also covers that target object's handles
+    (`handles_stamp`), and a capture is refused (RuntimeError) when the target object is not the one the slot's warm-up ran with.
+    The three-graph form (`split`) is not built for it.  `captures[(key, flag)]` counts the captures of each graph; `stale(key, flag)`
+    says, launching nothing, whether a captured graph would be dropped by the next update of that kind."""
+
+    def __init__(self, agent, batch_size, hip_kernels=False):
         self.agent, self.B = agent, int(batch_size)
+        self.hip_kernels = bool(hip_kernels)
+        self.captures = {}         # (key, flag) -> number of times that graph has been captured
         if getattr(agent.args, "actor_type", "set") == "mlp":
             raise NotImplementedError("GraphedUpdates is not built for 'mlp' agents: run their updates eagerly (DeviceTrainer(graph_updates=False))")
         dev = agent.device
@@ -711,11 +757,13 @@ class GraphedUpdates(object):
             # r6_takeoff_vendor_graphed_*); the vendor path is an A/B arm for EAGER updates, nobody has made its capture sound
             raise RuntimeError("GraphedUpdates replays this library's own training kernels: with SGRL_TRAIN_GEMM=0 (vendor kernels) run the "
                                "updates eagerly (DeviceTrainer(graph_updates=False))")
-        # the workspace stamps below follow the SET handles only: a SWAT or SMP agent's graphs record the PyTorch target chain
-        agent.use_swat_hip = False
-        agent.set_swat_train_kernels(False)      # graphed SWAT agents stay plain PyTorch throughout, as before
-        agent.use_smp_hip = False
-        agent.set_smp_train_kernels(False)       # and graphed SMP agents: the switch goes off together with the HIP target chain
+        if not self.hip_kernels:
+            # without hip_kernels the workspace stamps below follow the SET handles only: a SWAT or SMP agent's graphs record the
+            # PyTorch target chain
+            agent.use_swat_hip = False
+            agent.set_swat_train_kernels(False)      # graphed SWAT agents stay plain PyTorch throughout, as before
+            agent.use_smp_hip = False
+            agent.set_smp_train_kernels(False)       # and graphed SMP agents: the switch goes off together with the HIP target chain
         for opt in (agent.actor_optimizer, agent.critic_optimizer):
             if opt.state:
                 raise RuntimeError("switch to graphed updates before the first optimizer step (Adam's step counters must be device tensors)")
@@ -753,6 +801,41 @@ class GraphedUpdates(object):
         or is told to change the form of its tile products)."""
         return tuple((int(hh.L.sgrl_set_workspace_bytes(hh.h)), int(hh.L.sgrl_set_generation(hh.h))) for hh in self._hip_handles())
 
+    def _targets(self, sl):
+        """The object whose target chain an update on this slot records -- what `Agent._hip_targets` returns NOW (it re-creates the
+        object when a target module has been replaced) -- or None: without hip_kernels, and for agents whose chain is PyTorch."""
+        if not self.hip_kernels:
+            return None
+        return self.agent._hip_targets(sl["batch"]["next_obs"])
+
+    def _stamp(self, sl):
+        """The stamp of a graph on this slot: the SET handles' (`_workspace_stamp`) and, with hip_kernels, the SWAT / SMP target
+        handles' (`handles_stamp`: three for SWAT, two for SMP)."""
+        return (self._workspace_stamp(), handles_stamp(target_handles(self._targets(sl))))
+
+    def stale(self, key, flag):
+        """True when a graph has been captured for (key, flag) and its stamp is no longer the current one: the next update of that
+        kind drops it and captures again.  Launches nothing."""
+        sl = self.slots.get(key)
+        if sl is None or flag not in sl["graphs"]:
+            return False
+        return sl["stamp"].get(flag) != self._stamp(sl)
+
+    def _check_capture(self, sl, key):
+        """What must hold on the host before torch.cuda.graph(...) is entered for a graph on this slot."""
+        if self.hip_kernels and self.split:
+            raise RuntimeError("GraphedUpdates(hip_kernels=True) records ONE graph per update: the three-graph form is not built for the "
+                               "SWAT / SMP kernels; leave `split` False")
+        if key not in self.warmed:
+            raise RuntimeError("warm(%r, ...) every morphology before the first graphed update" % (key,))
+        if self._targets(sl) is not sl.get("targets"):
+            # a fresh target object: its handles have run nothing yet, so the capture would hold their first call -- which binds the
+            # parameters, builds the batch structure, allocates the workspace and creates the twin chain's side stream
+            # (include/sgrl_swat.h sgrl_swat_forward_twin: "make that call outside any stream capture")
+            raise RuntimeError("the agent's HIP target chain is not the one morphology %r was warmed with (a target network has been "
+                               "replaced, or the chain was switched on or off): warm(%r, ...) again before the next graphed update"
+                               % (key, key))
+
     def _load(self, sl, data_batch):
         for k, t in sl["batch"].items():
             t.copy_(data_batch[k].reshape(t.shape))
@@ -786,6 +869,8 @@ class GraphedUpdates(object):
                 outs.append(self.agent.update(sl["batch"], it, noise=sl["noise"], lazy_stats=True, skip_unused_critic_grads=True))
         torch.cuda.current_stream().wait_stream(s)
         self.warmed.add(key)
+        if outs:
+            sl["targets"] = self._targets(sl)   # (hip_kernels) whose first calls have now happened outside any capture
         return outs
 
     def update(self, key, graph, L, data_batch, it):
@@ -823,11 +908,15 @@ class GraphedUpdates(object):
         # A graph bakes the addresses of the SET handles' workspaces.  They only ever grow, and every morphology is run eagerly
         # before any capture -- but a graph captured before a LATER regrowth would fault on replay (a GPU memory fault, not an
         # exception): the workspaces' sizes are compared with those at capture time and such a graph is captured again.
-        stamp = self._workspace_stamp()
+        # With hip_kernels the same holds for the SWAT / SMP target handles: the stamp also carries their generations and bound addresses.
+        stamp = self._stamp(sl)
         owner = (id(self), key, flag)
         if flag in sl["graphs"] and sl["stamp"].get(flag) != stamp:
             del sl["graphs"][flag]
             release_tables(owner)
+        if flag not in sl["graphs"]:
+            self._check_capture(sl, key)
+            self.captures[(key, flag)] = self.captures.get((key, flag), 0) + 1
         global _capture_owner
         if flag not in sl["graphs"] and self.split:
             # Three graphs, all recorded on ONE capture stream (autograd's nodes then belong to one stream: no cross-stream
@@ -849,7 +938,7 @@ class GraphedUpdates(object):
                                                                skip_unused_critic_grads=True)
             _capture_owner = None
             sl["graphs"][flag] = gs
-            sl["stamp"][flag] = self._workspace_stamp()
+            sl["stamp"][flag] = self._stamp(sl)
         if flag not in sl["graphs"]:
             self.agent.change_morphology(graph)
             g = torch.cuda.CUDAGraph()
@@ -867,7 +956,7 @@ class GraphedUpdates(object):
             if dump:
                 g.debug_dump(os.path.join(dump, "update_%s_flag%d.dot" % (key, flag)))
             sl["graphs"][flag] = g           # capturing records the work without running it
-            sl["stamp"][flag] = self._workspace_stamp()
+            sl["stamp"][flag] = self._stamp(sl)
         g = sl["graphs"][flag]
         if isinstance(g, list):
             cur = torch.cuda.current_stream()

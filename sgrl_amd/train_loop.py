@@ -24,9 +24,11 @@ from .td3 import Agent, default_train_args
 class DeviceTrainer(object):
     def __init__(self, env_names, envs_per_morph, args=None, seed=0, device="cuda:0", max_buffer_size=1000000,
                  batch_size=None, dst=0, graph_updates=False, tune_gemms=False, rollout=None, lag_flag=True, device_sampler=False,
-                 device_noise=False, **env_kw):
+                 device_noise=False, graph_hip_kernels=False, **env_kw):
         """graph_updates: replay the TD3 update from hipGraphs (td3.GraphedUpdates; td3.GraphedMlpUpdates
-        for an `mlp` agent); tune_gemms: let PyTorch's TunableOp pick
+        for an `mlp` agent); graph_hip_kernels (with graph_updates; ignored for `mlp`): td3.GraphedUpdates(hip_kernels=True) -- a
+        swat or smp agent keeps its HIP target chain and its `*_train_kernels` switch under the graphs instead of being switched
+        to plain PyTorch; tune_gemms: let PyTorch's TunableOp pick
         the rocBLAS / hipBLASLt algorithm per GEMM shape on first use (the defaults choose 256 x 256 tiles for the 700-row
         weight-gradient GEMMs of a 100-row update: 50 -> 38 ms per update, round 1).  batch_size: rows per TD3 update, default
         args.agent_batch_size = 256 (the reference's trainer.py:289-291).  lag_flag (GPU ranks): the round-finished flag is read one
@@ -108,7 +110,8 @@ class DeviceTrainer(object):
             # an mlp agent's update is entirely library launches: one shared slot, no warm-up of its own (the first update of each
             # kind runs eagerly inside the ordinary schedule), so the (morphology, it, draw) sequence is the eager trainer's
             mlp = getattr(self.args, "actor_type", "set") == "mlp"
-            self.graphed = (GraphedMlpUpdates if mlp else GraphedUpdates)(self.agent, self.batch_size)
+            self.graphed = GraphedMlpUpdates(self.agent, self.batch_size) if mlp else \
+                GraphedUpdates(self.agent, self.batch_size, hip_kernels=bool(graph_hip_kernels))
             self._graphed_lazy = mlp
         self.begin_round()
 

@@ -1122,6 +1122,96 @@ class _NormalizeRowsFn(torch.autograd.Function):
         return dx.view(ctx.x_shape)
 
 
+def _bind_losses(L):
+    if not getattr(L, "_sgrl_td3_loss_bound", False):
+        vp, i64 = ctypes.c_void_p, ctypes.c_int64
+        L.sgrl_td3_twin_mse_forward.argtypes = [vp, vp, vp, i64, vp, vp]
+        L.sgrl_td3_twin_mse_backward.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
+        L.sgrl_td3_neg_mean_forward.argtypes = [vp, i64, vp, vp]
+        L.sgrl_td3_neg_mean_backward.argtypes = [i64, vp, vp, vp]
+        L._sgrl_td3_loss_bound = True
+    return L
+
+
+def _upstream(g):
+    """The upstream gradient of a scalar loss as the device scalar the backward kernels read."""
+    return g if g.dtype == torch.float32 else g.float()
+
+
+class _TwinMseFn(torch.autograd.Function):
+    """q1, q2, target (same shape, contiguous) -> mse(q1, target) + mse(q2, target), a 0-dim tensor: one launch forward, one
+    backward (csrc/td3_loss.hip k_twin_mse_*); target receives no gradient."""
+
+    @staticmethod
+    def forward(ctx, q1, q2, target):
+        L = _bind_losses(_L())
+        loss = torch.empty((), dtype=torch.float32, device=q1.device)
+        st = ctypes.c_void_p(torch.cuda.current_stream(q1.device).cuda_stream)
+        _check(L, L.sgrl_td3_twin_mse_forward(_p(q1), _p(q2), _p(target), q1.numel(), _p(loss), st), "sgrl_td3_twin_mse_forward")
+        ctx.save_for_backward(q1, q2, target)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        L = _bind_losses(_L())
+        q1, q2, target = ctx.saved_tensors
+        g = _upstream(g)
+        dq1, dq2 = torch.empty_like(q1), torch.empty_like(q2)
+        st = ctypes.c_void_p(torch.cuda.current_stream(q1.device).cuda_stream)
+        _check(L, L.sgrl_td3_twin_mse_backward(_p(q1), _p(q2), _p(target), q1.numel(), _p(g), _p(dq1), _p(dq2), st),
+               "sgrl_td3_twin_mse_backward")
+        return (dq1 if ctx.needs_input_grad[0] else None), (dq2 if ctx.needs_input_grad[1] else None), None
+
+
+class _NegMeanFn(torch.autograd.Function):
+    """q (contiguous) -> -q.mean(), a 0-dim tensor: one launch forward, one backward (csrc/td3_loss.hip k_neg_mean_*)."""
+
+    @staticmethod
+    def forward(ctx, q):
+        L = _bind_losses(_L())
+        loss = torch.empty((), dtype=torch.float32, device=q.device)
+        st = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+        _check(L, L.sgrl_td3_neg_mean_forward(_p(q), q.numel(), _p(loss), st), "sgrl_td3_neg_mean_forward")
+        ctx.q_shape = q.shape
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        L = _bind_losses(_L())
+        g = _upstream(g)
+        dq = torch.empty(ctx.q_shape, dtype=torch.float32, device=g.device)
+        st = ctypes.c_void_p(torch.cuda.current_stream(g.device).cuda_stream)
+        _check(L, L.sgrl_td3_neg_mean_backward(dq.numel(), _p(g), _p(dq), st), "sgrl_td3_neg_mean_backward")
+        return dq
+
+
+def _loss_kernel_inputs(*ts):
+    """The loss kernels apply: float32 tensors of one shape on one GPU, contiguous, non-empty, with autograd recording."""
+    a = ts[0]
+    return a.numel() > 0 and all(t.is_cuda and t.dtype == torch.float32 and t.device == a.device and t.shape == a.shape and
+                                 t.is_contiguous() for t in ts) and _on_device_with_grad(*ts)
+
+
+def twin_mse(q1, q2, target):
+    """F.mse_loss(q1, target) + F.mse_loss(q2, target) -- the critic loss of a TD3 update (reference agent.py:145-147): one launch
+    forward and one backward (float64 sums in a fixed order, include/sgrl_train.h sgrl_td3_twin_mse_*) when autograd records on the
+    GPU over contiguous float32 tensors of one shape; that expression itself otherwise.  `target` receives no gradient from the
+    kernels: pass a tensor that needs none (the update's target is computed under no_grad)."""
+    if not target.requires_grad and _loss_kernel_inputs(q1, q2, target):
+        return _TwinMseFn.apply(q1, q2, target)
+    return F.mse_loss(q1, target) + F.mse_loss(q2, target)
+
+
+def neg_mean(q):
+    """-q.mean() -- the actor loss of a TD3 update (reference agent.py:167): one launch forward and one backward under the
+    conditions of twin_mse; that expression itself otherwise."""
+    if _loss_kernel_inputs(q):
+        return _NegMeanFn.apply(q)
+    return -q.mean()
+
+
 def normalize_rows(x):
     """F.normalize(x, dim=-1): one launch forward and one backward when autograd records on the GPU and the rows are at most 256
     (32 x SGRL_SMP_MAX_CHILDREN) wide; F.normalize itself otherwise."""

@@ -3,7 +3,7 @@
 with its differentiable passes on the training kernels.
 
 usage: smp_update_bench.py forward [config3|config5] [reps=60]
-       smp_update_bench.py update [morphology=3d_walker_7_full] [hip|pytorch|auto|kernels] [updates=40]
+       smp_update_bench.py update [morphology=3d_walker_7_full] [hip|pytorch|auto|kernels|graphed] [updates=40]
   forward  twin critic forward (smp_hip.HipSmpCritic, both heads, max_children 5) over the 8 walker variants x 1024 environments
            (config3) or one GPU's share of 3D_CWHH++ (config5: 23 morphologies, 8188 environments), against the PyTorch path
            (per morphology: change_morphology + CriticGraphPolicy.forward under no_grad).  Device events around each forward,
@@ -12,8 +12,11 @@ usage: smp_update_bench.py forward [config3|config5] [reps=60]
            updates, then `updates` timed ones (host clock around update + device synchronisation; every second update includes
            the delayed actor step, as in training).  `hip`: the target chain on HIP (Agent(use_hip=True)); `pytorch`:
            Agent(use_hip=False); `auto`: the build's default; `kernels`: the HIP target chain AND the differentiable passes on the
-           training kernels (Agent(smp_train_kernels=True)).  The pytorch / auto arms use no API newer than Agent.update, so
-           this mode also runs on a checkout that has no HIP target chain (SGRL_BENCH_TREE=<checkout> times its package).
+           training kernels (Agent(smp_train_kernels=True)); `graphed`: that agent with the loss kernels as well (loss_kernels=True),
+           its updates replayed from hipGraphs (td3.GraphedUpdates(hip_kernels=True): two eager warm-up updates, the captures fall
+           among the untimed ones; the timed call includes filling the slot's static batch and noise).  The pytorch / auto arms use
+           no API newer than Agent.update, so this mode also runs on a checkout that has no HIP target chain
+           (SGRL_BENCH_TREE=<checkout> times its package).
 Prints one JSON line per run.
 """
 import json
@@ -110,6 +113,8 @@ def update(name, arm, updates):
     args = default_train_args(actor_type="smp", critic_type="smp", td=True, bu=True, max_children=MC)
     if arm == "kernels":
         agent = Agent(args, device=dev, smp_train_kernels=True)
+    elif arm == "graphed":
+        agent = Agent(args, device=dev, smp_train_kernels=True, loss_kernels=True)
     else:
         agent = Agent(args, device=dev) if arm == "auto" else Agent(args, device=dev, use_hip=(arm == "hip"))
     g = G.getGraphDict(mjcf.load_asset(name).parents, TRAV, [], device=dev)
@@ -122,14 +127,21 @@ def update(name, arm, updates):
         r = lambda *s: torch.rand(s, device=dev, generator=gen)
         batches.append({"obs": torch.randn((B, 41 * L), device=dev, generator=gen), "next_obs": torch.randn((B, 41 * L), device=dev, generator=gen),
                         "action": r(B, 3 * L) * 2 - 1, "reward": r(B, 1) * 2 - 1, "done": (r(B, 1) < 0.05).float()})
+    step = lambda it: agent.update(batches[it % 4], it, lazy_stats=True)
+    first = 0
+    if arm == "graphed":
+        from sgrl_amd.td3 import GraphedUpdates
+        gu = GraphedUpdates(agent, B, hip_kernels=True)
+        gu.warm(0, g, L, lambda: batches[0], iters=2)
+        step, first = (lambda it: gu.update(0, g, L, batches[it % 4], it)), 2
     loss = None
-    for it in range(8):
-        loss = agent.update(batches[it % 4], it, lazy_stats=True)
+    for it in range(first, 8):
+        loss = step(it)
     torch.cuda.synchronize()
     ms = []
     for it in range(8, 8 + updates):
         t0 = time.perf_counter()
-        loss = agent.update(batches[it % 4], it, lazy_stats=True)
+        loss = step(it)
         torch.cuda.synchronize()
         ms.append((time.perf_counter() - t0) * 1e3)
     ms = np.asarray(ms)
