@@ -183,6 +183,39 @@ int sgrl_swat_attention_forward(const float* qkv, const float* bias, float scale
 int sgrl_swat_attention_backward(const float* qkv, float scale, const float* w, const float* d_o, float* dqkv, float* ds, int B, int L,
                                  void* stream);
 
+/* ---- counter-RNG dropout (sgrl_amd/swat_policy.py with dropout_rate > 0; csrc/dropout.hip, csrc/dropout_rng.h) -------------------
+ * The reference's --dropout_rate reaches the SWAT networks only (StructureActor.py:130-134, StructureCritic.py:46, 60), at five
+ * kinds of site: the position embedding (StructureActor.py:29), the softmax weights (attentions.py:163), dropout1 behind out_proj,
+ * `dropout` between the ReLU and linear2, dropout2 behind linear2 (StructureActor.py:56-62).  Here a mask is a FUNCTION of four
+ * numbers instead of a draw from a generator, so no pass stores one and a backward regenerates its forward's:
+ *   word = replay_word(seed, step, 0x100 + site, i)       Philox4x32-10 as in sgrl_replay.h (stream ids 0 and 1 are the replay's);
+ *                                                          i = row-major linear index in the tensor the dropout is applied to
+ *   thr  = (uint64) floor((double) p * 4294967296.0)      p a float in [0, 1]
+ *   keep = (uint64) word >= thr
+ *   y    = keep ? x * (1.0f / (1.0f - p)) : 0.0f          p == 1: y = 0;  p == 0: y = x, bit for bit
+ * seed: a host argument (the agent's seed).  step_dev: a DEVICE uint64 the kernel reads -- the update number, which the host never
+ * has to know (td3.Agent increments it on the update's stream).  site: a host int in 0 .. 2^24 - 1, the running number of the
+ * dropout call inside one update; the backward of a call passes the forward's (step, site).
+ *
+ * sgrl_dropout_forward: y[0 .. n) = dropout(x[0 .. n)), element-wise and OUT OF PLACE (overlapping x and y are refused), n >= 1 with
+ * 64-bit indices; one Philox block serves four consecutive elements; 16-byte accesses when x and y are both 16-byte aligned,
+ * scalar ones otherwise and for the last n mod 4 elements.  sgrl_dropout_backward: dx = dropout(dy) with the same mask -- the same
+ * kernel.  One launch per call, every element written once: bit-reproducible.  A null pointer, n <= 0, p outside [0, 1] (a NaN
+ * included) or a site outside its range returns SGRL_ERR_ARG before anything is launched. */
+int sgrl_dropout_forward(const float* x, float* y, int64_t n, float p, uint64_t seed, const uint64_t* step_dev, int site, void* stream);
+int sgrl_dropout_backward(const float* dy, float* dx, int64_t n, float p, uint64_t seed, const uint64_t* step_dev, int site, void* stream);
+
+/* sgrl_swat_attention_forward / _backward with the softmax weights dropped, wd = dropout(w) over the index of w [B, 2, L, L]:
+ *   forward:   o = wd v;  the w returned is UNDROPPED (the softmax Jacobian needs it) and no mask is stored;
+ *   backward:  dw = (d_o v') keep / (1 - p),  ds = w (dw - sum_j w dw),  dv = wd' d_o,  dq = scale ds k,  dk = ds' (scale q).
+ * An o row whose weights were all dropped is exact zeros.  Limits, argument checks (plus those of p, step_dev and site above), one
+ * launch per call, no atomics and the fixed summation order are those of the pair above, whose kernels and bits are unchanged:
+ * both pairs are instantiations of one template. */
+int sgrl_swat_attention_forward_dropout(const float* qkv, const float* bias, float scale, float* w, float* o, int B, int L, float p,
+                                        uint64_t seed, const uint64_t* step_dev, int site, void* stream);
+int sgrl_swat_attention_backward_dropout(const float* qkv, float scale, const float* w, const float* d_o, float* dqkv, float* ds, int B, int L,
+                                         float p, uint64_t seed, const uint64_t* step_dev, int site, void* stream);
+
 /* ---- SMP networks (sgrl_amd/smp_policy.py `train_kernels`; csrc/smp_train.hip) --------------------------------------------------
  * What lies between the linear layers of the message-passing networks' differentiable passes, one launch per call, float32, on
  * `stream`, no host synchronisation, no atomics, no scratch; every output element is written exactly once in a fixed order

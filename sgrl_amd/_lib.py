@@ -11,7 +11,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGRL_HIP_LIB", os.path.join(_HERE, "libsgrl_hip.so"))   # override: A/B benchmarking of builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["engine.hip", "set_actor.hip", "train_gemm.hip", "render.hip", "swat_actor.hip", "smp_actor.hip", "replay_sample.hip", "eval_record.hip", "explore_actions.hip", "scene.hip", "mlp_actor.hip", "mlp_train.hip", "mlp_optim.hip", "mlp_batch.hip", "smp_train.hip", "td3_loss.hip"]
+SOURCES = ["engine.hip", "set_actor.hip", "train_gemm.hip", "render.hip", "swat_actor.hip", "smp_actor.hip", "replay_sample.hip", "eval_record.hip", "explore_actions.hip", "scene.hip", "mlp_actor.hip", "mlp_train.hip", "mlp_optim.hip", "mlp_batch.hip", "smp_train.hip", "td3_loss.hip", "dropout.hip"]
 
 _lib = None
 

@@ -29,6 +29,7 @@
 
 #include "../../include/sgrl.h"
 #include "../../include/sgrl_train.h"
+#include "dropout_rng.h"
 #include "train_internal.h"
 
 namespace {
@@ -877,14 +878,29 @@ __device__ __forceinline__ float swat_dot64(const float* a, const float* k) {
   }
   return (acc[0] + acc[1]) + (acc[2] + acc[3]);
 }
-__global__ __launch_bounds__(64) void k_swat_attn_fwd(const float* __restrict__ qkv, const float* __restrict__ bias, float scale,
-                                                      float* wout, float* o, int L) {
+// DROP (sgrl_swat_attention_*_dropout): the reference drops the softmax weights (attentions.py:163).  wd = dropout(w) over the index
+// of w [B, 2, L, L] (dropout_rng.h); w leaves the kernel UNDROPPED (the softmax Jacobian needs it), o = wd v, and no mask is stored:
+// the backward regenerates it from the same (seed, step, site).  `step` is read with the load batch at the top; the words are
+// generated only after that batch has been consumed (behind the first barrier), by the thread that owns the (i, j) entry.  The
+// DROP = false instantiation is the kernel as it was: every DROP statement is compiled out of it.
+struct SwatDrop {
+  uint64_t thr, seed;
+  const uint64_t* step_dev;
+  float scale;
+  uint32_t stream_id;
+};
+template <bool DROP>
+__device__ __forceinline__ void swat_attn_fwd_body(const float* __restrict__ qkv, const float* __restrict__ bias, float scale, float* wout,
+                                                   float* o, int L, const SwatDrop& dr) {
   __shared__ float qs[SL * SQ], ks[SL * SQ];
   __shared__ float sc[SL * SL];
+  __shared__ float sd[DROP ? SL * SL : 1];           // DROP: the dropped weights wd
   const int b = blockIdx.x >> 1, h = blockIdx.x & 1, d = threadIdx.x, c = 64 * h + d;
   const size_t n0 = (size_t)b * L;
   const int LL = L * L;
   float qv[SL], kv[SL], vv[SL], bz[4];
+  uint64_t step = 0;
+  if constexpr (DROP) step = dr.step_dev[0];
 #pragma unroll
   for (int i = 0; i < SL; i++)
     if (i < L) {
@@ -920,25 +936,51 @@ __global__ __launch_bounds__(64) void k_swat_attn_fwd(const float* __restrict__ 
     const int e = d + 64 * t;
     if (e < LL) wout[((size_t)b * 2 + h) * LL + e] = sc[e];
   }
+  if constexpr (DROP) {
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+      const int e = d + 64 * t;
+      if (e < LL)
+        sd[e] = sgrl_dropout::apply(sc[e], sgrl_replay::replay_word(dr.seed, step, dr.stream_id, ((uint64_t)b * 2 + h) * LL + e), dr.thr,
+                                    dr.scale);
+    }
+    __syncthreads();
+  }
+  const float* wv = DROP ? sd : sc;
 #pragma unroll
   for (int i = 0; i < SL; i++)
     if (i < L) {
       float acc = 0.f;
 #pragma unroll
-      for (int j = 0; j < SL; j++) if (j < L) acc += sc[i * L + j] * vv[j];
+      for (int j = 0; j < SL; j++) if (j < L) acc += wv[i * L + j] * vv[j];
       o[(n0 + i) * 128 + c] = acc;
     }
 }
+__global__ __launch_bounds__(64) void k_swat_attn_fwd(const float* __restrict__ qkv, const float* __restrict__ bias, float scale,
+                                                      float* wout, float* o, int L) {
+  swat_attn_fwd_body<false>(qkv, bias, scale, wout, o, L, SwatDrop{});
+}
+__global__ __launch_bounds__(64) void k_swat_attn_fwd_drop(const float* __restrict__ qkv, const float* __restrict__ bias, float scale,
+                                                           float* wout, float* o, int L, SwatDrop dr) {
+  swat_attn_fwd_body<true>(qkv, bias, scale, wout, o, L, dr);
+}
 // Backward: dw = do v' (per head), ds = w (dw - sum_j w dw), dq = scale ds k, dk = ds' (scale q), dv = w' do.  dqkv [B, L, 384] is
 // written packed, ds [B, 2, L, L] is written out as well (its sum over the environments is the gradient of the relation bias).
-__global__ __launch_bounds__(64) void k_swat_attn_bwd(const float* __restrict__ qkv, float scale, const float* __restrict__ win,
-                                                      const float* __restrict__ dout, float* dqkv, float* ds_out, int L) {
+// DROP: win is the UNDROPPED w of the forward; the thread that owns entry (i, j) regenerates its keep decision behind the first barrier
+// (the load batch has been consumed there):  dw = (do v') keep scale_p,  wd = w keep scale_p  (dv = wd' do); the softmax Jacobian
+// takes the undropped w.  DROP = false is the kernel as it was.
+template <bool DROP>
+__device__ __forceinline__ void swat_attn_bwd_body(const float* __restrict__ qkv, float scale, const float* __restrict__ win,
+                                                   const float* __restrict__ dout, float* dqkv, float* ds_out, int L, const SwatDrop& dr) {
   __shared__ float as[SL * SQ], vs[SL * SQ];
   __shared__ float w[SL * SL], dw[SL * SL];
+  __shared__ float wd[DROP ? SL * SL : 1];           // DROP: the dropped weights
   const int b = blockIdx.x >> 1, h = blockIdx.x & 1, d = threadIdx.x, c = 64 * h + d;
   const size_t n0 = (size_t)b * L;
   const int LL = L * L;
   float qv[SL], kv[SL], vv[SL], av[SL], wz[4];
+  uint64_t step = 0;
+  if constexpr (DROP) step = dr.step_dev[0];
 #pragma unroll
   for (int i = 0; i < SL; i++)
     if (i < L) {
@@ -963,7 +1005,15 @@ __global__ __launch_bounds__(64) void k_swat_attn_bwd(const float* __restrict__ 
 #pragma unroll
   for (int t = 0; t < 4; t++) {                      // dw[i][j] = do[i] . v[j]
     const int e = d + 64 * t;
-    if (e < LL) dw[e] = swat_dot64(as + (e / L) * SQ, vs + (e % L) * SQ);
+    if constexpr (DROP) {
+      if (e < LL) {
+        const uint32_t word = sgrl_replay::replay_word(dr.seed, step, dr.stream_id, ((uint64_t)b * 2 + h) * LL + e);
+        dw[e] = sgrl_dropout::apply(swat_dot64(as + (e / L) * SQ, vs + (e % L) * SQ), word, dr.thr, dr.scale);
+        wd[e] = sgrl_dropout::apply(wz[t], word, dr.thr, dr.scale);
+      }
+    } else {
+      if (e < LL) dw[e] = swat_dot64(as + (e / L) * SQ, vs + (e % L) * SQ);
+    }
   }
   __syncthreads();
   if (d < L) {                                       // softmax backward, one thread per row i; dw becomes ds in place
@@ -987,16 +1037,25 @@ __global__ __launch_bounds__(64) void k_swat_attn_bwd(const float* __restrict__ 
       for (int j = 0; j < SL; j++) if (j < L) acc += dw[i * L + j] * kv[j];
       dqkv[(n0 + i) * 384 + c] = acc * scale;
     }
+  const float* wv = DROP ? wd : w;
 #pragma unroll
   for (int j = 0; j < SL; j++)
-    if (j < L) {                                     // dk[j] = sum_i ds[i][j] (scale q[i]);  dv[j] = sum_i w[i][j] do[i]
+    if (j < L) {                                     // dk[j] = sum_i ds[i][j] (scale q[i]);  dv[j] = sum_i w[i][j] do[i]  (DROP: wd)
       float ak = 0.f, avv = 0.f;
 #pragma unroll
       for (int i = 0; i < SL; i++)
-        if (i < L) { ak += dw[i * L + j] * (qv[i] * scale); avv += w[i * L + j] * av[i]; }
+        if (i < L) { ak += dw[i * L + j] * (qv[i] * scale); avv += wv[i * L + j] * av[i]; }
       dqkv[(n0 + j) * 384 + 128 + c] = ak;
       dqkv[(n0 + j) * 384 + 256 + c] = avv;
     }
+}
+__global__ __launch_bounds__(64) void k_swat_attn_bwd(const float* __restrict__ qkv, float scale, const float* __restrict__ win,
+                                                      const float* __restrict__ dout, float* dqkv, float* ds_out, int L) {
+  swat_attn_bwd_body<false>(qkv, scale, win, dout, dqkv, ds_out, L, SwatDrop{});
+}
+__global__ __launch_bounds__(64) void k_swat_attn_bwd_drop(const float* __restrict__ qkv, float scale, const float* __restrict__ win,
+                                                           const float* __restrict__ dout, float* dqkv, float* ds_out, int L, SwatDrop dr) {
+  swat_attn_bwd_body<true>(qkv, scale, win, dout, dqkv, ds_out, L, dr);
 }
 
 // Equivariant contraction of a node's three 32-vectors with its 32 x 32 matrix (reference SEActor.py:108-110, 262-264):
@@ -1498,6 +1557,26 @@ int sgrl_swat_attention_backward(const float* qkv, float scale, const float* w, 
     return tfail(SGRL_ERR_ARG, "sgrl_swat_attention_backward: bad argument (null pointer, B <= 0 or L outside 1..15)");
   hipLaunchKernelGGL(k_swat_attn_bwd, dim3(2 * B), dim3(64), 0, (hipStream_t)stream, qkv, scale, w, d_o, dqkv, ds, L);
   { int lrc = SGRL_OK; if (!launched("k_swat_attn_bwd launch failed", &lrc)) return lrc; }
+  return SGRL_OK;
+}
+
+int sgrl_swat_attention_forward_dropout(const float* qkv, const float* bias, float scale, float* w, float* o, int B, int L, float p,
+                                        uint64_t seed, const uint64_t* step_dev, int site, void* stream) {
+  if (!qkv || !w || !o || !step_dev || B <= 0 || B > (1 << 30) || L < 1 || L > SL || !sgrl_dropout::valid(p, site))
+    return tfail(SGRL_ERR_ARG, "sgrl_swat_attention_forward_dropout: bad argument (null pointer, B <= 0, L outside 1..15, p outside [0, 1] or a bad site)");
+  const SwatDrop dr{sgrl_dropout::threshold(p), seed, step_dev, sgrl_dropout::scale(p), sgrl_dropout::stream_of(site)};
+  hipLaunchKernelGGL(k_swat_attn_fwd_drop, dim3(2 * B), dim3(64), 0, (hipStream_t)stream, qkv, bias, scale, w, o, L, dr);
+  { int lrc = SGRL_OK; if (!launched("k_swat_attn_fwd_drop launch failed", &lrc)) return lrc; }
+  return SGRL_OK;
+}
+
+int sgrl_swat_attention_backward_dropout(const float* qkv, float scale, const float* w, const float* d_o, float* dqkv, float* ds, int B, int L,
+                                         float p, uint64_t seed, const uint64_t* step_dev, int site, void* stream) {
+  if (!qkv || !w || !d_o || !dqkv || !ds || !step_dev || B <= 0 || B > (1 << 30) || L < 1 || L > SL || !sgrl_dropout::valid(p, site))
+    return tfail(SGRL_ERR_ARG, "sgrl_swat_attention_backward_dropout: bad argument (null pointer, B <= 0, L outside 1..15, p outside [0, 1] or a bad site)");
+  const SwatDrop dr{sgrl_dropout::threshold(p), seed, step_dev, sgrl_dropout::scale(p), sgrl_dropout::stream_of(site)};
+  hipLaunchKernelGGL(k_swat_attn_bwd_drop, dim3(2 * B), dim3(64), 0, (hipStream_t)stream, qkv, scale, w, d_o, dqkv, ds, L, dr);
+  { int lrc = SGRL_OK; if (!launched("k_swat_attn_bwd_drop launch failed", &lrc)) return lrc; }
   return SGRL_OK;
 }
 

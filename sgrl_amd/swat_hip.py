@@ -141,6 +141,10 @@ class HipSwatActor(object):
     def sync_weights(self, force=False):
         """Bind the handle to the parameters' storage (include/sgrl_swat.h sgrl_swat_bind_params).  The VALUES are read by every
         forward; this binds again only when a parameter's address moved (module.to(), re-created tensors) or with force."""
+        if self.net.training and getattr(self.net, "dropout", 0.0) > 0.0:
+            # every forward of this handle comes through here: the kernels behind it have no dropout, and training mode asks for it
+            raise _lib.SgrlError("the HIP forward of a SWAT network has no dropout: the module is in training mode with dropout %g "
+                                 "(call eval() for collection / evaluation; an update's passes run the modules)" % self.net.dropout)
         params = self._params()
         ptrs = tuple(p.data_ptr() for p in params)
         if not force and ptrs == self._bound:

@@ -11,6 +11,12 @@ the TD3 update back-props through: PyTorch operations by default, the training k
 (_TrainKernelsSwitch; td3.Agent(swat_train_kernels=True)).  The no-grad target chain of an update (td3.Agent.update_targets) runs on the
 same kernels through `hip_handle()`: the handle a module caches is per-process device state and is dropped whenever the
 module is pickled or deep-copied.
+
+Dropout (`args.dropout_rate`, which the reference hands to these networks only): in training mode the reference's five kinds of
+site -- position embedding, attention weights, dropout1, dropout, dropout2 -- go through train_ops.dropout / swat_attention on both
+paths; inside a train_ops.dropout_rng context (td3.Agent.update opens one) the masks are the counter RNG's (include/sgrl_train.h),
+otherwise torch's.  The HIP forwards behind `hip_handle()` have no dropout: they refuse a module that is in training mode with
+dropout > 0 (swat_hip.HipSwatActor.sync_weights), so collection and evaluation run in eval mode.
 """
 import copy
 import math
@@ -45,9 +51,11 @@ class _SelfAttention(_TrainKernelsSwitch, nn.Module):
     """Parameters of torch.nn.MultiheadAttention (in_proj_weight / in_proj_bias / out_proj), forward of the reference's
     attentions.multi_head_attention_forward: q scaled by head_dim^-0.5, additive float mask [B * H, L, L]."""
 
-    def __init__(self, embed_dim, num_heads):
+    dropout = 0.0          # (class default: a module pickled before the attribute existed)
+
+    def __init__(self, embed_dim, num_heads, dropout=0.0):
         super().__init__()
-        self.embed_dim, self.num_heads = embed_dim, num_heads
+        self.embed_dim, self.num_heads, self.dropout = embed_dim, num_heads, float(dropout)
         self.in_proj_weight = nn.Parameter(torch.empty(3 * embed_dim, embed_dim))
         self.in_proj_bias = nn.Parameter(torch.zeros(3 * embed_dim))
         self.out_proj = nn.Linear(embed_dim, embed_dim)
@@ -61,7 +69,7 @@ class _SelfAttention(_TrainKernelsSwitch, nn.Module):
         hd = E // H
         if self.train_kernels:
             qkv = train_ops.linear(x, self.in_proj_weight, self.in_proj_bias, slot=slot)
-            o = train_ops.swat_attention(qkv, bias, float(hd) ** -0.5, H)
+            o = train_ops.swat_attention(qkv, bias, float(hd) ** -0.5, H, dropout_p=self.dropout, training=self.training)
             return train_ops.linear(o, self.out_proj.weight, self.out_proj.bias)
         q, k, v = F.linear(x, self.in_proj_weight, self.in_proj_bias).chunk(3, dim=-1)
         q = (q * float(hd) ** -0.5).view(B, L, H, hd)
@@ -69,35 +77,46 @@ class _SelfAttention(_TrainKernelsSwitch, nn.Module):
         s = torch.einsum("bihd,bjhd->bhij", q, k)
         if bias is not None:
             s = s + bias.unsqueeze(0)
-        w = F.softmax(s, dim=-1)
+        w = train_ops.dropout(F.softmax(s, dim=-1), self.dropout, self.training)       # reference attentions.py:163
         o = torch.einsum("bhij,bjhd->bihd", w, v).reshape(B, L, E)
         return self.out_proj(o)
 
 
 class _EncoderLayer(_TrainKernelsSwitch, nn.Module):
-    """reference MyTransformerEncoderLayer (StructureActor.py:48-66): post-norm, ReLU feed-forward, dropout = identity at
-    the reference's dropout_rate 0."""
+    """reference MyTransformerEncoderLayer (StructureActor.py:48-66): post-norm, ReLU feed-forward; in training mode with
+    `dropout` > 0 the reference's four dropouts: the attention weights (inside self_attn), dropout1 behind out_proj, `dropout`
+    between the ReLU and linear2, dropout2 behind linear2 (train_ops.dropout: the identity otherwise, nothing launched)."""
 
-    def __init__(self, d_model, nhead, dim_feedforward):
+    dropout = 0.0
+
+    def __init__(self, d_model, nhead, dim_feedforward, dropout=0.0):
         super().__init__()
-        self.self_attn = _SelfAttention(d_model, nhead)
+        self.dropout = float(dropout)
+        self.self_attn = _SelfAttention(d_model, nhead, dropout)
         self.linear1 = nn.Linear(d_model, dim_feedforward)
         self.linear2 = nn.Linear(dim_feedforward, d_model)
         self.norm1 = nn.LayerNorm(d_model)
         self.norm2 = nn.LayerNorm(d_model)
 
     def forward(self, x, bias=None):
+        drop = lambda t: train_ops.dropout(t, self.dropout, self.training)
         if self.train_kernels:
             # x feeds in_proj and the residual, the first norm's output linear1 and the residual: handed out as aliases
             # (train_ops.fan_out), so that the two products add their input gradients onto the residual's instead of leaving an
             # element-wise addition each to autograd.  The hidden activation feeds linear2 only: the masked pair of train_ops.linear
             sa, (xa, xb) = train_ops.fan_out(x, 2)
-            x = train_ops.add_layer_norm(xb, self.self_attn(xa, bias, slot=sa), self.norm1)
+            x = train_ops.add_layer_norm(xb, drop(self.self_attn(xa, bias, slot=sa)), self.norm1)
             sf, (xa, xb) = train_ops.fan_out(x, 2)
             h = train_ops.linear(xa, self.linear1.weight, self.linear1.bias, relu=True, premasked=True, slot=sf)
-            return train_ops.add_layer_norm(xb, train_ops.linear(h, self.linear2.weight, self.linear2.bias, x_relu=True), self.norm2)
-        x = self.norm1(x + self.self_attn(x, bias))
-        return self.norm2(x + self.linear2(F.relu(self.linear1(x))))
+            # A dropout between the masked pair keeps it exact.  linear2's input is hd = dropout(h) = h * keep * s with s = 1 / (1 - p)
+            # >= 1, so hd > 0 exactly where (h > 0) & keep (no product with s underflows to zero).  x_relu masks linear2's input
+            # gradient by hd > 0: g = d_hd * [(h > 0) & keep].  The dropout's backward multiplies by keep * s, which changes nothing
+            # where keep is already applied: d_h = d_hd * s * [(h > 0) & keep] -- the ReLU's mask AND the dropout's, which is what
+            # linear1 (premasked: it applies no mask of its own) needs at its pre-activation.  p = 1: hd = 0, both sides are zero.
+            h = drop(h)
+            return train_ops.add_layer_norm(xb, drop(train_ops.linear(h, self.linear2.weight, self.linear2.bias, x_relu=True)), self.norm2)
+        x = self.norm1(x + drop(self.self_attn(x, bias)))
+        return self.norm2(x + drop(self.linear2(drop(F.relu(self.linear1(x))))))
 
 
 class _Encoder(_TrainKernelsSwitch, nn.Module):
@@ -123,12 +142,17 @@ class _Encoder(_TrainKernelsSwitch, nn.Module):
 class TransformerModel(_TrainKernelsSwitch, nn.Module):
     """reference StructureActor.TransformerModel (StructureActor.py:110-168)."""
 
+    dropout = 0.0
+
     def __init__(self, feature_size, output_size, ninp, nhead, nhid, nlayers, dropout=0.0, condition_decoder=False,
                  transformer_norm=False, num_positions=0, rel_size=1):
         super().__init__()
         self.model_type = "Structure"
+        # dropout (args.dropout_rate; a plain attribute, no parameter): applied in training mode to the position embedding's output
+        # (reference StructureActor.py:29) and inside every encoder layer (_EncoderLayer)
+        self.dropout = float(dropout)
         self.pos_encoder = ConcatPositionalEmbedding(ninp, num_positions=num_positions)
-        self.transformer_encoder = _Encoder(_EncoderLayer(ninp, nhead, nhid), nlayers, nhead,
+        self.transformer_encoder = _Encoder(_EncoderLayer(ninp, nhead, nhid, self.dropout), nlayers, nhead,
                                             norm=nn.LayerNorm(ninp) if transformer_norm else None, d_rel=rel_size)
         self.encoder = nn.Linear(feature_size, ninp)
         self.ninp = ninp
@@ -143,7 +167,8 @@ class TransformerModel(_TrainKernelsSwitch, nn.Module):
         """x [B, L, feature] (node-major) -> [B, L, output_size]."""
         kernels = self.train_kernels
         h = (train_ops.linear(x, self.encoder.weight, self.encoder.bias) if kernels else self.encoder(x)) * math.sqrt(self.ninp)
-        h = self.transformer_encoder(h, self.pos_encoder(graph["traversals"]), graph["relation"])
+        pos = train_ops.dropout(self.pos_encoder(graph["traversals"]), self.dropout, self.training)
+        h = self.transformer_encoder(h, pos, graph["relation"])
         if self.condition_decoder:
             h = torch.cat([h, x], dim=2)
         return train_ops.linear(h, self.decoder.weight, self.decoder.bias) if kernels else self.decoder(h)

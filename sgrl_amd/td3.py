@@ -416,6 +416,13 @@ class Agent(nn.Module):
         if loss_kernels is None:
             loss_kernels = LOSS_KERNELS_DEFAULT
         self.use_loss_kernels = bool(use_hip) and atype != "mlp" and bool(loss_kernels)
+        # dropout_rate: read by the swat networks only (the reference forces the SET networks to 0, SEActor.py:185; smp and mlp have
+        # none).  With a rate > 0 every update() runs inside a train_ops.dropout_rng context: seed = args.seed (0 when absent), step =
+        # a one-element int64 tensor on the batch's device, created by the first update and incremented once at the top of each one,
+        # on the update's stream.  A plain attribute: no parameter, no buffer, not in state_dict()
+        self.dropout_rate = float(getattr(args, "dropout_rate", 0.0) or 0.0) if "swat" in (atype, ctype) else 0.0
+        self.dropout_seed = int(getattr(args, "seed", 0) or 0)
+        self._dropout_step = None
 
     def set_swat_train_kernels(self, on):
         """Turn the training kernels of the online swat networks on or off (no other agent type has the switch)."""
@@ -489,6 +496,8 @@ class Agent(nn.Module):
         if not ((self.use_swat_hip or self.use_smp_hip or self.use_mlp_hip) and next_obs.is_cuda and next_obs.dtype == torch.float32 and
                 self.device.type == "cuda"):
             return None
+        if self.use_swat_hip and self.dropout_rate > 0 and (self.actor_target.training or self.critic_target.training):
+            return None      # the HIP chain has no dropout: targets in training mode run the modules, as the reference's do
         if self.use_smp_hip:
             t = self._smp_targets
             if t is None or t.actor.policy is not self.actor_target or t.critic.module is not self.critic_target:
@@ -527,6 +536,21 @@ class Agent(nn.Module):
         skip_unused_critic_grads=True, whatever that argument says.  With `mlp_hip_optim` as well, each clip_and_step and the soft
         update of the same network are one mlp_hip.HipMlpOptim step (two launches); the target critic is then written before the
         actor pass, which reads the online critic only."""
+        if self.dropout_rate > 0:
+            with self._dropout_rng(data_batch["obs"].device):
+                return self._update(data_batch, it, noise, lazy_stats, skip_unused_critic_grads)
+        return self._update(data_batch, it, noise, lazy_stats, skip_unused_critic_grads)
+
+    def _dropout_rng(self, device):
+        """The train_ops.dropout_rng context of one update: the step counter moves first (one launch on the current stream), every
+        dropout call of the update's three parts then numbers itself from site 0."""
+        step = self._dropout_step
+        if step is None or step.device != device:
+            step = self._dropout_step = torch.zeros(1, dtype=torch.int64, device=device)
+        step.add_(1)
+        return train_ops.dropout_rng(self.dropout_seed, step)
+
+    def _update(self, data_batch, it, noise, lazy_stats, skip_unused_critic_grads):
         grads = self._hip_grads(data_batch)
         if grads is not None:
             return self._update_hip_grads(grads, data_batch, it, noise, lazy_stats)
@@ -749,6 +773,11 @@ class GraphedUpdates(object):
         self.captures = {}         # (key, flag) -> number of times that graph has been captured
         if getattr(agent.args, "actor_type", "set") == "mlp":
             raise NotImplementedError("GraphedUpdates is not built for 'mlp' agents: run their updates eagerly (DeviceTrainer(graph_updates=False))")
+        if getattr(agent, "dropout_rate", 0.0) > 0:
+            # the site numbers of an update are host state and its passes differ between training and eval mode: nobody has made the
+            # capture of a dropout update sound, so it is refused rather than replayed with stale masks
+            raise NotImplementedError("GraphedUpdates does not replay updates with dropout (dropout_rate %g): run them eagerly "
+                                      "(DeviceTrainer(graph_updates=False)) or set dropout_rate to 0" % agent.dropout_rate)
         dev = agent.device
         if dev.type != "cuda":
             raise RuntimeError("GraphedUpdates needs the agent on the GPU")

@@ -60,6 +60,8 @@ class DeviceTrainer(object):
                 from .vec_env import resolve_models
                 xml = env_kw.get("xml_paths")
                 self.args.mlp_num_limbs = resolve_models(self.env_names[-1:], None if xml is None else xml[-1:])[0].num_limbs
+        if getattr(self.args, "seed", None) is None:
+            self.args.seed = int(seed)        # what the agent seeds its dropout masks with (td3.Agent.dropout_seed)
         torch.manual_seed(seed)               # same initial weights on every rank
         self.agent = Agent(self.args, device=device)
         if tune_gemms:

@@ -48,6 +48,11 @@ def _L():
         L.sgrl_attention_backward.argtypes = [vp, vp, vp, ctypes.c_float, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp]
         L.sgrl_swat_attention_forward.argtypes = [vp, vp, ctypes.c_float, vp, vp, ci, ci, vp]
         L.sgrl_swat_attention_backward.argtypes = [vp, ctypes.c_float, vp, vp, vp, vp, ci, ci, vp]
+        cf, u64 = ctypes.c_float, ctypes.c_uint64
+        L.sgrl_dropout_forward.argtypes = [vp, vp, ctypes.c_int64, cf, u64, vp, ci, vp]
+        L.sgrl_dropout_backward.argtypes = [vp, vp, ctypes.c_int64, cf, u64, vp, ci, vp]
+        L.sgrl_swat_attention_forward_dropout.argtypes = [vp, vp, cf, vp, vp, ci, ci, cf, u64, vp, ci, vp]
+        L.sgrl_swat_attention_backward_dropout.argtypes = [vp, cf, vp, vp, vp, vp, ci, ci, cf, u64, vp, ci, vp]
         L.sgrl_linear_forward_fused.argtypes = [vp, ci, vp, ci, vp, vp, vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, vp]
         L.sgrl_linear_forward_twin_fused.argtypes = [vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, ci, ci, ci, ci, ci, vp]
         L.sgrl_embed3_forward.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, ci, vp]
@@ -863,17 +868,182 @@ def set_attention(qkv, vgp, gdir, bias, scale):
     return o, og
 
 
+# ---- counter-RNG dropout (include/sgrl_train.h "counter-RNG dropout"; csrc/dropout_rng.h) ------------------------------------------
+# The masks of the SWAT networks' dropout sites are a function of (seed, step, site, element index), not a draw from torch's
+# generator: the kernels regenerate them in the backward pass, and the PyTorch path below draws the SAME masks with integer tensor
+# arithmetic -- slow and exact; it is what float64 comparisons and the no-grad target passes of an update run.
+DROPOUT_STREAM_BASE = 0x100      # stream ids 0 and 1 are the replay draw's (csrc/replay_rng.h)
+_M32 = 0xFFFFFFFF
+# how often each dropout path was ENTERED since import (tests: an agent with dropout_rate 0 enters none): "kernel" / "attention_kernel"
+# the HIP kernels, "counter" the torch restatement of the counter RNG, "torch" F.dropout (no dropout_rng context active)
+dropout_calls = {"kernel": 0, "attention_kernel": 0, "counter": 0, "torch": 0}
+_rng = None
+
+
+class DropoutRng(object):
+    """What the dropout calls of one update share: `seed` (a host int, 64 bits), `step` (a one-element int64 tensor holding the bits
+    of the uint64 the kernels read; whoever owns it changes it between updates, never inside one) and `site`, the running number of
+    the dropout call, which every call -- kernel or not -- takes in program order."""
+    __slots__ = ("seed", "step", "site")
+
+    def __init__(self, seed, step):
+        if not (torch.is_tensor(step) and step.dtype == torch.int64 and step.numel() == 1 and step.is_contiguous()):
+            raise ValueError("dropout_rng: step_tensor must be a one-element int64 tensor")
+        self.seed, self.step, self.site = int(seed) & (2 ** 64 - 1), step, 0
+
+    def next_site(self):
+        s = self.site
+        self.site = s + 1
+        return s
+
+
+@contextlib.contextmanager
+def dropout_rng(seed, step_tensor):
+    """Inside this context every dropout of this module (dropout(), swat_attention(dropout_p=...)) takes its mask from the counter RNG
+    with (seed, step_tensor's value, running site number from 0); outside any such context they fall back to F.dropout."""
+    global _rng
+    old, _rng = _rng, DropoutRng(seed, step_tensor)
+    try:
+        yield _rng
+    finally:
+        _rng = old
+
+
+def _mul_hi_lo(a, c):
+    """a: a 32-bit constant, c: int64 tensor of values < 2^32 -> (high, low) 32 bits of a * c, without leaving int64's range."""
+    al, ah = a & 0xFFFF, a >> 16
+    pl, ph = c * al, c * ah                     # < 2^48 each
+    return (ph + (pl >> 16)) >> 16, (pl + ((ph & 0xFFFF) << 16)) & _M32
+
+
+def counter_words(seed, step, stream, idx):
+    """replay_word(seed, step, stream, idx) of csrc/replay_rng.h for an int64 tensor of element indices `idx`; step: a one-element
+    int64 tensor on idx's device.  -> int64 tensor of the 32-bit words."""
+    step = step.reshape(())
+    c = [(idx >> 2) & _M32, (step & _M32).expand_as(idx), ((step >> 32) & _M32).expand_as(idx), torch.full_like(idx, int(stream) & _M32)]
+    k0, k1 = seed & _M32, (seed >> 32) & _M32
+    for _ in range(10):
+        h0, l0 = _mul_hi_lo(0xD2511F53, c[0])
+        h1, l1 = _mul_hi_lo(0xCD9E8D57, c[2])
+        c = [h1 ^ c[1] ^ k0, l1, h0 ^ c[3] ^ k1, l0]
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    return torch.stack(c, dim=-1).gather(-1, (idx & 3).unsqueeze(-1)).squeeze(-1)
+
+
+def dropout_threshold_scale(p):
+    """(thr, scale) of the definition for a probability p, which the ABI takes as a float32: thr = floor(p * 2^32), scale = the float32
+    1 / (1 - p), as a Python float (0 at p = 1, where nothing is kept and the kernels never multiply)."""
+    p32 = np.float32(p)
+    thr = int(np.floor(np.float64(p32) * 4294967296.0))
+    return thr, (0.0 if p32 >= 1 else float(np.float32(1.0) / (np.float32(1.0) - p32)))
+
+
+def _counter_dropout(x, p, rng, site):
+    """The definition on any device and dtype: the mask over x's row-major element index, x * scale where kept."""
+    dropout_calls["counter"] += 1
+    thr, scale = dropout_threshold_scale(p)
+    idx = torch.arange(x.numel(), dtype=torch.int64, device=x.device)
+    keep = (counter_words(rng.seed, rng.step.to(x.device), DROPOUT_STREAM_BASE + site, idx) >= thr).view(x.shape)
+    return torch.where(keep, x * scale, torch.zeros((), dtype=x.dtype, device=x.device))
+
+
+class _DropoutFn(torch.autograd.Function):
+    """y = dropout(x) by the counter RNG, one launch forward and one backward (csrc/dropout.hip); nothing is saved but the call's
+    (p, seed, step tensor, site)."""
+
+    @staticmethod
+    def forward(ctx, x, p, seed, step, site):
+        L = _L()
+        x2 = x if x.is_contiguous() else x.contiguous()
+        y = torch.empty_like(x2)
+        st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        _check(L, L.sgrl_dropout_forward(_p(x2), _p(y), x2.numel(), ctypes.c_float(p), ctypes.c_uint64(seed), _p(step), site, st),
+               "sgrl_dropout_forward")
+        ctx.call = (p, seed, step, site)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        L = _L()
+        p, seed, step, site = ctx.call
+        dy2 = dy if dy.is_contiguous() else dy.contiguous()
+        dx = torch.empty_like(dy2)
+        st = ctypes.c_void_p(torch.cuda.current_stream(dy.device).cuda_stream)
+        _check(L, L.sgrl_dropout_backward(_p(dy2), _p(dx), dy2.numel(), ctypes.c_float(p), ctypes.c_uint64(seed), _p(step), site, st),
+               "sgrl_dropout_backward")
+        return dx, None, None, None, None
+
+
+def dropout(x, p, training=True):
+    """F.dropout(x, p, training) with the mask of the active dropout_rng context: the element-wise kernels where autograd records on
+    the GPU in float32, the torch restatement of the same definition elsewhere (CPU, float64, torch.no_grad()).  Without a context:
+    F.dropout.  p == 0 or not training: x itself -- nothing is launched, allocated or recorded."""
+    if not training or p <= 0.0:
+        return x
+    rng = _rng
+    if rng is None:
+        dropout_calls["torch"] += 1
+        return F.dropout(x, float(p), True)
+    site = rng.next_site()
+    if x.numel() > 0 and _on_device_with_grad(x) and rng.step.device == x.device:
+        dropout_calls["kernel"] += 1
+        return _DropoutFn.apply(x, float(p), rng.seed, rng.step, site)
+    return _counter_dropout(x, p, rng, site)
+
+
+class _SwatAttnDropFn(torch.autograd.Function):
+    """_SwatAttnFn with the softmax weights dropped by the counter RNG (k_swat_attn_fwd_drop / k_swat_attn_bwd_drop): the saved w is
+    the undropped one, the backward regenerates the mask from (seed, step, site)."""
+
+    @staticmethod
+    def forward(ctx, qkv, bias, scale, p, seed, step, site):
+        L = _L()
+        B, Ln = qkv.shape[0], qkv.shape[1]
+        qkv = qkv if qkv.is_contiguous() else qkv.contiguous()
+        bz = None if bias is None else (bias if bias.is_contiguous() else bias.contiguous())
+        w = torch.empty((B, 2, Ln, Ln), dtype=torch.float32, device=qkv.device)
+        o = torch.empty((B, Ln, 128), dtype=torch.float32, device=qkv.device)
+        st = ctypes.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream)
+        _check(L, L.sgrl_swat_attention_forward_dropout(_p(qkv), _p(bz), ctypes.c_float(scale), _p(w), _p(o), B, Ln, ctypes.c_float(p),
+                                                        ctypes.c_uint64(seed), _p(step), site, st), "sgrl_swat_attention_forward_dropout")
+        ctx.save_for_backward(qkv, w)
+        ctx.has_bias, ctx.scale, ctx.call = bias is not None, float(scale), (p, seed, step, site)
+        return o
+
+    @staticmethod
+    def backward(ctx, d_o):
+        L = _L()
+        qkv, w = ctx.saved_tensors
+        p, seed, step, site = ctx.call
+        B, Ln = qkv.shape[0], qkv.shape[1]
+        d_o = d_o if d_o.is_contiguous() else d_o.contiguous()
+        dqkv, ds = torch.empty_like(qkv), torch.empty_like(w)
+        st = ctypes.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream)
+        _check(L, L.sgrl_swat_attention_backward_dropout(_p(qkv), ctypes.c_float(ctx.scale), _p(w), _p(d_o), _p(dqkv), _p(ds), B, Ln,
+                                                         ctypes.c_float(p), ctypes.c_uint64(seed), _p(step), site, st),
+               "sgrl_swat_attention_backward_dropout")
+        dbias = ds.sum(0) if (ctx.has_bias and ctx.needs_input_grad[1]) else None
+        return (dqkv if ctx.needs_input_grad[0] else None), dbias, None, None, None, None, None
+
+
 SWAT_MAX_LIMBS = 15      # SGRL_SWAT_MAX_LIMBS (include/sgrl_swat.h): what k_swat_attn_* hold in registers
 
 
-def swat_attention(qkv, bias, scale, num_heads=2):
+def swat_attention(qkv, bias, scale, num_heads=2, dropout_p=0.0, training=False):
     """Limb attention of the SWAT networks (swat_policy._SelfAttention between in_proj and out_proj): qkv [B, L, 3 E] = q | k | v
     (q is multiplied by `scale` here), bias [H, L, L] or None -> o [B, L, E] with w = softmax_j(scale q_i . k_j + bias) per head.
     One launch forward and one backward when autograd records on the GPU, E = 128, H = 2 and L <= 15; the module's own operations,
-    one for one, otherwise."""
+    one for one, otherwise.  dropout_p > 0 and training: the softmax weights are dropped (reference attentions.py:163) -- inside the
+    kernel pair's dropout variant under a dropout_rng context, by dropout() on the module's own operations otherwise; with
+    dropout_p == 0 or not training nothing differs from the call without the two arguments."""
     B, Ln = qkv.shape[:2]
-    if qkv.dim() == 3 and qkv.shape[-1] == 384 and num_heads == 2 and 1 <= Ln <= SWAT_MAX_LIMBS and B > 0 and _on_device_with_grad(qkv, bias):
+    drop = bool(training) and dropout_p > 0.0
+    on_kernels = qkv.dim() == 3 and qkv.shape[-1] == 384 and num_heads == 2 and 1 <= Ln <= SWAT_MAX_LIMBS and B > 0 and _on_device_with_grad(qkv, bias)
+    if on_kernels and not drop:
         return _SwatAttnFn.apply(qkv, bias, float(scale))
+    if on_kernels and _rng is not None and _rng.step.device == qkv.device:
+        dropout_calls["attention_kernel"] += 1
+        return _SwatAttnDropFn.apply(qkv, bias, float(scale), float(dropout_p), _rng.seed, _rng.step, _rng.next_site())
     E = qkv.shape[-1] // 3
     H, hd = num_heads, E // num_heads
     q, k, v = qkv.chunk(3, dim=-1)
@@ -883,6 +1053,8 @@ def swat_attention(qkv, bias, scale, num_heads=2):
     if bias is not None:
         s = s + bias.unsqueeze(0)
     w = F.softmax(s, dim=-1)
+    if drop:
+        w = dropout(w, dropout_p, True)
     return torch.einsum("bhij,bjhd->bihd", w, v).reshape(B, Ln, E)
 
 

@@ -2,7 +2,7 @@
 """Timing of the HIP SWAT twin critic forward and of an eager TD3 update of a SWAT agent with / without the HIP target chain.
 
 usage: swat_update_bench.py forward [config3|config5] [reps=60]
-       swat_update_bench.py update [morphology=3d_walker_7_full] [hip|pytorch|auto|kernels|graphed] [updates=40] [streams=1]
+       swat_update_bench.py update [morphology=3d_walker_7_full] [hip|pytorch|auto|kernels|graphed] [updates=40] [streams=1] [dropout=0]
   forward  twin critic forward (swat_hip.HipSwatCritic, both networks) over the 8 walker variants x 1024 environments (config3)
            or one GPU's share of 3D_CWHH++ (config5: 23 morphologies, 8188 environments), against the PyTorch path (per
            morphology: change_morphology + CriticStructurePolicy.forward under no_grad).  With two streams and with the second
@@ -16,7 +16,10 @@ usage: swat_update_bench.py forward [config3|config5] [reps=60]
            replayed from hipGraphs (td3.GraphedUpdates(hip_kernels=True): two eager warm-up updates, the captures fall among the
            untimed ones; the timed call includes filling the slot's static batch and noise).  The pytorch / auto arms use no API
            newer than Agent.update, so this mode also runs on a checkout that has no HIP target chain.  streams=0: the chain's
-           second critic on the caller's stream.
+           second critic on the caller's stream.  dropout: args.dropout_rate of the agent (eager arms only; with a rate the target
+           chain runs the modules).  After the timed updates two more (one without, one with the actor step) run under
+           torch.profiler: `launches_per_two_updates` counts their kernel launches (copies and fills excluded; null when the
+           profiler is not available).
 Prints one JSON line per run.
 """
 import json
@@ -110,11 +113,25 @@ def forward(which, reps):
                       "max_abs_diff_vs_torch": diff, "reps": reps, "device": torch.cuda.get_device_name(0)}), flush=True)
 
 
-def update(name, arm, updates, streams):
+def count_launches(step, it0):
+    """Kernel launches of the updates it0 (odd: no actor step) and it0 + 1, or None."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            step(it0)
+            step(it0 + 1)
+            torch.cuda.synchronize()
+        names = [e.name for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA]
+        return sum(1 for n in names if not n.lower().startswith(("memcpy", "memset")))
+    except Exception:
+        return None
+
+
+def update(name, arm, updates, streams, dropout=0.0):
     from sgrl_amd.td3 import Agent, default_train_args
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
-    args = default_train_args(actor_type="swat", critic_type="swat")
+    args = default_train_args(actor_type="swat", critic_type="swat", dropout_rate=float(dropout))
     if arm == "kernels":
         agent = Agent(args, device=dev, swat_train_kernels=True)
     elif arm == "graphed":
@@ -154,13 +171,16 @@ def update(name, arm, updates, streams):
         torch.cuda.synchronize()
         ms.append((time.perf_counter() - t0) * 1e3)
     ms = np.asarray(ms)
-    print(json.dumps({"mode": "update", "morphology": name, "limbs": L, "batch": B, "arm": arm,
+    critic_loss = float(loss["loss/critic_loss"])
+    launches = count_launches(step, 9 + updates - (updates % 2))        # an odd iteration first
+    print(json.dumps({"mode": "update", "morphology": name, "limbs": L, "batch": B, "arm": arm, "dropout_rate": float(dropout),
+                      "launches_per_two_updates": launches,
                       "hip_target_chain": getattr(agent, "_swat_targets", None) is not None, "twin_streams": bool(streams),
                       "train_kernels": bool(getattr(agent, "use_swat_train_kernels", False)),
                       "update_ms_mean": round(float(ms.mean()), 4), "update_ms_median": round(float(np.median(ms)), 4),
                       "update_ms_min": round(float(ms.min()), 4), "critic_only_ms_median": round(float(np.median(ms[1::2])), 4),
                       "with_actor_ms_median": round(float(np.median(ms[0::2])), 4), "updates": int(updates),
-                      "critic_loss": float(loss["loss/critic_loss"]), "device": torch.cuda.get_device_name(0)}), flush=True)
+                      "critic_loss": critic_loss, "device": torch.cuda.get_device_name(0)}), flush=True)
 
 
 def main():
@@ -169,7 +189,8 @@ def main():
         forward(sys.argv[2] if len(sys.argv) > 2 else "config3", max(50, int(sys.argv[3]) if len(sys.argv) > 3 else 60))
     elif mode == "update":
         update(sys.argv[2] if len(sys.argv) > 2 else "3d_walker_7_full", sys.argv[3] if len(sys.argv) > 3 else "auto",
-               int(sys.argv[4]) if len(sys.argv) > 4 else 40, int(sys.argv[5]) if len(sys.argv) > 5 else 1)
+               int(sys.argv[4]) if len(sys.argv) > 4 else 40, int(sys.argv[5]) if len(sys.argv) > 5 else 1,
+               float(sys.argv[6]) if len(sys.argv) > 6 else 0.0)
     else:
         raise SystemExit(__doc__)
 
