@@ -4,7 +4,8 @@
  * A morphology is two flat blobs produced by sgrl_amd.model_pack.pack_model():
  *   int32  ib[]:  header (SGRL_NHDR ints) followed by the integer tables, in the order of the
  *                 SGRL_INT_FIELDS list below;
- *   double fb[]:  SGRL_NFHDR scalars followed by the float tables in SGRL_F64_FIELDS order.
+ *   double fb[]:  SGRL_NFHDR scalars followed by the float tables in SGRL_F64_FIELDS order, then the tables the packer
+ *                 derives from them (geom_axis, pair_rowc, jnt_rowc).
  * This replaces what the reference obtains from MuJoCo's compiled `mjModel` through mujoco-py
  * (reference src/environments/ModularEnv.py:12 `MujocoEnv.__init__(self, xml, 4)`) plus the
  * per-file task constants of reference src/environments/<name>.py:15-44,150-164.
@@ -59,6 +60,15 @@ enum {
   SGRL_NFHDR = 16
 };
 
+/* One record of pair_rowc / jnt_rowc: the solimp parameters after their clamps, the spring constants K, B of solref, and the
+ * regularisation factors that depend only on the model.  R of a row = (1 - imp) / imp * TRAN; a pyramidal row:
+ * RF2 * max((1 - imp) / imp * RF1, tiny) with RF1 = TRAN + MU^2 TRAN, RF2 = 2 MU^2. */
+enum {
+  SGRL_RC_DMIN = 0, SGRL_RC_DMAX, SGRL_RC_WIDTH, SGRL_RC_MID, SGRL_RC_POWER,
+  SGRL_RC_K, SGRL_RC_B, SGRL_RC_MARGIN, SGRL_RC_MU, SGRL_RC_TRAN, SGRL_RC_RF1, SGRL_RC_RF2,
+  SGRL_ROWC = 12
+};
+
 enum { SGRL_GEOM_PLANE = 0, SGRL_GEOM_SPHERE = 2, SGRL_GEOM_CAPSULE = 3 };
 enum { SGRL_JNT_FREE = 0, SGRL_JNT_HINGE = 3 };
 
@@ -104,6 +114,11 @@ typedef struct SgrlModelView {
   sgrl_ftab_t geom_pos, geom_quat, geom_size;
   sgrl_ftab_t pair_mu, pair_margin, pair_solref, pair_solimp;
   sgrl_ftab_t act_gear, act_ctrlrange;
+  /* derived by the packer from the tables above (constants of a morphology the step would otherwise re-derive in every
+   * dynamics evaluation); the oracle does not read them: */
+  sgrl_ftab_t geom_axis;    /* [ngeom*3] local z axis of the geom in its body's frame: R(geom_quat) e_z */
+  sgrl_ftab_t pair_rowc;    /* [npair*SGRL_ROWC] constraint-row constants of a contact pair (SGRL_RC_* below) */
+  sgrl_ftab_t jnt_rowc;     /* [njnt*SGRL_ROWC] ... of a joint's limit rows (mu = 0, tran = dof_invweight0 of its dof) */
   int n_int, n_f64; /* total blob lengths */
 } SgrlModelView;
 
@@ -177,6 +192,9 @@ SGRL_HD int sgrl_model_view_dims(const int32_t* dims, sgrl_hdr_t hdr_src, sgrl_f
   v->pair_solimp = f; f += 5 * np;
   v->act_gear = f; f += nu;
   v->act_ctrlrange = f; f += 2 * nu;
+  v->geom_axis = f; f += 3 * ng;
+  v->pair_rowc = f; f += SGRL_ROWC * np;
+  v->jnt_rowc = f; f += SGRL_ROWC * nj;
   v->n_f64 = (int)(f - fb);
   return 0;
 }
@@ -194,7 +212,7 @@ SGRL_HD void sgrl_model_blob_sizes(const int32_t* hdr, int* n_int, int* n_f64) {
   const int nb = hdr[SGRL_H_NBODY], nj = hdr[SGRL_H_NJNT], nq = hdr[SGRL_H_NQ], nv = hdr[SGRL_H_NV];
   const int nu = hdr[SGRL_H_NU], ng = hdr[SGRL_H_NGEOM], np = hdr[SGRL_H_NPAIR];
   *n_int = SGRL_NHDR + 18 * nb + 5 * nj + 4 * nv + 2 * ng + 3 * np + 2 * nu;
-  *n_f64 = SGRL_NFHDR + nq + 19 * nb + 17 * nj + 3 * nv + 10 * ng + 9 * np + 3 * nu;
+  *n_f64 = SGRL_NFHDR + nq + 19 * nb + 29 * nj + 3 * nv + 13 * ng + 21 * np + 3 * nu;
 }
 
 SGRL_HD int sgrl_model_view(const int32_t* ib, const double* fb, SgrlModelView* v) {

@@ -653,17 +653,23 @@ struct Engine {
   SGRL_DEV void solve_lower_inplace(int base, int xo) { w.trsv_lower(o.nv, S + base, S + o.dinv, S + xo); }
 
   // ---- collision ------------------------------------------------------------------------------
-  SGRL_DEV void geom_pose(int g, double* pos, double* mat) {
+  // World position and z axis (capsule axis / plane normal: all that collide() uses of a geom's orientation) of geom g.  The axis
+  // in the body frame is a constant of the morphology (m.geom_axis, made by the packer), and a geom of the world body -- the floor --
+  // lies where the model puts it: nothing of it is read from the slab.
+  SGRL_DEV void geom_pose(int g, double* pos, double* ax) {
     const int b = m.geom_body[g];
-    double t[3], gp[3], gq[4], gm[9], xm[9];
+    double gp[3], ga[3];
     ld3(gp, m.geom_pos + 3 * g);
+    ld3(ga, m.geom_axis + 3 * g);
+    if (b == 0) {
+      for (int k = 0; k < 3; k++) { pos[k] = gp[k]; ax[k] = ga[k]; }
+      return;
+    }
+    double t[3], xm[9];
     for (int k = 0; k < 9; k++) xm[k] = S[o.xmat + 9 * b + k];
     mat_vec(t, xm, gp);
     for (int k = 0; k < 3; k++) pos[k] = S[o.xpos + 3 * b + k] + t[k];
-    for (int k = 0; k < 4; k++) gq[k] = m.geom_quat[4 * g + k];
-    quat2mat(gm, gq);
-    for (int r = 0; r < 3; r++)
-      for (int c = 0; c < 3; c++) mat[3 * r + c] = xm[3 * r] * gm[c] + xm[3 * r + 1] * gm[3 + c] + xm[3 * r + 2] * gm[6 + c];
+    mat_vec(ax, xm, ga);
   }
   SGRL_DEV void make_frame(double* fr) {
     const double n2 = sqrt(dot3(fr + 3, fr + 3));
@@ -698,17 +704,17 @@ struct Engine {
   SGRL_DEV void collide() {
     w.lanes(o.np, [&](int p) {
       const int g1 = m.pair_g1[p], g2 = m.pair_g2[p];
-      double p1[3], m1[9], p2[3], m2[9];
-      geom_pose(g1, p1, m1); geom_pose(g2, p2, m2);
+      double p1[3], a1[3], p2[3], a2[3];
+      geom_pose(g1, p1, a1); geom_pose(g2, p2, a2);
       const double margin = m.pair_margin[p];
       const int t1 = m.geom_type[g1], t2 = m.geom_type[g2];
       if (t1 == SGRL_GEOM_PLANE) {
-        const double n[3] = {m1[2], m1[5], m1[8]};
+        const double* n = a1;
         if (t2 == SGRL_GEOM_SPHERE) {
           plane_sphere(2 * p, margin, p1, n, p2, m.geom_size[3 * g2], nullptr);
           I[o.con_valid + 2 * p + 1] = 0;
         } else {
-          const double ax[3] = {m2[2], m2[5], m2[8]};
+          const double* ax = a2;
           const double h = m.geom_size[3 * g2 + 1], r = m.geom_size[3 * g2];
           double ca[3], cb[3];
           for (int k = 0; k < 3; k++) { ca[k] = p2[k] + ax[k] * h; cb[k] = p2[k] - ax[k] * h; }
@@ -718,7 +724,6 @@ struct Engine {
       } else {
         // capsule - capsule (oracle/physics.c collide()): closest points of the two segments; parallel axes: the end
         // spheres of each capsule against the other's axis, at most two contacts
-        const double a1[3] = {m1[2], m1[5], m1[8]}, a2[3] = {m2[2], m2[5], m2[8]};
         const double h1 = m.geom_size[3 * g1 + 1], h2 = m.geom_size[3 * g2 + 1];
         const double r1 = m.geom_size[3 * g1], r2 = m.geom_size[3 * g2];
         const double d[3] = {p1[0] - p2[0], p1[1] - p2[1], p1[2] - p2[2]};
@@ -832,16 +837,10 @@ struct Engine {
   }
 
   // ---- constraint rows ------------------------------------------------------------------------
-  SGRL_DEV double impedance(const double* solimp, double x_raw) {
-    double dmin = solimp[0], dmax = solimp[1], width = solimp[2], mid = solimp[3], power = solimp[4];
-    if (dmin < kMinImp) dmin = kMinImp;
-    if (dmin > kMaxImp) dmin = kMaxImp;
-    if (dmax < kMinImp) dmax = kMinImp;
-    if (dmax > kMaxImp) dmax = kMaxImp;
-    if (width < 0) width = 0;
-    if (mid < kMinImp) mid = kMinImp;
-    if (mid > kMaxImp) mid = kMaxImp;
-    if (power < 1) power = 1;
+  // `rc`: the row's record of m.pair_rowc / m.jnt_rowc -- solimp arrives with its clamps applied (kMinImp .. kMaxImp, width >= 0,
+  // power >= 1: model_pack.py), K and B of solref beside it; only what depends on the distance is left to do here
+  SGRL_DEV double impedance(const double* rc, double x_raw) {
+    const double dmin = rc[SGRL_RC_DMIN], dmax = rc[SGRL_RC_DMAX], width = rc[SGRL_RC_WIDTH], mid = rc[SGRL_RC_MID], power = rc[SGRL_RC_POWER];
     if (dmin == dmax || width <= kMinVal) return 0.5 * (dmin + dmax);
     const double x = fabs(x_raw) / width;
     if (x >= 1) return dmax;
@@ -852,16 +851,6 @@ struct Engine {
     else if (x <= mid) y = pow(x, power) / pow(mid, power - 1);
     else y = 1 - pow(1 - x, power) / pow(1 - mid, power - 1);
     return dmin + y * (dmax - dmin);
-  }
-  SGRL_DEV void kb(const double* solref, const double* solimp, double* K, double* B) {
-    double dmax = solimp[1];
-    if (dmax < kMinImp) dmax = kMinImp;
-    if (dmax > kMaxImp) dmax = kMaxImp;
-    double tc = solref[0];
-    const double dr = solref[1], h2 = 2 * m.fhdr[SGRL_F_TIMESTEP];
-    if (tc < h2) tc = h2;
-    *K = 1.0 / (dmax * dmax * tc * tc * dr * dr);
-    *B = 2.0 / (dmax * tc);
   }
 
   // row table (serial, lane 0): limits in joint order, then contacts in slot order; same cap rule as the oracle
@@ -909,8 +898,19 @@ struct Engine {
       }
       I[o.ecnt + t] = c;
     });
+    if (nitem <= 64) {
+      // the counts are small (0, 1 or 2 (condim - 1) <= 10): one ballot per bit gives the total here and every item's exclusive
+      // prefix in fill_rows, with no reduction chain and no serial scan
+      int total = 0;
+      for (int k = 0; k < 4; k++) {
+        cbits[k] = w.ballot(nitem, [&](int t) { return ((I[o.ecnt + t] >> k) & 1) != 0; });
+        total += popcount64(cbits[k]) << k;
+      }
+      return total;
+    }
     return (int)w.sum(nitem, [&](int t) { return (double)I[o.ecnt + t]; });     // small integers: exact in f64
   }
+  uint64_t cbits[4] = {0, 0, 0, 0};    // bit t of cbits[k] = bit k of item t's row count (count_rows, up to 64 items)
 
   // row table (kind, source, sub-index) into the arrays of R; sets IC_NROW / IC_NROW_WANTED and counts overflows
   SGRL_DEV void fill_rows(const Rows& R, int wanted_total, int cap) {
@@ -918,7 +918,12 @@ struct Engine {
     if (wanted_total <= cap) {
       w.lanes(nitem, [&](int t) {
         int pre = 0;
-        for (int u = 0; u < t; u++) pre += I[o.ecnt + u];
+        if (nitem <= 64) {
+          const uint64_t below = (1ull << t) - 1;
+          for (int k = 0; k < 4; k++) pre += popcount64(cbits[k] & below) << k;
+        } else {
+          for (int u = 0; u < t; u++) pre += I[o.ecnt + u];
+        }
         const int c = I[o.ecnt + t];
         if (t == 0) { I[o.icnt + IC_NROW_WANTED] = wanted_total; I[o.icnt + IC_NROW] = wanted_total; }
         for (int k = 0; k < c; k++) {
@@ -973,26 +978,25 @@ struct Engine {
         return;
       }
       const int kind = R.kind[r], src = R.src[r], sub = R.sub[r];
-      double Rreg, aref;
-      if (kind == ROW_LIMIT_LO || kind == ROW_LIMIT_HI) {
+      const bool lim = kind == ROW_LIMIT_LO || kind == ROW_LIMIT_HI;
+      // the constants of the row: one contiguous record per joint / contact pair (clamped solimp, K, B, margin, mu, the model-only
+      // factors of the regulariser)
+      sgrl_ftab_t rcp = lim ? m.jnt_rowc + SGRL_ROWC * src : m.pair_rowc + SGRL_ROWC * (src >> 1);
+      double rc[SGRL_ROWC];
+      for (int k = 0; k < SGRL_ROWC; k++) rc[k] = rcp[k];
+      double dist, vel;
+      if (lim) {
         const int j = src, side = kind == ROW_LIMIT_LO ? -1 : 1, dof = m.jnt_dofadr[j];
         for (int d = 0; d < nv; d++) Yr[d] = 0;
         Yr[dof] = -side;
         const double q = S[o.qpos + m.jnt_qposadr[j]];
-        const double margin = m.jnt_margin[j];
-        const double dist = side * (m.jnt_range[2 * j + (side + 1) / 2] - q);
-        double si[5], sr[2], K, B;
-        for (int k = 0; k < 5; k++) si[k] = m.jnt_solimp[5 * j + k];
-        sr[0] = m.jnt_solref[2 * j]; sr[1] = m.jnt_solref[2 * j + 1];
-        const double imp = impedance(si, dist - margin);
-        kb(sr, si, &K, &B);
-        Rreg = (1 - imp) / imp * m.dof_invweight0[dof];
-        if (Rreg < kMinVal) Rreg = kMinVal;
-        aref = -B * (-side * S[o.qvel + dof]) - K * imp * (dist - margin);
+        dist = side * (m.jnt_range[2 * j + (side + 1) / 2] - q);
+        vel = -side * S[o.qvel + dof];
       } else {
         const int s = src, p = s >> 1;
         const int b1 = m.geom_body[m.pair_g1[p]], b2 = m.geom_body[m.pair_g2[p]];
-        const double margin = m.pair_margin[p], dist = S[o.con_dist + s], mu = m.pair_mu[p];
+        const double mu = rc[SGRL_RC_MU];
+        dist = S[o.con_dist + s];
         double off[3], dir[3];
         const double* fr = S + o.con_frame + o.fstride * s;     // normal, tangent 1; tangent 2 is their cross product (make_frame)
         for (int k = 0; k < 3; k++) off[k] = S[o.con_pos + 3 * s + k] - S[o.misc + MS_COM + k];
@@ -1007,7 +1011,7 @@ struct Engine {
         }
         sgrl_itab_t mk1 = m.body_dofmask + 2 * b1;
         sgrl_itab_t mk2 = m.body_dofmask + 2 * b2;
-        double vel = 0;
+        vel = 0;
         for (int d = 0; d < nv; d++) {
           double sgn = 0;
           if (b2 > 0 && dof_in_mask(mk2, d)) sgn += 1.0;
@@ -1023,35 +1027,42 @@ struct Engine {
           Yr[d] = val;
           vel += val * S[o.qvel + d];
         }
-        double si[5], sr[2], K, B;
-        for (int k = 0; k < 5; k++) si[k] = m.pair_solimp[5 * p + k];
-        sr[0] = m.pair_solref[2 * p]; sr[1] = m.pair_solref[2 * p + 1];
-        const double imp = impedance(si, dist - margin);
-        kb(sr, si, &K, &B);
-        const double tran = m.body_invweight0[2 * b1] + m.body_invweight0[2 * b2];
-        if (kind == ROW_CON1) {
-          Rreg = (1 - imp) / imp * tran;
-          if (Rreg < kMinVal) Rreg = kMinVal;
-        } else {
-          double R0 = (1 - imp) / imp * (tran + mu * mu * tran);
-          if (R0 < kMinVal) R0 = kMinVal;
-          Rreg = 2 * mu * mu * R0;
-          if (Rreg < kMinVal) Rreg = kMinVal;
-        }
-        aref = -B * vel - K * imp * (dist - margin);
       }
+      // what the two kinds of row share, once: impedance at the row's distance, regulariser, reference acceleration
+      const bool pyr = kind == ROW_PYR;
+      const double x = dist - rc[SGRL_RC_MARGIN];
+      const double imp = impedance(rc, x);
+      double Rreg = (1 - imp) / imp * (pyr ? rc[SGRL_RC_RF1] : rc[SGRL_RC_TRAN]);
+      if (Rreg < kMinVal) Rreg = kMinVal;
+      if (pyr) {
+        Rreg = rc[SGRL_RC_RF2] * Rreg;
+        if (Rreg < kMinVal) Rreg = kMinVal;
+      }
+      const double aref = -rc[SGRL_RC_B] * vel - rc[SGRL_RC_K] * imp * x;
       R.eR[r] = Rreg; R.earef[r] = aref;
       // warm start from the previous evaluation of this env-step: same constraint (kind, source, edge) -> same force.  The
-      // memory of the first kPrevRows rows is in LDS, that of the rest (contact-rich states only) in the environment's HBM slab
+      // memory of the first kPrevRows rows is in LDS, that of the rest (contact-rich states only) in the environment's HBM slab.
+      // Between two evaluations of a step the row table rarely changes, so row r looks at index r first and scans the memory
+      // only when another row's key sits there (keys are unique in the memory: the same force either way).
       const int key = (kind << 16) | (src << 3) | sub;
       double f0 = 0;
       const int pn = I[o.icnt + IC_PREV_N];
       const int pcap = o.prevcap, pl = pn < pcap ? pn : pcap;
-      for (int k = 0; k < pl; k++) if (I[o.prev_key + k] == key) f0 = S[o.prev_f + k];
-      if (pn > pcap) {
+      bool hit = false;
+      if (r < pl) {
+        if (I[o.prev_key + r] == key) { f0 = S[o.prev_f + r]; hit = true; }
+      } else if (r < pn) {
         const double* hf = big_scratch + slab_prev_offset(o.maxrows, o.ldy);
         const int32_t* hk = reinterpret_cast<const int32_t*>(hf + o.maxrows);
-        for (int k = pcap; k < pn; k++) if (hk[k] == key) f0 = hf[k];
+        if (hk[r] == key) { f0 = hf[r]; hit = true; }
+      }
+      if (!hit) {
+        for (int k = 0; k < pl; k++) if (I[o.prev_key + k] == key) f0 = S[o.prev_f + k];
+        if (pn > pcap) {
+          const double* hf = big_scratch + slab_prev_offset(o.maxrows, o.ldy);
+          const int32_t* hk = reinterpret_cast<const int32_t*>(hf + o.maxrows);
+          for (int k = pcap; k < pn; k++) if (hk[k] == key) f0 = hf[k];
+        }
       }
       R.ef[r] = f0;
     });

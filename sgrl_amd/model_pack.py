@@ -71,6 +71,53 @@ def _derived_int_tables(model):
     return [depth, path.ravel(), subend, mask.ravel(), dof_act]
 
 
+ROWC = 12            # SGRL_ROWC: doubles per record of pair_rowc / jnt_rowc
+MIN_IMP, MAX_IMP = 0.0001, 0.9999
+
+
+def _row_constants(solref, solimp, margin, mu, tran, timestep):
+    """One SGRL_RC_* record: solimp after its clamps, K and B of solref, and the model-only factors of the row's regulariser
+    (same expressions, in the same association, as the step evaluated per row before the tables existed)."""
+    dmin, dmax, width, mid, power = (float(x) for x in solimp)
+    dmin = min(max(dmin, MIN_IMP), MAX_IMP)
+    dmax = min(max(dmax, MIN_IMP), MAX_IMP)
+    width = max(width, 0.0)
+    mid = min(max(mid, MIN_IMP), MAX_IMP)
+    power = max(power, 1.0)
+    tc, dr = max(float(solref[0]), 2 * float(timestep)), float(solref[1])
+    k = 1.0 / (dmax * dmax * tc * tc * dr * dr)
+    b = 2.0 / (dmax * tc)
+    mu, tran = float(mu), float(tran)
+    return [dmin, dmax, width, mid, power, k, b, float(margin), mu, tran, tran + mu * mu * tran, 2 * mu * mu]
+
+
+def _derived_f64_tables(model):
+    """geom_axis, pair_rowc, jnt_rowc (see include/sgrl_model.h): what depends on the morphology alone."""
+    ng, npair, nj = model.ngeom, model.npair, model.njnt
+    gq = np.asarray(model.geom_quat, dtype=np.float64).reshape(ng, 4)
+    axis = np.empty((ng, 3))
+    axis[:, 0] = 2 * (gq[:, 1] * gq[:, 3] + gq[:, 0] * gq[:, 2])
+    axis[:, 1] = 2 * (gq[:, 2] * gq[:, 3] - gq[:, 0] * gq[:, 1])
+    axis[:, 2] = gq[:, 0] * gq[:, 0] - gq[:, 1] * gq[:, 1] - gq[:, 2] * gq[:, 2] + gq[:, 3] * gq[:, 3]
+    iw_body = np.asarray(model.body_invweight0, dtype=np.float64).reshape(-1, 2)
+    iw_dof = np.asarray(model.dof_invweight0, dtype=np.float64).ravel()
+    p_solref = np.asarray(model.pair_solref, dtype=np.float64).reshape(npair, 2)
+    p_solimp = np.asarray(model.pair_solimp, dtype=np.float64).reshape(npair, 5)
+    pair = np.zeros((npair, ROWC))
+    for p in range(npair):
+        b1 = int(model.geom_body[int(model.pair_g1[p])])
+        b2 = int(model.geom_body[int(model.pair_g2[p])])
+        pair[p] = _row_constants(p_solref[p], p_solimp[p], np.ravel(model.pair_margin)[p], np.ravel(model.pair_mu)[p],
+                                 iw_body[b1, 0] + iw_body[b2, 0], model.timestep)
+    j_solref = np.asarray(model.jnt_solref, dtype=np.float64).reshape(nj, 2)
+    j_solimp = np.asarray(model.jnt_solimp, dtype=np.float64).reshape(nj, 5)
+    jnt = np.zeros((nj, ROWC))
+    for j in range(nj):
+        jnt[j] = _row_constants(j_solref[j], j_solimp[j], np.ravel(model.jnt_margin)[j], 0.0,
+                                iw_dof[int(model.jnt_dofadr[j])], model.timestep)
+    return [axis.ravel(), pair.ravel(), jnt.ravel()]
+
+
 def worst_case_rows(model):
     """Upper bound on simultaneously active constraint rows: one per limited joint + every contact of every pair."""
     rows = int(np.sum(np.asarray(model.jnt_limited) != 0))
@@ -118,4 +165,5 @@ def pack_model(model, spec=None, env_name=None, max_rows=DEFAULT_MAX_ROWS, pgs_i
     fls = [fh]
     for k in mjcf.Model.F64_FIELDS:
         fls.append(np.asarray(getattr(model, k), dtype=np.float64).ravel())
+    fls.extend(_derived_f64_tables(model))
     return np.ascontiguousarray(np.concatenate(ints)), np.ascontiguousarray(np.concatenate(fls))
