@@ -162,6 +162,29 @@ int sgrl_set_forward(sgrl_set* s, const float* obs, int obs_ld, float* act, int 
 int sgrl_set_forward_q(sgrl_set* s, const float* obs, int obs_ld, const float* action, int action_ld, float* q, int q_ld,
                        void* stream);
 
+/* The no-grad half of a TD3 update of a SET agent (reference src/agent.py:126-148: target actor, clipped noise, action clamp, twin
+ * target critics, minimum, Bellman target) as the launches of three forwards and nothing else -- `actor` an actor's handle, `q1` /
+ * `q2` the handles of the two target critics, all three pointed at the same batch structure (mixed morphologies, ragged rows):
+ *   a~[e, k]     = clamp(max_action * tanh(actor(next_obs[e]))[k] + clamp(noise[e, k], +-noise_clip), +-max_action)   k < 3 L_e
+ *   target[e, l] = reward[e] + ((1 - done[e]) * discount) * min(Q1, Q2)(next_obs[e], a~[e])[l]                       l < L_e
+ * next_obs: DEV float [n_env, obs_ld]; noise: DEV float [n_env, noise_ld], the UNCLIPPED draw laid out like an action row (what lies
+ * beyond 3 L_e in a row is never read: a NaN there does not surface); reward, done: DEV float [n_env]; target: DEV float
+ * [n_env, q_ld], exact zeros beyond L_e.  The element-wise steps are epilogue modes of the heads' last kernels (k_head_out /
+ * k_head_out2: the noisy action; k_q_head of the second critic: the target), each one IEEE float32 operation in the order PyTorch
+ * runs agent.py:128-148, never contracted into an FMA: the result equals, bit for bit, sgrl_set_forward -> those PyTorch operations
+ * -> sgrl_set_forward_q twice -> torch.min -> the Bellman line.  (min is symmetric: q1 and q2 may be exchanged.)
+ * The noisy action [n_env, 3 Lmax] (zero beyond 3 L_e) and the first critic's values [n_env, Lmax] live in a region of the actor's
+ * and of q1's workspace behind the forwards' own arrays, which stay where and what they were.  A handle's FIRST chain call reserves
+ * the region: the workspace may regrow (sgrl_set_generation moves, sgrl_set_workspace_bytes grows), so make that call outside any
+ * stream capture -- inside one it is refused.  From then on the handle reserves the region for every batch structure it is given.
+ * Streams: each of the three forwards follows its own rule (one stream for small batches and under capture; the side stream and
+ * the two halves on the eager tile path) and has joined `stream` when the next one starts.
+ * SGRL_ERR_ARG, with nothing launched: a null pointer, two arguments naming one handle, handles whose batch structures differ in
+ * n_env, node count or Lmax, obs_ld < 41 Lmax, noise_ld < 3 Lmax, q_ld < Lmax, noise_clip < 0, max_action <= 0. */
+int sgrl_set_td_target(sgrl_set* actor, sgrl_set* q1, sgrl_set* q2, const float* next_obs, int obs_ld, const float* noise,
+                       int noise_ld, const float* reward, const float* done, float max_action, float noise_clip, float discount,
+                       float* target, int q_ld, void* stream);
+
 int sgrl_set_num_nodes(const sgrl_set* s);
 int64_t sgrl_set_workspace_bytes(const sgrl_set* s);
 /* Counter bumped whenever the handle FREES device memory that a forward recorded earlier may point into: a batch structure

@@ -605,11 +605,47 @@ __global__ __launch_bounds__(128) void k_equiv(const float* __restrict__ T, cons
   }
 }
 
+// Epilogue modes of the three head kernels (sgrl_set_td_target: the no-grad half of a TD3 update, reference agent.py:126-148, as the
+// three forwards' own launches).  TD_PLAIN is the forward as it always was.  The other modes act on the value the kernel holds in a
+// register, one IEEE float32 operation per step of the reference's chain, in PyTorch's order and never contracted into an FMA:
+//   TD_ACTION (actor heads)  a~ = clamp(a + clamp(noise[env][3 limb + k], +-noise_clip), +-max_action)          agent.py:128-134
+//   TD_TARGET (critic head)  reward[env] + ((1 - done[env]) * discount) * min(q_other[env][limb], q)            agent.py:136-148
+// Only the slots of real limbs are read: what lies beyond 3 L_e in a noise row never reaches a result.
+enum { TD_PLAIN = 0, TD_ACTION = 1, TD_TARGET = 2 };
+struct TdEpi {
+  const float* noise = nullptr; int noise_ld = 0; float noise_clip = 0.f;       // TD_ACTION
+  const float* q_other = nullptr; int q_other_ld = 0;                           // TD_TARGET: the first critic's plain values
+  const float *reward = nullptr, *done = nullptr; float discount = 0.f;         //            DEV float[n_env] each
+};
+__device__ __forceinline__ float td_clamp(float v, float bound) { return fminf(fmaxf(v, -bound), bound); }   // torch.clamp on a number
+// one rounding each: with contraction off the operation carries no licence to fuse with a neighbouring product or sum
+__device__ __forceinline__ float td_add(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ float td_sub(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+__device__ __forceinline__ float td_mul(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float td_action(float a, const TdEpi& td, int env, int slot, float max_action) {
+  const float nz = td_clamp(td.noise[(size_t)env * td.noise_ld + slot], td.noise_clip);
+  return td_clamp(td_add(a, nz), max_action);
+}
+__device__ __forceinline__ float td_target(float q, const TdEpi& td, int env, int limb) {
+  const float m = fminf(td.q_other[(size_t)env * td.q_other_ld + limb], q);
+  return td_add(td.reward[env], td_mul(td_mul(td_sub(1.0f, td.done[env]), td.discount), m));
+}
+
 // head: vec[s] = T[n][s][:] . wdec (T = Zh . mat from the linear2_m GEMM's epilogue); action_k = max_action * tanh(sum_s
 // axis_k[s] * vec[s]); 32 lanes per node
+template <int MODE>
 __global__ __launch_bounds__(128) void k_head_out(const float* __restrict__ T, const float* __restrict__ wdec,
                                                   const float* __restrict__ obs, int obs_ld, NodeTab nt, float* act, int act_ld,
-                                                  float max_action, int N) {
+                                                  float max_action, int N, TdEpi td) {
   const int n = blockIdx.x * 4 + (threadIdx.x >> 5), c = threadIdx.x & 31;
   if (n >= N) return;
   float vec[3];
@@ -623,15 +659,19 @@ __global__ __launch_bounds__(128) void k_head_out(const float* __restrict__ T, c
     const int env = nt.node_env[n], limb = nt.node_limb[n];
     const float* o = obs + (size_t)env * obs_ld + 41 * limb + 3 * (5 + c);
     const float a = o[0] * vec[0] + o[1] * vec[1] + o[2] * vec[2];
-    act[(size_t)env * act_ld + 3 * limb + c] = max_action * tanhf(a);
+    if (MODE == TD_ACTION)
+      act[(size_t)env * act_ld + 3 * limb + c] = td_action(max_action * tanhf(a), td, env, 3 * limb + c, max_action);
+    else
+      act[(size_t)env * act_ld + 3 * limb + c] = max_action * tanhf(a);
   }
 }
 
 
 // head with decoder_g folded through linear2_m (include/sgrl_set.h): m2[n][q] = (Wf . h[n] + bf)[q] / fn[n] comes out of a 32-wide
 // product; vec[s] = z[n][s][:] . m2[n][:]; action_k = max_action * tanh(sum_s axis_k[s] * vec[s]); 32 lanes per node
+template <int MODE>
 __global__ __launch_bounds__(128) void k_head_out2(const float* __restrict__ m2, const float* __restrict__ z, const float* __restrict__ obs,
-                                                   int obs_ld, NodeTab nt, float* act, int act_ld, float max_action, int N) {
+                                                   int obs_ld, NodeTab nt, float* act, int act_ld, float max_action, int N, TdEpi td) {
   const int n = blockIdx.x * 4 + (threadIdx.x >> 5), c = threadIdx.x & 31;
   if (n >= N) return;
   float vec[3];
@@ -645,18 +685,29 @@ __global__ __launch_bounds__(128) void k_head_out2(const float* __restrict__ m2,
     const int env = nt.node_env[n], limb = nt.node_limb[n];
     const float* o = obs + (size_t)env * obs_ld + 41 * limb + 3 * (5 + c);
     const float a = o[0] * vec[0] + o[1] * vec[1] + o[2] * vec[2];
-    act[(size_t)env * act_ld + 3 * limb + c] = max_action * tanhf(a);
+    if (MODE == TD_ACTION)
+      act[(size_t)env * act_ld + 3 * limb + c] = td_action(max_action * tanhf(a), td, env, 3 * limb + c, max_action);
+    else
+      act[(size_t)env * act_ld + 3 * limb + c] = max_action * tanhf(a);
   }
 }
 
 // critic head: q[env][limb] = (w . c[n] + b) / fn[n]   (reference SEActor.py:279-281 with output_size = 1); one wave per node
+template <int MODE>
 __global__ __launch_bounds__(256) void k_q_head(const float* __restrict__ c, const float* __restrict__ w, const float* __restrict__ b,
-                                                const float* __restrict__ fn, NodeTab nt, float* q, int q_ld, int N) {
+                                                const float* __restrict__ fn, NodeTab nt, float* q, int q_ld, int N, TdEpi td) {
   const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (n >= N) return;
   const float* row = c + (size_t)n * 256;
   float v = row[lane] * w[lane] + row[64 + lane] * w[64 + lane] + row[128 + lane] * w[128 + lane] + row[192 + lane] * w[192 + lane];
   v = wave_sum_f32(v);
+  if (MODE == TD_TARGET) {
+    if (lane == 0) {
+      const int env = nt.node_env[n], limb = nt.node_limb[n];
+      q[(size_t)env * q_ld + limb] = td_target((v + b[0]) / fn[n], td, env, limb);
+    }
+    return;
+  }
   if (lane == 0) q[(size_t)nt.node_env[n] * q_ld + nt.node_limb[n]] = (v + b[0]) / fn[n];
 }
 
@@ -700,6 +751,11 @@ struct sgrl_set {
   float* ws = nullptr;
   int64_t ws_floats = 0;
   int carved_N = 0;
+  // sgrl_set_td_target: a region behind the forward's arrays -- the noisy target action [n_env, 3 Lmax] on the actor's handle, the
+  // first critic's values [n_env, Lmax] on that critic's.  Reserved from the handle's first chain call on (td_region), for every
+  // batch structure it is pointed at; no forward reads or writes it
+  bool td_region = false;
+  float* td_buf = nullptr;
   float* cat_cur = nullptr;    // which of cat / cat2 holds [inv | ng] after the last forward (the fused form alternates: run_forward)
   float *g, *cat, *cat2, *zc, *fn, *h256, *qkv, *vg, *g1, *z2, *mat, *t256, *t256b, *t128a, *t128b, *delta,
       *outg, *outng, *gdir;
@@ -757,6 +813,8 @@ constexpr int64_t kPerNodeFloats = 384 /*g*/ + 256 + 256 /*cat, cat2*/ + 96 /*zc
 constexpr int kWsArrays = 19;
 
 int64_t ws_floats_for(int64_t N) { return kPerNodeFloats * N + 32 * kWsArrays; }
+// the chain's region of a batch structure (either role: an action row is the wider one)
+int64_t td_floats_for(const GraphCfg* c) { return ((int64_t)c->n_env * 3 * c->Lmax + 31) & ~int64_t(31); }
 
 void free_graphs(sgrl_set* s) {
   for (GraphCfg* c : s->cfgs) { c->release(); delete c; }
@@ -793,7 +851,7 @@ void pick_split(const std::vector<int32_t>& env_off, int N, int* env_out, int* n
 // point the handle at a cached batch structure; (re)carve the shared workspace for its node count
 int use_cfg(sgrl_set* s, GraphCfg* c) {
   const int64_t N = c->N;
-  const int64_t need = ws_floats_for(N);
+  const int64_t need = ws_floats_for(N) + (s->td_region ? td_floats_for(c) : 0);
   if (need > s->ws_floats) {
     if (s->ws) { (void)hipFree(s->ws); s->generation++; }       // hipFree waits for the device: no kernel still reads the old block
     s->ws = nullptr; s->ws_floats = 0; s->carved_N = 0;
@@ -810,6 +868,7 @@ int use_cfg(sgrl_set* s, GraphCfg* c) {
     if (p - s->ws > s->ws_floats) return sfail(SGRL_ERR_LIMIT, "workspace carve-up overflow");
     s->carved_N = c->N;
   }
+  s->td_buf = s->td_region ? s->ws + ws_floats_for(N) : nullptr;     // behind the arrays carved above, whatever their block
   s->n_env = c->n_env; s->N = c->N; s->n_morph = c->n_morph; s->TM = c->TM; s->Lmax = c->Lmax;
   s->split_env = c->split_env; s->split_node = c->split_node;
   s->d_node_env = c->d_node_env; s->d_node_limb = c->d_node_limb; s->d_node_mnode = c->d_node_mnode; s->d_trav = c->d_trav;
@@ -1147,6 +1206,8 @@ struct Forward {
   GemmCtx gx;
   NodeTab nt;
   EnvTab et;
+  int td_mode = TD_PLAIN;            // epilogue of the head's last kernel (sgrl_set_td_target); TD_PLAIN: td is not read
+  TdEpi td;
 
   // Independent GEMM chains go to the side stream: fork() makes it wait for everything issued so far on the part's stream, join()
   // makes that stream wait for it.  The chains' store-heavy epilogues and partial last tile waves overlap each other.
@@ -1371,7 +1432,8 @@ struct Forward {
   int head_out(const Part& p) const {
     const int N = p.M;
     if (critic) {     // slots reused by the critic head: DECG = decoder_ng.weight [256], L1M_B = decoder_ng.bias [1]
-      hipLaunchKernelGGL(k_q_head, dim3((N + 3) / 4), dim3(256), 0, p.st, p.cato, s->W(SGRL_SET_DECG), s->W(SGRL_SET_L1M_B), p.fn, p.nt, act, act_ld, N);
+      auto* const kq = td_mode == TD_TARGET ? k_q_head<TD_TARGET> : k_q_head<TD_PLAIN>;
+      hipLaunchKernelGGL(kq, dim3((N + 3) / 4), dim3(256), 0, p.st, p.cato, s->W(SGRL_SET_DECG), s->W(SGRL_SET_L1M_B), p.fn, p.nt, act, act_ld, N, td);
       return SGRL_OK;
     }
     int rc = gemm(p.st, p.cato, 256, s->W(SGRL_SET_L1M_W), 256, s->W(SGRL_SET_L1M_B), p.t256, 256, N, 256, 256, EPI_RELU);
@@ -1380,12 +1442,14 @@ struct Forward {
       // decoder_g folded through linear2_m: the 1024-wide product and its contraction collapse into a 32-wide product
       rc = gemm(p.st, p.t256, 256, s->l2mf_w, 256, s->l2mf_b, p.mat, 32, N, 32, 256, EPI_ROWDIV, p.fn);
       if (rc != SGRL_OK) return rc;
-      hipLaunchKernelGGL(k_head_out2, dim3((N + 3) / 4), dim3(128), 0, p.st, p.mat, p.z2, obs, obs_ld, p.nt, act, act_ld, max_action, N);
+      auto* const k2 = td_mode == TD_ACTION ? k_head_out2<TD_ACTION> : k_head_out2<TD_PLAIN>;
+      hipLaunchKernelGGL(k2, dim3((N + 3) / 4), dim3(128), 0, p.st, p.mat, p.z2, obs, obs_ld, p.nt, act, act_ld, max_action, N, td);
       return SGRL_OK;
     }
     rc = equiv_gemm(p, p.t256, s->W(SGRL_SET_L2M_W), s->W(SGRL_SET_L2M_B));
     if (rc != SGRL_OK) return rc;
-    hipLaunchKernelGGL(k_head_out, dim3((N + 3) / 4), dim3(128), 0, p.st, p.mat, s->W(SGRL_SET_DECG), obs, obs_ld, p.nt, act, act_ld, max_action, N);
+    auto* const k1 = td_mode == TD_ACTION ? k_head_out<TD_ACTION> : k_head_out<TD_PLAIN>;
+    hipLaunchKernelGGL(k1, dim3((N + 3) / 4), dim3(128), 0, p.st, p.mat, s->W(SGRL_SET_DECG), obs, obs_ld, p.nt, act, act_ld, max_action, N, td);
     return SGRL_OK;
   }
   int stage(Part& p, int k) const {
@@ -1417,9 +1481,10 @@ GemmCtx gemm_ctx_of(const sgrl_set* s) {
 }
 
 int run_forward(sgrl_set* s, const float* obs, int obs_ld, float* act, int act_ld, float max_action, hipStream_t st,
-                bool critic = false, const float* action = nullptr, int action_ld = 0) {
+                bool critic = false, const float* action = nullptr, int action_ld = 0, int td_mode = TD_PLAIN, const TdEpi* td = nullptr) {
   const int N = s->N;
   Forward f{s, obs, obs_ld, act, act_ld, max_action, critic, action, action_ld, st};
+  if (td_mode != TD_PLAIN) { f.td_mode = td_mode; f.td = *td; }
   f.gx = gemm_ctx_of(s);
   f.ngf = critic ? 20 : 17;
   f.nt = NodeTab{s->d_node_env, s->d_node_limb, s->d_node_mnode, s->d_trav, s->TM};
@@ -1770,6 +1835,43 @@ int sgrl_set_forward_q(sgrl_set* s, const float* obs, int obs_ld, const float* a
   if (obs_ld < 41 * s->Lmax || action_ld < 3 * s->Lmax || q_ld < s->Lmax)
     return sfail(SGRL_ERR_ARG, "sgrl_set_forward_q: obs_ld < 41 * Lmax, action_ld < 3 * Lmax or q_ld < Lmax");
   return run_forward(s, obs, obs_ld, q, q_ld, 0.f, (hipStream_t)stream, true, action, action_ld);
+}
+
+int sgrl_set_td_target(sgrl_set* actor, sgrl_set* q1, sgrl_set* q2, const float* next_obs, int obs_ld, const float* noise, int noise_ld,
+                       const float* reward, const float* done, float max_action, float noise_clip, float discount, float* target, int q_ld,
+                       void* stream) {
+  if (!actor || !q1 || !q2 || !next_obs || !noise || !reward || !done || !target) return sfail(SGRL_ERR_ARG, "sgrl_set_td_target: null argument");
+  if (actor == q1 || actor == q2 || q1 == q2) return sfail(SGRL_ERR_ARG, "sgrl_set_td_target: three networks need three handles");
+  for (const sgrl_set* h : {actor, q1, q2})
+    if (!h->have_w || !h->have_graph || !h->cur) return sfail(SGRL_ERR_ARG, "sgrl_set_td_target: weights or graph not set");
+  for (const sgrl_set* h : {q1, q2})
+    if (h->n_env != actor->n_env || h->N != actor->N || h->Lmax != actor->Lmax)
+      return sfail(SGRL_ERR_ARG, "sgrl_set_td_target: the handles hold different batch structures");
+  const int Lmax = actor->Lmax;
+  if (obs_ld < 41 * Lmax || noise_ld < 3 * Lmax || q_ld < Lmax)
+    return sfail(SGRL_ERR_ARG, "sgrl_set_td_target: obs_ld < 41 * Lmax, noise_ld < 3 * Lmax or q_ld < Lmax");
+  if (!(noise_clip >= 0.f) || !(max_action > 0.f)) return sfail(SGRL_ERR_ARG, "sgrl_set_td_target: noise_clip < 0 or max_action <= 0");
+  hipStream_t st = (hipStream_t)stream;
+  // the regions of the noisy action and of the first critic's values: reserved by the first chain call of a handle (the workspace
+  // may have to regrow, which frees the old block) -- never inside a stream capture
+  for (sgrl_set* h : {actor, q1}) {
+    if (h->td_region && h->td_buf) continue;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(st, &cap);
+    if (cap != hipStreamCaptureStatusNone)
+      return sfail(SGRL_ERR_ARG, "sgrl_set_td_target: the first call on these handles must happen outside a stream capture (it reserves workspace)");
+    h->td_region = true;
+    const int rc = use_cfg(h, h->cur);
+    if (rc != SGRL_OK) return rc;
+  }
+  TdEpi ea, et;
+  ea.noise = noise; ea.noise_ld = noise_ld; ea.noise_clip = noise_clip;
+  et.q_other = q1->td_buf; et.q_other_ld = Lmax; et.reward = reward; et.done = done; et.discount = discount;
+  float* const a_t = actor->td_buf;     // [n_env, 3 Lmax]: every forward zeroes its output rows first, so slots beyond 3 L_e stay zero
+  int rc = run_forward(actor, next_obs, obs_ld, a_t, 3 * Lmax, max_action, st, false, nullptr, 0, TD_ACTION, &ea);
+  if (rc == SGRL_OK) rc = run_forward(q1, next_obs, obs_ld, q1->td_buf, Lmax, 0.f, st, true, a_t, 3 * Lmax);
+  if (rc == SGRL_OK) rc = run_forward(q2, next_obs, obs_ld, target, q_ld, 0.f, st, true, a_t, 3 * Lmax, TD_TARGET, &et);
+  return rc;
 }
 
 int sgrl_set_time_forward(sgrl_set* s, const float* obs, int obs_ld, float* act, int act_ld, float max_action,

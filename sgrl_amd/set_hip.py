@@ -6,6 +6,8 @@ rebuilds its flat weight buffer from the live storage at the top of every forwar
 reference's `target_param.data.copy_(...)` soft updates (common/functional.py:7-10, invisible to version counters)
 and `load_state_dict` are all seen by the next call.  It also describes the batch structure (morphologies x env
 counts) to the engine and runs `actions = max_action * tanh(actor(obs))` for all environments in one call.
+`HipSetCritic` pairs two such handles over the twin critics of an `SECritic`; `HipSetTargets` runs the no-grad half of a
+TD3 update over the target modules' handles as one library call (sgrl_set_td_target).
 No CPU fallback: a missing extension or device raises `SgrlError`.
 """
 import ctypes
@@ -51,6 +53,8 @@ def _bind(L):
     ci = ctypes.c_int
     L.sgrl_set_debug_product.argtypes = [vp, ci, ci, vp, ci, vp, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp]
     L.sgrl_set_debug_chain.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp]
+    cf = ctypes.c_float
+    L.sgrl_set_td_target.argtypes = [vp, vp, vp, vp, ci, vp, ci, vp, vp, cf, cf, cf, vp, ci, vp]
     L._set_bound = True
 
 
@@ -495,6 +499,10 @@ class HipSetActor(object):
         """The layer-0 fold of the fused tile path (include/sgrl_set.h): False = layer 0 runs unfolded like the others (A/B, tests)."""
         _check(self.L, self.L.sgrl_set_debug_l0fold(self.h, 1 if on else 0), "sgrl_set_debug_l0fold")
 
+    def generation(self):
+        """include/sgrl_set.h sgrl_set_generation: moves whenever the handle frees device memory a recorded forward may point into."""
+        return int(self.L.sgrl_set_generation(self.h))
+
     def last_split(self):
         """Nodes in the first half of the last forward; 0: it ran as a single pass (include/sgrl_set.h, the two-half forward)."""
         return int(self.L.sgrl_set_last_split(self.h))
@@ -530,6 +538,7 @@ class HipSetCritic(object):
     two handles, one per TransformerModel, sharing the batch structure."""
 
     def __init__(self, critic_module, device=None):
+        self.module = critic_module
         self.q1 = HipSetActor(critic_module, device=device, net=critic_module.critic1, critic=True)
         self.q2 = HipSetActor(critic_module, device=device, net=critic_module.critic2, critic=True)
 
@@ -550,3 +559,55 @@ class HipSetCritic(object):
         B, L = state.shape[0], len(graph["parents"])
         self.configure([graph], [B])
         return self.forward_batch(state.contiguous().float(), action.contiguous().float(), q_ld=L, which=which)
+
+
+class HipSetTargets(object):
+    """The no-grad half of a TD3 update of a SET agent (reference src/agent.py:126-148) on the HIP path: the cached handles of the
+    target actor (`SEPolicy._hip`) and of the twin target critics (`SECritic._hip_handles()`), created where absent, and `target_q`
+    over sgrl_set_td_target -- the three forwards' launches and nothing else; the noisy target action and the first critic's values
+    never leave the handles' workspaces.  `q1` / `q2` are the critic handles in the order the library is given them."""
+
+    def __init__(self, actor_target, critic_target):
+        if not torch.cuda.is_available():
+            raise _lib.SgrlError("HipSetTargets needs an MI355X (no CPU fallback)")
+        if getattr(actor_target, "_hip", None) is None:
+            actor_target._hip = HipSetActor(actor_target)
+        self.actor = actor_target._hip
+        self.critic = critic_target._hip_handles()
+        self.q1, self.q2 = self.critic.q1, self.critic.q2
+        self.L, self.device = self.actor.L, self.actor.device
+        if self.actor.critic or not (self.q1.critic and self.q2.critic):
+            raise _lib.SgrlError("HipSetTargets needs an actor's handle and two critics' handles")
+
+    def configure(self, graphs, counts):
+        self.actor.configure(graphs, counts)
+        self.critic.configure(graphs, counts)
+
+    def target_q(self, next_obs, noise, reward, done, graph, noise_clip, discount, counts=None, out=None, q_ld=None):
+        """reward + (1 - done) * discount * min(Q1_t, Q2_t)(next_obs, clamp(actor_t(next_obs) + clamp(noise, +-noise_clip),
+        +-max_action)) per limb -> float32 [B, q_ld], exact zeros beyond L_e.  next_obs [B, >= 41 Lmax], noise [B, >= 3 Lmax] (the
+        unclipped draw, laid out like an action row), reward / done [B] or [B, 1].  graph: the morphology's graph dict, or a list of
+        them with `counts` environments each (row blocks in that order)."""
+        graphs = graph if isinstance(graph, (list, tuple)) else [graph]
+        self.configure(graphs, counts if counts is not None else [next_obs.shape[0]])
+        a = self.actor
+        for t, per_limb, what in ((next_obs, 41, "observation"), (noise, 3, "noise")):
+            assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == a.n_env, what
+            assert t.shape[1] >= per_limb * a.max_limbs, "%s rows narrower than %d * max_limbs" % (what, per_limb)
+        reward, done = reward.reshape(-1), done.reshape(-1)
+        for t in (reward, done):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape[0] == a.n_env
+        a.sync_weights()
+        self.q1.sync_weights()
+        self.q2.sync_weights()
+        q_ld = q_ld or a.max_limbs
+        assert q_ld >= a.max_limbs
+        if out is None:
+            out = torch.empty((a.n_env, q_ld), dtype=torch.float32, device=self.device)
+        assert out.is_contiguous() and out.shape == (a.n_env, q_ld)
+        vp, cf = ctypes.c_void_p, ctypes.c_float
+        _check(self.L, self.L.sgrl_set_td_target(a.h, self.q1.h, self.q2.h, vp(next_obs.data_ptr()), a._ld(next_obs),
+                                                 vp(noise.data_ptr()), a._ld(noise), vp(reward.data_ptr()), vp(done.data_ptr()),
+                                                 cf(float(a.policy.max_action)), cf(float(noise_clip)), cf(float(discount)),
+                                                 vp(out.data_ptr()), int(q_ld), a._stream()), "sgrl_set_td_target")
+        return out

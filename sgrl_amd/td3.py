@@ -305,17 +305,23 @@ SMP_TRAIN_KERNELS_DEFAULT = False
 # neg_mean: one launch each way instead of about a dozen; float64 sums, so the last bit of a loss may differ from PyTorch's) when the
 # caller does not say: opt-in, no learning curve has been run with it
 LOSS_KERNELS_DEFAULT = False
+# Whether a set + set agent on the GPU runs the no-grad target chain of its update as ONE library call over the target modules' HIP
+# handles (set_hip.HipSetTargets, include/sgrl_set.h sgrl_set_td_target: the three forwards' launches and nothing else) when the
+# caller does not say: opt-in (no update-time table yet).  Takes effect where the target critics' no-grad forward is two
+# passes of the rollout kernels (set_policy.TWIN_TARGETS = False); with the default twin pass the chain yields (Agent._hip_targets)
+SET_HIP_TARGETS_DEFAULT = False
 
 
 class Agent(nn.Module):
     def __init__(self, args, device=None, use_hip=True, mlp_hip_grads=None, mlp_hip_optim=None, swat_train_kernels=None,
-                 smp_train_kernels=None, loss_kernels=None):
+                 smp_train_kernels=None, loss_kernels=None, set_hip_targets=None):
         super().__init__()
         self.args = args
         atype, ctype = getattr(args, "actor_type", "set"), getattr(args, "critic_type", "set")
         if atype not in ("set", "swat", "smp", "mlp") or ctype not in ("set", "swat", "smp", "mlp"):
             raise NotImplementedError("actor / critic types 'set', 'swat', 'smp' and 'mlp' are built (the actors with a batched HIP forward for "
                                       "collection, smp in its td and bu mode; the target chain of a swat, an smp (td and bu) or an mlp update on HIP, "
+                                      "that of a set update as one call over the HIP forwards where `set_hip_targets` says so, "
                                       "the differentiable passes of those updates on the training kernels where `swat_train_kernels` / "
                                       "`smp_train_kernels` / `mlp_hip_grads` say so, in PyTorch otherwise); got actor_type %r, critic_type %r"
                                       % (atype, ctype))
@@ -390,6 +396,17 @@ class Agent(nn.Module):
         # chain packs from the live target parameters, so soft updates and load_state_dict need no notification
         self.use_mlp_hip = bool(use_hip) and atype == "mlp" and ctype == "mlp"
         self._mlp_targets = None
+        # set_hip_targets: a SET actor AND critic run the chain as one call over the target modules' own HIP handles
+        # (set_hip.HipSetTargets); None: args.set_hip_targets, then SET_HIP_TARGETS_DEFAULT.  Follows use_hip; ignored by every other
+        # agent type.  Off, or on a CPU / float64 batch: the PyTorch chain of update_targets around the modules' forwards -- and so
+        # wherever the target critics' no-grad forward is the twin pass of the training kernels (set_policy.TWIN_TARGETS, the
+        # default): the chain replaces the two-forward route only, whose results it reproduces bit for bit (_hip_targets)
+        if set_hip_targets is None:
+            set_hip_targets = getattr(args, "set_hip_targets", None)
+        if set_hip_targets is None:
+            set_hip_targets = SET_HIP_TARGETS_DEFAULT
+        self.use_set_hip = bool(use_hip) and atype == "set" and ctype == "set" and bool(set_hip_targets)
+        self._set_targets = None
         # mlp_hip_grads: the gradient half of an mlp + mlp update (critics' forward, both losses, both backward passes) on the HIP
         # kernels too (mlp_hip.HipMlpGrads), for float32 batches on the GPU; None: MLP_HIP_GRADS_DEFAULT.  Follows use_hip; ignored by
         # every other agent type and on the CPU
@@ -446,6 +463,7 @@ class Agent(nn.Module):
         d["_swat_targets"] = None     # per-process device handles: never pickled / deep-copied with the agent
         d["_smp_targets"] = None
         d["_mlp_targets"] = None
+        d["_set_targets"] = None
         d["_mlp_grads"] = None
         d["_mlp_optim"] = None
         return d
@@ -491,11 +509,25 @@ class Agent(nn.Module):
         return o
 
     def _hip_targets(self, next_obs):
-        """swat_hip.HipSwatTargets / smp_hip.HipSmpTargets / mlp_hip.HipMlpTargets when this update's target chain runs on HIP, else
-        None."""
-        if not ((self.use_swat_hip or self.use_smp_hip or self.use_mlp_hip) and next_obs.is_cuda and next_obs.dtype == torch.float32 and
-                self.device.type == "cuda"):
+        """swat_hip.HipSwatTargets / smp_hip.HipSmpTargets / mlp_hip.HipMlpTargets / set_hip.HipSetTargets when this update's target
+        chain runs on HIP, else None."""
+        if not ((self.use_swat_hip or self.use_smp_hip or self.use_mlp_hip or self.use_set_hip) and next_obs.is_cuda and
+                next_obs.dtype == torch.float32 and self.device.type == "cuda"):
             return None
+        if self.use_set_hip:
+            from . import set_policy
+            if set_policy.TWIN_TARGETS and set_policy.TWIN_CRITICS and train_ops.ENABLED:
+                # The switch promises the switch-off agent's results bit for bit.  Here that agent's `critic_target(...)` is ONE twin
+                # pass of the training kernels (SECritic.forward), another kernel family than the chain's two forwards: their values
+                # differ by rounding (measured 3.0e-8 in a target), so the chain yields and update_targets stays the code it was.  It
+                # runs where SECritic.forward itself takes two passes of the rollout kernels (set_policy.TWIN_TARGETS = False,
+                # TWIN_CRITICS = False, SGRL_TRAIN_GEMM=0).
+                return None
+            t = self._set_targets
+            if t is None or t.actor.policy is not self.actor_target or t.critic.module is not self.critic_target:
+                from .set_hip import HipSetTargets      # raises SgrlError when the extension is missing (no fallback)
+                t = self._set_targets = HipSetTargets(self.actor_target, self.critic_target)
+            return t
         if self.use_swat_hip and self.dropout_rate > 0 and (self.actor_target.training or self.critic_target.training):
             return None      # the HIP chain has no dropout: targets in training mode run the modules, as the reference's do
         if self.use_smp_hip:
@@ -730,8 +762,8 @@ def _no_finalizers_during_capture():
 
 
 def target_handles(targets):
-    """The library handles behind a swat_hip.HipSwatTargets (target actor, critic.q1, critic.q2) or an smp_hip.HipSmpTargets (target
-    actor, target critic); none for None."""
+    """The library handles behind a swat_hip.HipSwatTargets or a set_hip.HipSetTargets (target actor, critic.q1, critic.q2) or an
+    smp_hip.HipSmpTargets (target actor, target critic); none for None."""
     if targets is None:
         return []
     c = targets.critic
@@ -764,7 +796,9 @@ class GraphedUpdates(object):
     former forks onto the handle's side stream, which the warm-up creates) and, with `swat_train_kernels` / `smp_train_kernels`,
     its differentiable passes on the training kernels.  The stamp of a graph then also covers that target object's handles
     (`handles_stamp`), and a capture is refused (RuntimeError) when the target object is not the one the slot's warm-up ran with.
-    The three-graph form (`split`) is not built for it.  `captures[(key, flag)]` counts the captures of each graph; `stale(key, flag)`
+    The three-graph form (`split`) is not built for it.  A SET agent built with `set_hip_targets` records its one-call chain
+    (set_hip.HipSetTargets) with either value of hip_kernels -- its HIP forwards are recorded in both -- under the same two rules: the
+    chain's first call, which reserves workspace, is made by the warm-up's eager updates.  `captures[(key, flag)]` counts the captures of each graph; `stale(key, flag)`
     says, launching nothing, whether a captured graph would be dropped by the next update of that kind."""
 
     def __init__(self, agent, batch_size, hip_kernels=False):
@@ -832,8 +866,9 @@ class GraphedUpdates(object):
 
     def _targets(self, sl):
         """The object whose target chain an update on this slot records -- what `Agent._hip_targets` returns NOW (it re-creates the
-        object when a target module has been replaced) -- or None: without hip_kernels, and for agents whose chain is PyTorch."""
-        if not self.hip_kernels:
+        object when a target module has been replaced) -- or None: without hip_kernels, and for agents whose chain is PyTorch.  A SET
+        agent's chain object (`set_hip_targets`) counts with either value of hip_kernels: its forwards are recorded in both."""
+        if not self.hip_kernels and not getattr(self.agent, "use_set_hip", False):
             return None
         return self.agent._hip_targets(sl["batch"]["next_obs"])
 
