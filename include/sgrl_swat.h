@@ -128,6 +128,44 @@ int sgrl_swat_td_target(sgrl_swat* actor_t, sgrl_swat* q1_t, sgrl_swat* q2_t, co
 /* Launches of one sgrl_swat_forward_twin (2 x 22, on two streams) and of one sgrl_swat_td_target (3 x 22). */
 int sgrl_swat_twin_launches(void);
 int sgrl_swat_td_target_launches(void);
+
+/* ---- networks in TRAINING mode: counter-RNG dropout inside the forwards (reference src/agent.py:118-121 puts all four networks
+ * into training mode for an update, so the three target networks of a TD3 update drop) ----------------------------------------
+ * The three entries below are sgrl_swat_forward / _forward_q / _td_target with the masks of include/sgrl_train.h "counter-RNG
+ * dropout" (csrc/dropout_rng.h, nothing else) applied inside the row kernels:
+ *   word = replay_word(seed, *step_dev, 0x100 + site, i),  keep = word >= floor(p * 2^32),  y = keep ? x * (1 / (1 - p)) : 0
+ * step_dev: DEV uint64, read by the kernels (the host never learns it: a recorded call moves with the device word).  One network
+ * has sgrl_swat_dropout_sites() = 13 sites, numbered in the program order of swat_policy.TransformerModel.forward; i is the
+ * row-major index in the tensor the module drops (B environments of L limbs, node n = b L + l):
+ *   site 0        pos_encoder output [L, 128]            i = 128 l + c                  on pos before it is added (ONE mask for
+ *                                                                                         every environment, as the module's)
+ *   site 1 + 4k   softmax weights of layer k [B, 2, L, L]  i = ((2 b + h) L + i) L + j    after normalisation, before the w . v sum
+ *   site 2 + 4k   dropout1: out_proj output [B, L, 128]   i = 128 n + c                  before the residual sum of norm1
+ *   site 3 + 4k   dropout: relu(linear1) [B, L, 256]      i = 256 n + c                  one element-wise launch between the products
+ *   site 4 + 4k   dropout2: linear2 output [B, L, 128]    i = 128 n + c                  before the residual sum of norm2
+ * A single network uses sites site0 .. site0 + 12.  site_map (tests; NULL = the identity): HOST int32[13], site k of the network
+ * becomes site0 + site_map[k].  25 launches per network (sgrl_swat_dropout_launches), the plain entries keep their 22.
+ * A row whose weights are all dropped gives exact zeros; p = 0 gives the plain entry's bits; p = 1 drops everything and stays
+ * finite.  Recordable into a hipGraph under the plain entries' rule (a handle's first calls are made outside a capture).
+ * SGRL_ERR_ARG, nothing launched: everything the plain entry refuses; p outside [0, 1] or NaN; step_dev null; site0 < 0 or a
+ * last site beyond 2^24 - 1; a batch structure of more than one morphology (the indices above are the modules' only then: an
+ * update batch is one morphology). */
+int sgrl_swat_forward_dropout(sgrl_swat* s, const float* obs, int obs_ld, float* act, int act_ld, float max_action, float p,
+                              uint64_t seed, const uint64_t* step_dev, int site0, const int32_t* site_map, void* stream);
+int sgrl_swat_forward_q_dropout(sgrl_swat* s, const float* obs, int obs_ld, const float* action, int act_ld, int act_feature, float* q,
+                                int q_ld, float p, uint64_t seed, const uint64_t* step_dev, int site0, const int32_t* site_map,
+                                void* stream);
+/* The chain takes 39 sites, in the order Agent.update_targets runs the modules (critic1 before critic2 in
+ * CriticStructurePolicy.forward): the target actor site0 .. + 12, the first critic site0 + 13 .. + 25, the second critic
+ * site0 + 26 .. + 38.  The second critic still runs on the first handle's side stream; the noise, clamp, min and Bellman
+ * epilogues are those of sgrl_swat_td_target.  75 launches (sgrl_swat_td_target_dropout_launches). */
+int sgrl_swat_td_target_dropout(sgrl_swat* actor_t, sgrl_swat* q1_t, sgrl_swat* q2_t, const float* next_obs, int obs_ld,
+                                const float* noise, int noise_ld, const float* reward, const float* done, float max_action,
+                                float noise_clip, float discount, float* target_q, int q_ld, float p, uint64_t seed,
+                                const uint64_t* step_dev, int site0, void* stream);
+int sgrl_swat_dropout_sites(void);
+int sgrl_swat_dropout_launches(void);
+int sgrl_swat_td_target_dropout_launches(void);
 /* Measurements only (process-wide): 0 = the twin's second chain follows the first on the caller's stream; 1 (default) = side stream. */
 int sgrl_swat_debug_twin_streams(int on);
 

@@ -10,6 +10,12 @@ every entry point raises `_lib.SgrlError`.
 `HipSwatCritic` is the same over the two networks of a `CriticStructurePolicy` (per-limb Q values, single or twin, the surface
 of set_hip.HipSetCritic); `HipSwatTargets` runs the no-grad half of a TD3 update -- target actor, clipped noise, twin target
 critics, min and Bellman target (reference src/agent.py:126-148) -- as one library call (`td3.Agent.update_targets`).
+
+Dropout: the forwards take an optional `dropout=(p, seed, step_tensor, site0)` and then run the library's dropout entries
+(sgrl_swat_forward_dropout / _forward_q_dropout / _td_target_dropout) -- the forward of a module in TRAINING mode under a
+train_ops.dropout_rng context with that (seed, step), the network's 13 sites numbered from site0 in the order of
+`dropout_site_plan()`.  Batches of one morphology only.  Without the argument nothing changes: a module in training mode with
+dropout > 0 is refused, collection and evaluation run dropout-free in eval mode.
 """
 import ctypes
 
@@ -56,6 +62,22 @@ def plan_params(net):
     return plan
 
 
+# The dropout sites of ONE network in the program order of swat_policy.TransformerModel.forward: (kind, layer, shape of the tensor the
+# module drops as a function of (B, L)); the element index of a mask is the row-major index in that tensor.  The one host-side
+# statement of the order: site k of a network is site0 + k (include/sgrl_swat.h has the kernels' side of the table)
+SITES_PER_NET = 1 + 4 * LAYERS
+
+
+def dropout_site_plan():
+    """[(kind, layer, shape(B, L))] * 13: 'pos' (pos_encoder's output, layer None), then per layer 'attn' (softmax weights),
+    'dropout1' (out_proj's output), 'dropout' (ReLU(linear1)) and 'dropout2' (linear2's output)."""
+    plan = [("pos", None, lambda B, L: (L, 128))]
+    for l in range(LAYERS):
+        plan += [("attn", l, lambda B, L: (B, 2, L, L)), ("dropout1", l, lambda B, L: (B, L, 128)),
+                 ("dropout", l, lambda B, L: (B, L, 256)), ("dropout2", l, lambda B, L: (B, L, 128))]
+    return plan
+
+
 def _bind(L):
     if getattr(L, "_swat_bound", False):
         return
@@ -77,6 +99,16 @@ def _bind(L):
     L.sgrl_swat_forward_twin.restype = ci
     L.sgrl_swat_td_target.argtypes = [vp, vp, vp, vp, ci, vp, ci, vp, vp, cf, cf, cf, vp, ci, vp]
     L.sgrl_swat_td_target.restype = ci
+    u64 = ctypes.c_uint64
+    L.sgrl_swat_forward_dropout.argtypes = [vp, vp, ci, vp, ci, cf, cf, u64, vp, ci, vp, vp]
+    L.sgrl_swat_forward_dropout.restype = ci
+    L.sgrl_swat_forward_q_dropout.argtypes = [vp, vp, ci, vp, ci, ci, vp, ci, cf, u64, vp, ci, vp, vp]
+    L.sgrl_swat_forward_q_dropout.restype = ci
+    L.sgrl_swat_td_target_dropout.argtypes = [vp, vp, vp, vp, ci, vp, ci, vp, vp, cf, cf, cf, vp, ci, cf, u64, vp, ci, vp]
+    L.sgrl_swat_td_target_dropout.restype = ci
+    for name in ("sgrl_swat_dropout_sites", "sgrl_swat_dropout_launches", "sgrl_swat_td_target_dropout_launches"):
+        getattr(L, name).argtypes = []
+        getattr(L, name).restype = ci
     L.sgrl_swat_twin_launches.argtypes = []
     L.sgrl_swat_twin_launches.restype = ci
     L.sgrl_swat_td_target_launches.argtypes = []
@@ -138,10 +170,11 @@ class HipSwatActor(object):
         named = dict(self.net.named_parameters())
         return [named[n] for n, _ in self.plan]
 
-    def sync_weights(self, force=False):
+    def sync_weights(self, force=False, dropout=False):
         """Bind the handle to the parameters' storage (include/sgrl_swat.h sgrl_swat_bind_params).  The VALUES are read by every
-        forward; this binds again only when a parameter's address moved (module.to(), re-created tensors) or with force."""
-        if self.net.training and getattr(self.net, "dropout", 0.0) > 0.0:
+        forward; this binds again only when a parameter's address moved (module.to(), re-created tensors) or with force.
+        dropout=True: the caller runs a dropout entry, which is the forward of a module in training mode."""
+        if not dropout and self.net.training and getattr(self.net, "dropout", 0.0) > 0.0:
             # every forward of this handle comes through here: the kernels behind it have no dropout, and training mode asks for it
             raise _lib.SgrlError("the HIP forward of a SWAT network has no dropout: the module is in training mode with dropout %g "
                                  "(call eval() for collection / evaluation; an update's passes run the modules)" % self.net.dropout)
@@ -205,19 +238,46 @@ class HipSwatActor(object):
     def _ld(t):
         return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
 
-    def forward_batch(self, obs, out=None, act_ld=None):
+    def dropout_args(self, dropout, site_map=None, with_map=False):
+        """`dropout=(p, seed, step_tensor, site0)` -> the trailing ctypes arguments (p, seed, step_dev, site0[, site_map]) of a
+        dropout entry.  step_tensor: a one-element int64 tensor on the handle's device, which the kernels read."""
+        p, seed, step, site0 = dropout
+        if not (torch.is_tensor(step) and step.dtype == torch.int64 and step.numel() == 1 and step.is_contiguous()
+                and step.device == self.device):
+            raise _lib.SgrlError("dropout=(p, seed, step_tensor, site0): step_tensor must be a one-element int64 tensor on %s" % (self.device,))
+        args = [ctypes.c_float(float(p)), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), ctypes.c_void_p(step.data_ptr()), int(site0)]
+        if with_map:                     # the single-network entries: a HOST int32[13], read during the call, or NULL
+            sm = None if site_map is None else np.ascontiguousarray(site_map, dtype=np.int32)
+            assert sm is None or sm.shape == (SITES_PER_NET,)
+            args.append(ctypes.c_void_p(None if sm is None else sm.ctypes.data))
+            self._site_map = sm          # alive over the call
+        return args
+
+    def dropout_launches(self):
+        """Kernel launches of one dropout forward (constant)."""
+        return int(self.L.sgrl_swat_dropout_launches())
+
+    def forward_batch(self, obs, out=None, act_ld=None, dropout=None, site_map=None):
         """obs: float32 CUDA [n_env, obs_ld] -> actions float32 [n_env, act_ld] (StructurePolicy.forward for every environment;
-        slots beyond out * L_e of a row are exact zeros)."""
+        slots beyond out * L_e of a row are exact zeros).  dropout=(p, seed, step_tensor, site0): the forward of the module in
+        training mode, sites site0 .. site0 + 12 (one morphology; site_map: tests, include/sgrl_swat.h)."""
         assert obs.is_cuda and obs.dtype == torch.float32 and obs.dim() == 2 and obs.stride(1) == 1
         assert obs.shape[0] == self.n_env
         assert obs.shape[1] >= self.feature * self.max_limbs, "observation rows narrower than feature * max_limbs"
-        self.sync_weights()
+        self.sync_weights(dropout=dropout is not None)
         act_ld = act_ld or self.out_dim * self.max_limbs
         assert act_ld >= self.out_dim * self.max_limbs, "action rows narrower than out * max_limbs"
         if out is None:
             out = torch.empty((self.n_env, act_ld), dtype=torch.float32, device=self.device)
         assert out.is_contiguous() and out.shape == (self.n_env, act_ld)
         stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        if dropout is not None:
+            extra = self.dropout_args(dropout, site_map, with_map=True)
+            _check(self.L, self.L.sgrl_swat_forward_dropout(self.h, ctypes.c_void_p(obs.data_ptr()), self._ld(obs),
+                                                            ctypes.c_void_p(out.data_ptr()), int(act_ld),
+                                                            ctypes.c_float(float(self.policy.max_action)), *extra, stream),
+                   "sgrl_swat_forward_dropout")
+            return out
         _check(self.L, self.L.sgrl_swat_forward(self.h, ctypes.c_void_p(obs.data_ptr()), self._ld(obs),
                                                 ctypes.c_void_p(out.data_ptr()), int(act_ld),
                                                 ctypes.c_float(float(self.policy.max_action)), stream), "sgrl_swat_forward")
@@ -230,18 +290,25 @@ class HipSwatActor(object):
         assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == self.n_env, what
         assert t.shape[1] >= per_limb * self.max_limbs, "%s rows narrower than %d * max_limbs" % (what, per_limb)
 
-    def forward_q(self, obs, action, out=None, q_ld=None):
+    def forward_q(self, obs, action, out=None, q_ld=None, dropout=None, site_map=None):
         """Critic network (a handle over CriticStructurePolicy.critic1 / .critic2): obs [n_env, obs_ld], action [n_env, act_ld]
-        (out_dim-of-the-actor slots per limb) -> per-limb Q [n_env, q_ld], exact zeros beyond L_e."""
+        (out_dim-of-the-actor slots per limb) -> per-limb Q [n_env, q_ld], exact zeros beyond L_e.  dropout: as forward_batch."""
         act_feature = self.act_feature                # 0 on an actor's handle: the library refuses it
         self.check_rows(obs, self.feature - act_feature, "observation")
         self.check_rows(action, act_feature, "action")
-        self.sync_weights()
+        self.sync_weights(dropout=dropout is not None)
         q_ld = q_ld or self.max_limbs
         assert q_ld >= self.max_limbs
         if out is None:
             out = torch.empty((self.n_env, q_ld), dtype=torch.float32, device=self.device)
         assert out.is_contiguous() and out.shape == (self.n_env, q_ld)
+        if dropout is not None:
+            extra = self.dropout_args(dropout, site_map, with_map=True)
+            _check(self.L, self.L.sgrl_swat_forward_q_dropout(self.h, ctypes.c_void_p(obs.data_ptr()), self._ld(obs),
+                                                              ctypes.c_void_p(action.data_ptr()), self._ld(action), act_feature,
+                                                              ctypes.c_void_p(out.data_ptr()), int(q_ld), *extra, self._stream()),
+                   "sgrl_swat_forward_q_dropout")
+            return out
         _check(self.L, self.L.sgrl_swat_forward_q(self.h, ctypes.c_void_p(obs.data_ptr()), self._ld(obs),
                                                   ctypes.c_void_p(action.data_ptr()), self._ld(action), act_feature,
                                                   ctypes.c_void_p(out.data_ptr()), int(q_ld), self._stream()), "sgrl_swat_forward_q")
@@ -280,9 +347,15 @@ class HipSwatCritic(object):
         """Kernel launches of one twin forward (constant)."""
         return int(self.L.sgrl_swat_twin_launches())
 
-    def forward_batch(self, obs, action, q_ld=None, which=(1, 2)):
+    def forward_batch(self, obs, action, q_ld=None, which=(1, 2), dropout=None):
         """obs [n_env, obs_ld], action [n_env, act_ld] (float32 CUDA) -> tuple of per-limb Q [n_env, q_ld], one per network in
-        `which`; slots beyond L_e of a row are exact zeros."""
+        `which`; slots beyond L_e of a row are exact zeros.  dropout=(p, seed, step_tensor, site0): the networks in training mode,
+        one dropout forward each, the networks of `which` taking 13 sites each from site0 in their order (CriticStructurePolicy.
+        forward: critic1 site0 .. + 12, critic2 site0 + 13 .. + 25; Q1 alone: site0 .. + 12)."""
+        if dropout is not None:
+            p, seed, step, site0 = dropout
+            nets = [h for k, h in ((1, self.q1), (2, self.q2)) if k in which]
+            return tuple(h.forward_q(obs, action, q_ld=q_ld, dropout=(p, seed, step, site0 + SITES_PER_NET * n)) for n, h in enumerate(nets))
         if not (1 in which and 2 in which):
             return tuple(h.forward_q(obs, action, q_ld=q_ld) for k, h in ((1, self.q1), (2, self.q2)) if k in which)
         q1 = self.q1
@@ -328,11 +401,17 @@ class HipSwatTargets(object):
         """Kernel launches of one target chain (constant)."""
         return int(self.L.sgrl_swat_td_target_launches())
 
-    def target_q(self, next_obs, noise, reward, done, graph, noise_clip, discount, counts=None, out=None, q_ld=None):
+    def dropout_launches(self):
+        """Kernel launches of one target chain with dropout (constant)."""
+        return int(self.L.sgrl_swat_td_target_dropout_launches())
+
+    def target_q(self, next_obs, noise, reward, done, graph, noise_clip, discount, counts=None, out=None, q_ld=None, dropout=None):
         """reward + (1 - done) * discount * min(Q1_t, Q2_t)(next_obs, clamp(actor_t(next_obs) + clamp(noise, +-noise_clip),
         +-max_action)) per limb -> float32 [B, q_ld].  next_obs [B, >= 41 Lmax], noise [B, >= 3 Lmax] (the unclipped draw, laid
         out like an action row), reward / done [B] or [B, 1].  graph: the morphology's graph dict, or a list of them with
-        `counts` environments each (row blocks in that order)."""
+        `counts` environments each (row blocks in that order).  dropout=(p, seed, step_tensor, site0): the three target networks in
+        training mode (one morphology): the target actor takes sites site0 .. + 12, critic1 + 13 .. + 25, critic2 + 26 .. + 38, the
+        order `Agent.update_targets` runs the modules in."""
         graphs = graph if isinstance(graph, (list, tuple)) else [graph]
         self.configure(graphs, counts if counts is not None else [next_obs.shape[0]])
         a = self.actor
@@ -341,15 +420,21 @@ class HipSwatTargets(object):
         reward, done = reward.reshape(-1), done.reshape(-1)
         for t in (reward, done):
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape[0] == a.n_env
-        a.sync_weights()
-        self.critic.q1.sync_weights()
-        self.critic.q2.sync_weights()
+        for h in (a, self.critic.q1, self.critic.q2):
+            h.sync_weights(dropout=dropout is not None)
         q_ld = q_ld or a.max_limbs
         assert q_ld >= a.max_limbs
         if out is None:
             out = torch.empty((a.n_env, q_ld), dtype=torch.float32, device=self.device)
         assert out.is_contiguous() and out.shape == (a.n_env, q_ld)
         vp, cf = ctypes.c_void_p, ctypes.c_float
+        if dropout is not None:
+            _check(self.L, self.L.sgrl_swat_td_target_dropout(a.h, self.critic.q1.h, self.critic.q2.h, vp(next_obs.data_ptr()), a._ld(next_obs),
+                                                              vp(noise.data_ptr()), a._ld(noise), vp(reward.data_ptr()), vp(done.data_ptr()),
+                                                              cf(float(a.policy.max_action)), cf(float(noise_clip)), cf(float(discount)),
+                                                              vp(out.data_ptr()), int(q_ld), *a.dropout_args(dropout), a._stream()),
+                   "sgrl_swat_td_target_dropout")
+            return out
         _check(self.L, self.L.sgrl_swat_td_target(a.h, self.critic.q1.h, self.critic.q2.h, vp(next_obs.data_ptr()), a._ld(next_obs),
                                                   vp(noise.data_ptr()), a._ld(noise), vp(reward.data_ptr()), vp(done.data_ptr()),
                                                   cf(float(a.policy.max_action)), cf(float(noise_clip)), cf(float(discount)),

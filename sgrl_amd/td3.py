@@ -310,11 +310,17 @@ LOSS_KERNELS_DEFAULT = False
 # caller does not say: opt-in (no update-time table yet).  Takes effect where the target critics' no-grad forward is two
 # passes of the rollout kernels (set_policy.TWIN_TARGETS = False); with the default twin pass the chain yields (Agent._hip_targets)
 SET_HIP_TARGETS_DEFAULT = False
+# Whether a swat + swat agent with dropout_rate > 0 runs the target chain of an update -- whose three networks are then in training
+# mode, as the reference's are -- on the HIP chain's dropout entries (swat_hip.HipSwatTargets.target_q(dropout=...),
+# include/sgrl_swat.h sgrl_swat_td_target_dropout: 75 launches) instead of the modules under torch.no_grad() with the torch
+# restatement of the counter RNG, when the caller does not say: opt-in (profiles/swat_dropout_chain.json).  The masks are
+# the same function of (seed, step, site, index) either way; the values differ by float32 rounding
+SWAT_HIP_DROPOUT_DEFAULT = False
 
 
 class Agent(nn.Module):
     def __init__(self, args, device=None, use_hip=True, mlp_hip_grads=None, mlp_hip_optim=None, swat_train_kernels=None,
-                 smp_train_kernels=None, loss_kernels=None, set_hip_targets=None):
+                 smp_train_kernels=None, loss_kernels=None, set_hip_targets=None, swat_hip_dropout=None):
         super().__init__()
         self.args = args
         atype, ctype = getattr(args, "actor_type", "set"), getattr(args, "critic_type", "set")
@@ -440,6 +446,15 @@ class Agent(nn.Module):
         self.dropout_rate = float(getattr(args, "dropout_rate", 0.0) or 0.0) if "swat" in (atype, ctype) else 0.0
         self.dropout_seed = int(getattr(args, "seed", 0) or 0)
         self._dropout_step = None
+        # swat_hip_dropout: with dropout_rate > 0 and the target networks in training mode, the target chain runs the HIP chain's
+        # dropout entries and takes the 39 site numbers the three modules would have taken (update_targets); None:
+        # args.swat_hip_dropout, then SWAT_HIP_DROPOUT_DEFAULT.  Follows use_hip; ignored by every other agent type.  Off: such a
+        # chain runs the modules (_hip_targets returns None)
+        if swat_hip_dropout is None:
+            swat_hip_dropout = getattr(args, "swat_hip_dropout", None)
+        if swat_hip_dropout is None:
+            swat_hip_dropout = SWAT_HIP_DROPOUT_DEFAULT
+        self.swat_hip_dropout = self.use_swat_hip and bool(swat_hip_dropout)
 
     def set_swat_train_kernels(self, on):
         """Turn the training kernels of the online swat networks on or off (no other agent type has the switch)."""
@@ -529,7 +544,10 @@ class Agent(nn.Module):
                 t = self._set_targets = HipSetTargets(self.actor_target, self.critic_target)
             return t
         if self.use_swat_hip and self.dropout_rate > 0 and (self.actor_target.training or self.critic_target.training):
-            return None      # the HIP chain has no dropout: targets in training mode run the modules, as the reference's do
+            # the plain HIP chain has no dropout: targets in training mode run the modules, as the reference's do -- unless the switch
+            # hands them to the chain's dropout entries, which serve the three networks in ONE mode (_targets_drop)
+            if not (self.swat_hip_dropout and self.actor_target.training and self.critic_target.training):
+                return None
         if self.use_smp_hip:
             t = self._smp_targets
             if t is None or t.actor.policy is not self.actor_target or t.critic.module is not self.critic_target:
@@ -550,6 +568,11 @@ class Agent(nn.Module):
             from .swat_hip import HipSwatTargets    # raises SgrlError when the extension is missing (no fallback)
             t = self._swat_targets = HipSwatTargets(self.actor_target, self.critic_target)
         return t
+
+    def _targets_drop(self):
+        """True when the HIP chain `_hip_targets` has just returned must DROP: a swat agent with a rate > 0 whose target networks
+        are (both) in training mode -- `_hip_targets` returns a chain for that only with `swat_hip_dropout`."""
+        return bool(self.use_swat_hip and self.dropout_rate > 0 and self.actor_target.training and self.critic_target.training)
 
     @property
     def device(self):
@@ -627,6 +650,20 @@ class Agent(nn.Module):
             if noise is None:
                 noise = torch.zeros_like(action_batch).normal_(0, args.policy_noise)
             hip = self._hip_targets(next_obs_batch)
+            if hip is not None and self._targets_drop():
+                # the three target networks in training mode on the chain's dropout entries: the masks of this update's context,
+                # and the 39 site numbers the modules would take here (actor_target, critic1, critic2: 13 each, in that order), so
+                # that the online passes behind number from 39 as they do behind the modules.  Outside a context the modules would
+                # draw from torch's generator, which no kernel restates: they run
+                rng = train_ops._rng
+                if rng is None or rng.step.device != next_obs_batch.device:
+                    hip = None
+                else:
+                    from .swat_hip import SITES_PER_NET
+                    target_Q = hip.target_q(next_obs_batch.contiguous(), noise.contiguous(), reward_batch, done_batch,
+                                            self.actor_target.graph, args.noise_clip, args.discount,
+                                            dropout=(self.dropout_rate, rng.seed, rng.step, rng.reserve(3 * SITES_PER_NET)))
+                    return reward_batch, target_Q
             if hip is not None:      # one library call: target actor, noise clip and clamp, twin target critics, min, Bellman target
                 target_Q = hip.target_q(next_obs_batch.contiguous(), noise.contiguous(), reward_batch, done_batch,
                                         self.actor_target.graph, args.noise_clip, args.discount)
@@ -799,17 +836,32 @@ class GraphedUpdates(object):
     The three-graph form (`split`) is not built for it.  A SET agent built with `set_hip_targets` records its one-call chain
     (set_hip.HipSetTargets) with either value of hip_kernels -- its HIP forwards are recorded in both -- under the same two rules: the
     chain's first call, which reserves workspace, is made by the warm-up's eager updates.  `captures[(key, flag)]` counts the captures of each graph; `stale(key, flag)`
-    says, launching nothing, whether a captured graph would be dropped by the next update of that kind."""
+    says, launching nothing, whether a captured graph would be dropped by the next update of that kind.
+
+    Dropout (`agent.dropout_rate` > 0): accepted with hip_kernels=True on an agent whose target chain runs the HIP dropout entries
+    (`use_swat_hip` and `swat_hip_dropout`), refused otherwise.  The step counter's increment is recorded, the site numbers are baked
+    in, the stamp also carries the four networks' `training` flags and the step tensor's address (see __init__)."""
+
+    dropout = False       # True: the agent's updates drop (dropout_rate > 0) and are captured with the HIP chain's dropout entries
 
     def __init__(self, agent, batch_size, hip_kernels=False):
         self.agent, self.B = agent, int(batch_size)
         self.hip_kernels = bool(hip_kernels)
-        self.captures = {}         # (key, flag) -> number of times that graph has been captured
+        self.captures = {}       # (key, flag) -> number of times that graph has been captured
         if getattr(agent.args, "actor_type", "set") == "mlp":
             raise NotImplementedError("GraphedUpdates is not built for 'mlp' agents: run their updates eagerly (DeviceTrainer(graph_updates=False))")
-        if getattr(agent, "dropout_rate", 0.0) > 0:
+        self.dropout = getattr(agent, "dropout_rate", 0.0) > 0
+        if self.dropout and not (self.hip_kernels and getattr(agent, "use_swat_hip", False) and getattr(agent, "swat_hip_dropout", False)):
             # the site numbers of an update are host state and its passes differ between training and eval mode: nobody has made the
-            # capture of a dropout update sound, so it is refused rather than replayed with stale masks
+            # capture of a dropout update sound where the targets run the modules, so it is refused rather than replayed with stale
+            # masks.  With the HIP chain's dropout entries (hip_kernels and the agent's swat_hip_dropout) it is sound:
+            #   - the step is a device word: `Agent._dropout_rng`'s increment is RECORDED, every replay moves the masks, and every
+            #     kernel reads the word itself; the warm-up's eager updates create the tensor before any capture, and
+            #     `_check_capture` refuses a capture on another tensor than the slot was warmed with;
+            #   - the site numbers are baked in and right in every replay: the program order of an update is fixed per
+            #     (morphology, flag);
+            #   - the passes an update runs depend on the four networks' `training` flags: they and the step tensor's address are
+            #     part of a graph's stamp (`_stamp`), a mismatch captures again
             raise NotImplementedError("GraphedUpdates does not replay updates with dropout (dropout_rate %g): run them eagerly "
                                       "(DeviceTrainer(graph_updates=False)) or set dropout_rate to 0" % agent.dropout_rate)
         dev = agent.device
@@ -875,7 +927,13 @@ class GraphedUpdates(object):
     def _stamp(self, sl):
         """The stamp of a graph on this slot: the SET handles' (`_workspace_stamp`) and, with hip_kernels, the SWAT / SMP target
         handles' (`handles_stamp`: three for SWAT, two for SMP)."""
-        return (self._workspace_stamp(), handles_stamp(target_handles(self._targets(sl))))
+        base = (self._workspace_stamp(), handles_stamp(target_handles(self._targets(sl))))
+        if not self.dropout:
+            return base
+        a = self.agent
+        step = a._dropout_step
+        return base + (tuple(bool(m.training) for m in (a.actor, a.actor_target, a.critic, a.critic_target)),
+                       None if step is None else int(step.data_ptr()))
 
     def stale(self, key, flag):
         """True when a graph has been captured for (key, flag) and its stamp is no longer the current one: the next update of that
@@ -899,6 +957,10 @@ class GraphedUpdates(object):
             raise RuntimeError("the agent's HIP target chain is not the one morphology %r was warmed with (a target network has been "
                                "replaced, or the chain was switched on or off): warm(%r, ...) again before the next graphed update"
                                % (key, key))
+        if self.dropout and (self.agent._dropout_step is None or self.agent._dropout_step is not sl.get("dropout_step")):
+            # the graph records the increment of, and every kernel's reads from, the step tensor the warm-up's updates created
+            raise RuntimeError("the agent's dropout step tensor is not the one morphology %r was warmed with: warm(%r, ...) again before "
+                               "the next graphed update" % (key, key))
 
     def _load(self, sl, data_batch):
         for k, t in sl["batch"].items():
@@ -935,6 +997,7 @@ class GraphedUpdates(object):
         self.warmed.add(key)
         if outs:
             sl["targets"] = self._targets(sl)   # (hip_kernels) whose first calls have now happened outside any capture
+            sl["dropout_step"] = self.agent._dropout_step      # (dropout) created by the first eager update
         return outs
 
     def update(self, key, graph, L, data_batch, it):

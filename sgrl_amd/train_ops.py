@@ -896,6 +896,13 @@ class DropoutRng(object):
         self.site = s + 1
         return s
 
+    def reserve(self, n):
+        """The running site number, advanced by n: for a caller that runs n dropout calls behind ONE library call (the HIP target
+        chain of a SWAT update: 39) and takes their numbers in program order, where the calls themselves would have."""
+        s = self.site
+        self.site = s + int(n)
+        return s
+
 
 @contextlib.contextmanager
 def dropout_rng(seed, step_tensor):
