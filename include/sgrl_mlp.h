@@ -173,7 +173,9 @@ int sgrl_mlp_actor_step_launches(void);  /* 4 */
  * Replaces, for ONE handle (an actor, 1 stack, or a critic, 2 stacks) whose parameters and gradients are bound, clip_grad_norm_ +
  * Adam.step (reference src/agent.py:161-164, 174-177) and, with tau > 0, the soft update of the network's target
  * (common/functional.py:7-10), in TWO launches:
- *   coef = max_norm > 0 ? fminf(1, max_norm / (sqrtf(total) + 1e-6f)) : none        total = sum of g^2 over every bound gradient
+ *   coef = max_norm > 0 ? min(1, max_norm / (sqrtf(total) + 1e-6f)) : none          total = sum of g^2 over every bound gradient
+ *          (a NaN total gives a NaN coef, as torch.clamp(coef, max=1.0) does in clip_grad_norm_: every g, m, v, p and target of the
+ *          handle becomes NaN; an infinite total gives coef = 0; a select, not fminf, which would return 1 for a NaN)
  *   g   := g * coef               (written back to .grad when max_norm > 0, as clip_grad_norm_ does)
  *   t    = the first bound step counter, after every bound counter has been advanced by 1
  *   m   := b1 m + (1 - b1) g;   v := b2 v + (1 - b2) g g;   p := p - (lr / (1 - b1^t)) * m / (sqrtf(v) / sqrtf(1 - b2^t) + eps)

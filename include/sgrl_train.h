@@ -150,6 +150,9 @@ int sgrl_embed3_backward(const long long* idx, const float* dout, float* dw0, fl
  *     place (torch.nn.utils.clip_grad_norm_); every step += 1; Adam exactly as torch's fused kernel (no weight decay, no amsgrad):
  *     m = lerp(m, g, 1 - b1), v = b2 v + (1 - b2) g^2, p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps).
  *     scratch: 1 + n_chunks floats (total of squares, partials).  Three launches (two without clipping), fixed summation order.
+ *     Non-finite gradients go the way clip_grad_norm_ sends them (its torch.clamp(coef, max=1.0) lets a NaN through): a NaN
+ *     anywhere gives a NaN total and a NaN factor, so every gradient, moment and parameter of the table becomes NaN; an infinite
+ *     total gives the factor 0 (the infinite element itself becomes NaN, every other gradient 0).  Finite totals: min(1, .) exactly.
  *   sgrl_optim_lerp: rows (dst*, src*, -, -, -, numel): dst = dst (1 - tau) + tau src.  One launch. */
 int sgrl_optim_chunk(void);
 int sgrl_optim_clip_adam(const void* table, int n_tensors, const void* chunks, int n_chunks, double lr, double beta1, double beta2, double eps,

@@ -13,8 +13,8 @@
 //
 //   k_mlp_opt_norm    partial[c] = sum of g^2 over chunk c;  workgroup 0 also advances every bound step counter by 1.
 //                     With max_norm == 0 the squares are skipped (one workgroup, the counters only).
-//   k_mlp_opt_apply   total = sum of all partials (every workgroup, itself); coef = min(1, max_norm / (sqrt(total) + 1e-6));
-//                     g *= coef (written back, as clip_grad_norm_ does); Adam; target = target (1 - tau) + tau p with the p just written.
+//   k_mlp_opt_apply   total = sum of all partials (every workgroup, itself); coef = min(1, max_norm / (sqrt(total) + 1e-6)),
+//                     NaN for a NaN total; g *= coef (written back, as clip_grad_norm_ does); Adam; target = target (1 - tau) + tau p with the p just written.
 //
 // ORDER OF THE SUM (fixed, so a step is bit-repeatable; no atomics).  A thread adds its four squares in element order (4 additions
 // from 0); a wave adds its 64 lanes by a butterfly (xor 32, 16, 8, 4, 2, 1: 6 additions); the four waves' sums are added in wave
@@ -114,7 +114,9 @@ __global__ __launch_bounds__(256) void k_mlp_opt_apply(OptArgs a, int n_chunks, 
     float s = 0.f;
     for (int i = threadIdx.x; i < n_chunks; i += 256) s += a.partial[i];
     const float total = group_sum(s, red);
-    c.coef = fminf(1.0f, max_norm / (sqrtf(total) + 1e-6f));
+    // a select, not fminf: a NaN total gives a NaN coef, as torch.clamp(coef, max=1.0) does in clip_grad_norm_ (k_opt_adam)
+    const float ratio = max_norm / (sqrtf(total) + 1e-6f);
+    c.coef = ratio > 1.0f ? 1.0f : ratio;
   }
   const double t = (double)*a.step[0];                        // already advanced by k_mlp_opt_norm
   const float bc1 = (float)(1.0 - pow(b1, t));

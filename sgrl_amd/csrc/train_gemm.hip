@@ -1214,7 +1214,7 @@ __global__ __launch_bounds__(128) void k_embed3_bwd(Embed3 e, const float* __res
 // numel), the work is cut into chunks of kOptChunk elements ((tensor, first element) pairs), one workgroup per chunk:
 //   k_opt_sqnorm   partial[c] = sum of grad^2 over chunk c
 //   k_opt_total    total = sum_c partial[c] in chunk order (one workgroup; bit-reproducible); every tensor's step += 1
-//   k_opt_adam     g *= min(1, max_norm / (sqrt(total) + 1e-6))  (written back, as clip_grad_norm_ does);  Adam as torch's fused kernel
+//   k_opt_adam     g *= min(1, max_norm / (sqrt(total) + 1e-6))  (written back, as clip_grad_norm_ does; NaN for a NaN total);  Adam as torch's fused kernel
 //                  computes it: m = lerp(m, g, 1 - b1), v = b2 v + (1 - b2) g g, p -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 //   k_opt_lerp     dst = dst (1 - tau) + tau src   (table rows: dst, src, -, -, -, numel)
 constexpr int kOptChunk = 1024;
@@ -1253,7 +1253,10 @@ __global__ __launch_bounds__(256) void k_opt_adam(const OptRow* __restrict__ tab
   const int2 c = chunks[blockIdx.x];
   const OptRow r = tab[c.x];
   const long long end = min(r.n, (long long)c.y + kOptChunk);
-  const float coef = total ? fminf(1.0f, max_norm / (sqrtf(*total) + 1e-6f)) : 1.0f;
+  // a select, not fminf: a NaN total (a NaN gradient anywhere in the table) gives a NaN coef, as torch.clamp(coef, max=1.0) does in
+  // clip_grad_norm_; an infinite total gives coef = 0; for finite totals the bits are fminf's
+  const float ratio = total ? max_norm / (sqrtf(*total) + 1e-6f) : 1.0f;
+  const float coef = ratio > 1.0f ? 1.0f : ratio;
   const double t = (double)*r.step;                               // already advanced by k_opt_total
   const float bc1 = (float)(1.0 - pow(b1, t));
   const float bc2_sqrt = sqrtf((float)(1.0 - pow(b2, t)));

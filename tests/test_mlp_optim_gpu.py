@@ -10,6 +10,10 @@ td3.Agent(mlp_hip_grads=True, mlp_hip_optim=True)) on the MI355X.
    (the floor: the longest chain of additions into the gradient norm is 128 at most, 128 * 2^-24 = 7.6e-6 relative on `total`,
    half of that on coef, at most that on g^2; the factor 10 is test_mlp_grads_gpu._check_grads'); for p and the target the
    project's step bar, 2e-3 |step64| + sqrt(numel) max|x| 1.2e-7.
+   The same bars where Adam's eps decides the step: gradients from tests/optim_restate.py's generator, every tensor at 1e-11 and
+   scales 1e-13 ... 1e-2 mixed across the tensors, three steps from the seeded parameters and from parameters at zero (which resolve
+   a step of 1e-7: the step bar's floor vanishes).  And one NaN / one inf element in one gradient: the NaN pattern of both parent
+   paths and of the restatement in g, m, v, p and the target of every tensor, the finite values under the same bars.
 2  bit-exact: tau = 1 leaves target == p; max_norm = 0 and an inactive clip give the same p, m, v and leave .grad alone; zero
    gradients from fresh state leave p alone and everything finite; the same state twice gives the same bits; tau = 0 leaves the
    targets alone; a critic step leaves the actor's side alone and the reverse
@@ -26,6 +30,12 @@ inactive); p and the target sit at 6e-3 of the step bar and below; the [1, 7] ne
 Twenty agent updates: |new - parent| 0 ... 1.4e-7 per tensor under tolerances of 7.5e-7 ... 1.3e-3.  The reference replay: critic loss
 2.52044296 / 1.08880043 against 2.52044344 / 1.08880043, step norms within 8.8e-3 of their tolerance.  Two deliberately wrong builds fail:
 bias correction at t - 1 fails 19 of the 22 tests, the lerp reading the pre-step parameter 15.
+Where eps decides, worst error / bar from the seeded parameters | from zero: [1, 7] critic 0.36 | 0.018 (1e-11) and 0.50 | 0.012 (mixed),
+actor 0.56 | 0.006 and 0.66 | 0.008; [40, 72] critic 0.42 | 0.009 and 0.29 | 0.019, actor 0.26 | 0.007 and 0.22 | 0.016 (from the seeded
+parameters the figure is the rounding of p itself against the bar's floor; from zero it is the step's error against 2e-3 of the step).
+Non-finite: NaN with the clip, every value of the side (1 550 / 1 050 / 83 450 / 42 845) NaN on all three paths and in float64; NaN without
+the clip and inf with it, 5 values (the element in g, m, v, p, target); inf without the clip, 2 (p and the target: inf / inf).  The build
+with fminf for the clip factor (the code before) fails both NaN cases.
 """
 import ctypes
 import functools
@@ -35,6 +45,7 @@ import numpy as np
 import pytest
 import torch
 
+import optim_restate
 from mlp_optim_restate import step_restated
 from mlp_restate import apply_seeded_
 
@@ -237,6 +248,91 @@ def test_step_against_float64(L, hidden):
                     what = "L%d %s %s %s clip %s tau %g" % (L, hidden, s, "step 1000" if preload else "fresh", clip, tau)
                     worst = max(worst, _one_case(tw, s, what, state, gsteps, tau, hip_capturable=(L == 7)))
         print("L%d %s %s: worst error / bar %.3g" % (L, hidden, s, worst))
+
+
+def _generated(tw, s, kind, seed):
+    """Gradients of side s from optim_restate's generator (per tensor sign * scale * 2^U(-1, 1)): 'tiny' -- every tensor at 1e-11,
+    where Adam's eps decides the step -- or 'mixed' -- scales 1e-13 ... 1e-2 across the tensors."""
+    shapes = [tuple(p.shape) for p in tw.params(s)]
+    return [torch.from_numpy(x).cuda() for x in optim_restate.draw_gradients(shapes, optim_restate.tensor_scales(kind, shapes, seed=3), seed)]
+
+
+def _zero_start(tw, s):
+    """The fresh state of side s with every parameter at zero: such parameters resolve any step (the step bar's floor vanishes)."""
+    st = tw.state(s)
+    return dict(st, p=[torch.zeros_like(x) for x in st["p"]])
+
+
+@pytest.mark.parametrize("L,hidden", [(3, (1, 7)), (3, (40, 72))], ids=["L3-1x7", "L3-40x72"])
+def test_step_against_float64_where_eps_decides(L, hidden):
+    """The bars of test_step_against_float64 on the generator's gradient sets, from the seeded parameters and from zero: at 1e-11
+    sqrt(v_hat) lies three decades below eps and the step is lr m_hat / eps, 1e-7 per element, which only the zero-start
+    parameters (bar: 2e-3 of the step) and the m, v state resolve."""
+    tw = _twin(L, hidden)
+    for s in SIDES:
+        worst = {}
+        for kind in ("tiny", "mixed"):
+            gsteps = [_generated(tw, s, kind, 500 + k) for k in range(3)]
+            if kind == "tiny":
+                v = _np64([(1 - BETAS[1]) * g.double() ** 2 for g in gsteps[0]])
+                assert optim_restate.eps_share(v, [1] * len(v)) == 1.0
+            for start, state in (("seeded", tw.state(s)), ("zero", _zero_start(tw, s))):
+                for tau in (0.0, 0.005):
+                    what = "L%d %s %s %s gradients from %s tau %g" % (L, hidden, s, kind, start, tau)
+                    w = _one_case(tw, s, what, state, gsteps, tau, hip_capturable=(tau > 0))
+                    worst[(kind, start)] = max(worst.get((kind, start), 0.0), w)
+        print("L%d %s %s: worst error / bar %s" % (L, hidden, s, {"%s/%s" % k: "%.3g" % v for k, v in worst.items()}))
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("inf")], ids=["nan", "inf"])
+@pytest.mark.parametrize("L,hidden", [(3, (1, 7)), (3, (40, 72))], ids=["L3-1x7", "L3-40x72"])
+def test_non_finite_gradients_spread_as_on_the_parent_path(L, hidden, bad):
+    """One NaN (one inf) element in one gradient, ordinary floats in ordinary launches: with the clip a NaN total gives a NaN
+    coefficient (torch.clamp propagates it in clip_grad_norm_) and NaN in g, m, v, p and the target of every tensor; an infinite
+    total gives coef = 0 and a NaN in the element alone.  The NaN pattern of both parent paths and of the restatement; the finite
+    values within the bars of test 1."""
+    tw = _twin(L, hidden)
+    tau = 0.005
+    for s in SIDES:
+        for max_norm in (MAX_NORM, 0.0):
+            state = tw.state(s)
+            gs = [x.clone() for x in tw.gradients(s, 61, 10 * MAX_NORM)]
+            gs[1].view(-1)[-1] = bad
+            runs = {}
+            for kind, cap, hip in (("hip", False, True), ("capturable", True, False), ("plain", False, False)):
+                tw.reset({s: state}, capturable=cap, hip=hip)
+                tw.set_grads(s, gs)
+                tw.step(s, max_norm, tau)
+                runs[kind] = {k: _np64(v) if k != "steps" else v for k, v in tw.read(s).items()}
+            zeros = [np.zeros(x.shape) for x in state["p"]]
+            p, g, m, v, count, t = step_restated(_np64(state["p"]), _np64(gs), zeros, zeros, 0, LR, BETAS[0], BETAS[1], EPS, max_norm, tau, _np64(state["t"]))
+            ref = {"p": p, "g": g, "m": m, "v": v, "t": t}
+            assert runs["hip"]["steps"] == runs["plain"]["steps"] == [1.0] * len(p)
+            n_nan = 0
+            for key in ("p", "g", "m", "v", "t"):
+                for i, (a, r) in enumerate(zip(runs["hip"][key], ref[key])):
+                    nan = np.isnan(a)
+                    n_nan += int(nan.sum())
+                    for other in (runs["capturable"][key][i], runs["plain"][key][i], r):
+                        assert np.array_equal(nan, np.isnan(other)), (s, max_norm, key, i)
+                        assert np.array_equal(np.isinf(a), np.isinf(other)) and np.array_equal(a[np.isinf(a)], other[np.isinf(a)]), (s, max_norm, key, i)
+                    fin = np.isfinite(r)
+                    if not fin.any():
+                        continue
+                    if key in ("g", "m", "v"):                     # max-norm: the parents' ceiling and the floor
+                        e = lambda x: float(np.abs(x[fin] - r[fin]).max())
+                        bar = 10.0 * min(e(runs["capturable"][key][i]), e(runs["plain"][key][i])) + 1e-5 * float(np.abs(r[fin]).max())
+                    else:                                          # 2-norm: the step bar
+                        e = lambda x: float(np.sqrt(((x[fin] - r[fin]) ** 2).sum()))
+                        before = _np64(state[key])[i]
+                        bar = 2e-3 * float(np.sqrt(((r - before)[fin] ** 2).sum())) + np.sqrt(r.size) * float(np.abs(before).max()) * 1.2e-7
+                    assert e(a) <= bar, (s, max_norm, key, i, e(a), bar)
+            total = sum(x.size for key in ("p", "g", "m", "v", "t") for x in ref[key])
+            print("L%d %s %s %s max_norm %g: %d of %d values NaN" % (L, hidden, s, bad, max_norm, n_nan, total))
+            assert n_nan == (total if (np.isnan(bad) and max_norm > 0) else (5 if (np.isnan(bad) or max_norm > 0) else 2))
+    tw.reset({s: tw.state(s) for s in SIDES}, capturable=False, hip=False)     # the shared twin is left finite
+    for s in SIDES:
+        tw.set_grads(s, [torch.zeros_like(p) for p in tw.params(s)])
 
 
 # ---- 2 ---------------------------------------------------------------------------------------------------------------------

@@ -479,7 +479,9 @@ def test_embed3_matches_the_three_embeddings():
 def test_table_optimizer_steps_match_torch(max_norm):
     """td3.clip_and_step (gradient clipping + Adam over a device table of tensor addresses, three launches) against
     torch.nn.utils.clip_grad_norm_ + torch.optim.Adam on ragged tensors, three steps: parameters, both moments, step counters
-    and the clipped gradients left behind; and the soft target update against the reference's formula."""
+    and the clipped gradients left behind; and the soft target update against the reference's formula.  A float32 comparison at
+    one step count and gradients far above Adam's eps; tests/test_table_optim_gpu.py holds the same kernels to float64 where eps
+    decides the step, at a count per tensor, past table row 256 and on non-finite gradients."""
     from sgrl_amd import td3
     g = torch.Generator().manual_seed(int(max_norm * 10) % 97 + 3)
     shapes = [(256, 256), (128,), (30, 128), (1,), (15, 42), (1024, 256), (5000,), (4097,), (3, 3, 3)]
