@@ -318,6 +318,19 @@ SET_HIP_TARGETS_DEFAULT = False
 SWAT_HIP_DROPOUT_DEFAULT = False
 
 
+def _switch(args, name, given):
+    """The value of the Agent switch `name`: the constructor's keyword, else args.<name>, else the constant <NAME>_DEFAULT above as
+    it stands NOW (read from the module on every call)."""
+    if given is None:
+        given = getattr(args, name, None)
+    return globals()[name.upper() + "_DEFAULT"] if given is None else given
+
+
+# agent kind -> (module of this package, class) of its HIP target chain; imported by Agent._hip_targets when a chain is first wanted
+_TARGET_CHAINS = {"set": ("set_hip", "HipSetTargets"), "swat": ("swat_hip", "HipSwatTargets"), "smp": ("smp_hip", "HipSmpTargets"),
+                  "mlp": ("mlp_hip", "HipMlpTargets")}
+
+
 class Agent(nn.Module):
     def __init__(self, args, device=None, use_hip=True, mlp_hip_grads=None, mlp_hip_optim=None, swat_train_kernels=None,
                  smp_train_kernels=None, loss_kernels=None, set_hip_targets=None, swat_hip_dropout=None):
@@ -375,70 +388,30 @@ class Agent(nn.Module):
         self.tot_update_count = 0
         self.target_smoothing_tau = args.agent.target_smoothing_tau
         self.reward_scale = args.agent.reward_scale
-        # SWAT actor AND critic on the GPU: the no-grad target chain of an update runs on the HIP kernels (swat_hip.HipSwatTargets,
-        # created by the first update on a CUDA batch); anything else keeps the PyTorch chain of update_targets
-        self.use_swat_hip = bool(use_hip) and atype == "swat" and ctype == "swat"
-        self._swat_targets = None
-        # swat_train_kernels: the ONLINE swat actor and critic differentiate on the training kernels (swat_policy `train_kernels`;
-        # the targets run the HIP chain above); None: args.swat_train_kernels, then SWAT_TRAIN_KERNELS_DEFAULT.  Follows use_hip;
-        # ignored by every other agent type, as mlp_hip_grads is
-        if swat_train_kernels is None:
-            swat_train_kernels = getattr(args, "swat_train_kernels", None)
-        if swat_train_kernels is None:
-            swat_train_kernels = SWAT_TRAIN_KERNELS_DEFAULT
-        self.set_swat_train_kernels(self.use_swat_hip and bool(swat_train_kernels))
-        # the same for SMP actor AND critic in the published mode (td and bu; smp_hip.HipSmpTargets); the td-only mode stays PyTorch
-        self.use_smp_hip = bool(use_hip) and atype == "smp" and ctype == "smp" and bool(args.td) and bool(args.bu)
-        self._smp_targets = None
-        # smp_train_kernels: the ONLINE smp actor and critic differentiate on the training kernels (smp_policy `train_kernels`); None:
-        # args.smp_train_kernels, then SMP_TRAIN_KERNELS_DEFAULT.  Takes effect only where the HIP target chain does (use_smp_hip);
-        # applied after set_swat_train_kernels above, which leaves every switch of a non-swat agent off
-        if smp_train_kernels is None:
-            smp_train_kernels = getattr(args, "smp_train_kernels", None)
-        if smp_train_kernels is None:
-            smp_train_kernels = SMP_TRAIN_KERNELS_DEFAULT
-        self.set_smp_train_kernels(smp_train_kernels)
-        # and for the monolithic MLP pair: the whole chain is ONE launch (mlp_hip.HipMlpTargets).  The handles do not hold: every
-        # chain packs from the live target parameters, so soft updates and load_state_dict need no notification
-        self.use_mlp_hip = bool(use_hip) and atype == "mlp" and ctype == "mlp"
-        self._mlp_targets = None
-        # set_hip_targets: a SET actor AND critic run the chain as one call over the target modules' own HIP handles
-        # (set_hip.HipSetTargets); None: args.set_hip_targets, then SET_HIP_TARGETS_DEFAULT.  Follows use_hip; ignored by every other
-        # agent type.  Off, or on a CPU / float64 batch: the PyTorch chain of update_targets around the modules' forwards -- and so
-        # wherever the target critics' no-grad forward is the twin pass of the training kernels (set_policy.TWIN_TARGETS, the
-        # default): the chain replaces the two-forward route only, whose results it reproduces bit for bit (_hip_targets)
-        if set_hip_targets is None:
-            set_hip_targets = getattr(args, "set_hip_targets", None)
-        if set_hip_targets is None:
-            set_hip_targets = SET_HIP_TARGETS_DEFAULT
-        self.use_set_hip = bool(use_hip) and atype == "set" and ctype == "set" and bool(set_hip_targets)
-        self._set_targets = None
-        # mlp_hip_grads: the gradient half of an mlp + mlp update (critics' forward, both losses, both backward passes) on the HIP
-        # kernels too (mlp_hip.HipMlpGrads), for float32 batches on the GPU; None: MLP_HIP_GRADS_DEFAULT.  Follows use_hip; ignored by
-        # every other agent type and on the CPU
-        if mlp_hip_grads is None:
-            mlp_hip_grads = getattr(args, "mlp_hip_grads", None)     # so that a trainer's args can ask for it
-        if mlp_hip_grads is None:
-            mlp_hip_grads = MLP_HIP_GRADS_DEFAULT
-        self.use_mlp_hip_grads = self.use_mlp_hip and bool(mlp_hip_grads)
+        # Which HIP paths this agent takes.  Every switch (the *_DEFAULT constants above say what each one does) is the keyword, else
+        # args.<name>, else its constant (_switch), and follows use_hip; agent kinds it is not for ignore it.
+        # The no-grad target chain of an update runs on HIP for a swat + swat, an smp + smp (td and bu; the td-only mode stays PyTorch)
+        # and an mlp + mlp agent, and for a set + set agent that asks for it: ONE chain object (_TARGET_CHAINS), made by the first update
+        # on a float32 CUDA batch (_hip_targets); anything else keeps the PyTorch chain of update_targets
+        hip = bool(use_hip)
+        self.use_swat_hip = hip and atype == "swat" and ctype == "swat"
+        self.use_smp_hip = hip and atype == "smp" and ctype == "smp" and bool(args.td) and bool(args.bu)
+        self.use_mlp_hip = hip and atype == "mlp" and ctype == "mlp"
+        self.use_set_hip = hip and atype == "set" and ctype == "set" and bool(_switch(args, "set_hip_targets", set_hip_targets))
+        self._targets = None
+        # SWAT_ / SMP_TRAIN_KERNELS_DEFAULT: the ONLINE actor and critic differentiate on the training kernels; the smp switch is applied after the swat one, which leaves
+        # every switch of a non-swat agent off
+        self.set_swat_train_kernels(self.use_swat_hip and bool(_switch(args, "swat_train_kernels", swat_train_kernels)))
+        self.set_smp_train_kernels(_switch(args, "smp_train_kernels", smp_train_kernels))
+        # MLP_HIP_GRADS_ / MLP_HIP_OPTIM_DEFAULT: the two halves of an mlp + mlp update after the target chain: float32 batches on the GPU;
+        # the optimizer half only together with the gradient half
+        self.use_mlp_hip_grads = self.use_mlp_hip and bool(_switch(args, "mlp_hip_grads", mlp_hip_grads))
         self._mlp_grads = None
-        # mlp_hip_optim: the optimizer half as well (mlp_hip.HipMlpOptim); None: args.mlp_hip_optim, then MLP_HIP_OPTIM_DEFAULT.  Takes
-        # effect only together with the gradient half; ignored otherwise, as mlp_hip_grads is
-        if mlp_hip_optim is None:
-            mlp_hip_optim = getattr(args, "mlp_hip_optim", None)
-        if mlp_hip_optim is None:
-            mlp_hip_optim = MLP_HIP_OPTIM_DEFAULT
-        self.use_mlp_hip_optim = self.use_mlp_hip_grads and bool(mlp_hip_optim)
+        self.use_mlp_hip_optim = self.use_mlp_hip_grads and bool(_switch(args, "mlp_hip_optim", mlp_hip_optim))
         self._mlp_optim = None
-        # loss_kernels: the critic loss and the actor loss of update_finish, and their gradients, on the loss kernels (train_ops.twin_mse
-        # / neg_mean); None: args.loss_kernels, then LOSS_KERNELS_DEFAULT.  Follows use_hip; an mlp agent ignores it (its gradient half
-        # has losses of its own).  An Agent switch, not one of GraphedUpdates: an eager and a graphed agent with the same switches run
-        # the same arithmetic
-        if loss_kernels is None:
-            loss_kernels = getattr(args, "loss_kernels", None)
-        if loss_kernels is None:
-            loss_kernels = LOSS_KERNELS_DEFAULT
-        self.use_loss_kernels = bool(use_hip) and atype != "mlp" and bool(loss_kernels)
+        # LOSS_KERNELS_DEFAULT: an mlp agent ignores it (its gradient half has losses of its own).  An Agent switch, not one of GraphedUpdates: an eager and a
+        # graphed agent with the same switches run the same arithmetic
+        self.use_loss_kernels = hip and atype != "mlp" and bool(_switch(args, "loss_kernels", loss_kernels))
         # dropout_rate: read by the swat networks only (the reference forces the SET networks to 0, SEActor.py:185; smp and mlp have
         # none).  With a rate > 0 every update() runs inside a train_ops.dropout_rng context: seed = args.seed (0 when absent), step =
         # a one-element int64 tensor on the batch's device, created by the first update and incremented once at the top of each one,
@@ -446,15 +419,8 @@ class Agent(nn.Module):
         self.dropout_rate = float(getattr(args, "dropout_rate", 0.0) or 0.0) if "swat" in (atype, ctype) else 0.0
         self.dropout_seed = int(getattr(args, "seed", 0) or 0)
         self._dropout_step = None
-        # swat_hip_dropout: with dropout_rate > 0 and the target networks in training mode, the target chain runs the HIP chain's
-        # dropout entries and takes the 39 site numbers the three modules would have taken (update_targets); None:
-        # args.swat_hip_dropout, then SWAT_HIP_DROPOUT_DEFAULT.  Follows use_hip; ignored by every other agent type.  Off: such a
-        # chain runs the modules (_hip_targets returns None)
-        if swat_hip_dropout is None:
-            swat_hip_dropout = getattr(args, "swat_hip_dropout", None)
-        if swat_hip_dropout is None:
-            swat_hip_dropout = SWAT_HIP_DROPOUT_DEFAULT
-        self.swat_hip_dropout = self.use_swat_hip and bool(swat_hip_dropout)
+        # SWAT_HIP_DROPOUT_DEFAULT; off: a chain with the targets in training mode runs the modules (_target_kind returns None)
+        self.swat_hip_dropout = self.use_swat_hip and bool(_switch(args, "swat_hip_dropout", swat_hip_dropout))
 
     def set_swat_train_kernels(self, on):
         """Turn the training kernels of the online swat networks on or off (no other agent type has the switch)."""
@@ -475,12 +441,7 @@ class Agent(nn.Module):
 
     def __getstate__(self):
         d = self.__dict__.copy()
-        d["_swat_targets"] = None     # per-process device handles: never pickled / deep-copied with the agent
-        d["_smp_targets"] = None
-        d["_mlp_targets"] = None
-        d["_set_targets"] = None
-        d["_mlp_grads"] = None
-        d["_mlp_optim"] = None
+        d["_targets"] = d["_mlp_grads"] = d["_mlp_optim"] = None     # per-process device handles: never pickled / deep-copied with the agent
         return d
 
     def _hip_grads(self, data_batch):
@@ -523,9 +484,8 @@ class Agent(nn.Module):
             o = self._mlp_optim = HipMlpOptim(grads, self.actor_optimizer, self.critic_optimizer, self.actor_target, self.critic_target)
         return o
 
-    def _hip_targets(self, next_obs):
-        """swat_hip.HipSwatTargets / smp_hip.HipSmpTargets / mlp_hip.HipMlpTargets / set_hip.HipSetTargets when this update's target
-        chain runs on HIP, else None."""
+    def _target_kind(self, next_obs):
+        """Which HIP target chain serves this update's batch -- a key of _TARGET_CHAINS -- or None: the modules run."""
         if not ((self.use_swat_hip or self.use_smp_hip or self.use_mlp_hip or self.use_set_hip) and next_obs.is_cuda and
                 next_obs.dtype == torch.float32 and self.device.type == "cuda"):
             return None
@@ -538,35 +498,34 @@ class Agent(nn.Module):
                 # runs where SECritic.forward itself takes two passes of the rollout kernels (set_policy.TWIN_TARGETS = False,
                 # TWIN_CRITICS = False, SGRL_TRAIN_GEMM=0).
                 return None
-            t = self._set_targets
-            if t is None or t.actor.policy is not self.actor_target or t.critic.module is not self.critic_target:
-                from .set_hip import HipSetTargets      # raises SgrlError when the extension is missing (no fallback)
-                t = self._set_targets = HipSetTargets(self.actor_target, self.critic_target)
-            return t
+            return "set"
         if self.use_swat_hip and self.dropout_rate > 0 and (self.actor_target.training or self.critic_target.training):
             # the plain HIP chain has no dropout: targets in training mode run the modules, as the reference's do -- unless the switch
             # hands them to the chain's dropout entries, which serve the three networks in ONE mode (_targets_drop)
             if not (self.swat_hip_dropout and self.actor_target.training and self.critic_target.training):
                 return None
         if self.use_smp_hip:
-            t = self._smp_targets
-            if t is None or t.actor.policy is not self.actor_target or t.critic.module is not self.critic_target:
-                from .smp_hip import HipSmpTargets      # raises SgrlError when the extension is missing (no fallback)
-                t = self._smp_targets = HipSmpTargets(self.actor_target, self.critic_target)
-            return t
+            return "smp"
         if self.use_mlp_hip:
             if float(self.actor_target.max_action) != float(self.args.max_action):
                 raise ValueError("the HIP target chain of an mlp agent scales and clamps with one max_action: the target policy's (%r) differs "
                                  "from args.max_action (%r); build the agent with use_hip=False" % (self.actor_target.max_action, self.args.max_action))
-            t = self._mlp_targets
-            if t is None or t.actor.policy is not self.actor_target or t.critic.module is not self.critic_target:
-                from .mlp_hip import HipMlpTargets      # raises SgrlError when the extension is missing (no fallback)
-                t = self._mlp_targets = HipMlpTargets(self.actor_target, self.critic_target)
-            return t
-        t = self._swat_targets
-        if t is None or t.actor.policy is not self.actor_target or t.critic.module is not self.critic_target:
-            from .swat_hip import HipSwatTargets    # raises SgrlError when the extension is missing (no fallback)
-            t = self._swat_targets = HipSwatTargets(self.actor_target, self.critic_target)
+            return "mlp"
+        return "swat"
+
+    def _hip_targets(self, next_obs):
+        """The chain object of `_target_kind(next_obs)` (swat_hip.HipSwatTargets / smp_hip.HipSmpTargets / mlp_hip.HipMlpTargets /
+        set_hip.HipSetTargets) when this update's target chain runs on HIP, else None.  The object is kept in `_targets` and made
+        again when it is of another kind or a target module has been replaced."""
+        kind = self._target_kind(next_obs)
+        if kind is None:
+            return None
+        module, cls = _TARGET_CHAINS[kind]
+        t = self._targets
+        if t is None or type(t).__name__ != cls or t.actor.policy is not self.actor_target or t.critic.module is not self.critic_target:
+            import importlib
+            # raises SgrlError when the extension is missing (no fallback)
+            t = self._targets = getattr(importlib.import_module("." + module, __package__), cls)(self.actor_target, self.critic_target)
         return t
 
     def _targets_drop(self):
@@ -649,7 +608,7 @@ class Agent(nn.Module):
         with torch.no_grad():
             if noise is None:
                 noise = torch.zeros_like(action_batch).normal_(0, args.policy_noise)
-            hip = self._hip_targets(next_obs_batch)
+            hip, drop = self._hip_targets(next_obs_batch), {}
             if hip is not None and self._targets_drop():
                 # the three target networks in training mode on the chain's dropout entries: the masks of this update's context,
                 # and the 39 site numbers the modules would take here (actor_target, critic1, critic2: 13 each, in that order), so
@@ -660,13 +619,10 @@ class Agent(nn.Module):
                     hip = None
                 else:
                     from .swat_hip import SITES_PER_NET
-                    target_Q = hip.target_q(next_obs_batch.contiguous(), noise.contiguous(), reward_batch, done_batch,
-                                            self.actor_target.graph, args.noise_clip, args.discount,
-                                            dropout=(self.dropout_rate, rng.seed, rng.step, rng.reserve(3 * SITES_PER_NET)))
-                    return reward_batch, target_Q
+                    drop = {"dropout": (self.dropout_rate, rng.seed, rng.step, rng.reserve(3 * SITES_PER_NET))}
             if hip is not None:      # one library call: target actor, noise clip and clamp, twin target critics, min, Bellman target
                 target_Q = hip.target_q(next_obs_batch.contiguous(), noise.contiguous(), reward_batch, done_batch,
-                                        self.actor_target.graph, args.noise_clip, args.discount)
+                                        self.actor_target.graph, args.noise_clip, args.discount, **drop)
                 return reward_batch, target_Q
             noise = noise.clamp(-args.noise_clip, args.noise_clip)
             next_action = (self.actor_target(next_obs_batch) + noise).clamp(-args.max_action, args.max_action)
@@ -815,7 +771,75 @@ def handles_stamp(handles):
     return tuple((int(h.generation()), None if h._bound is None else tuple(h._bound)) for h in handles)
 
 
-class GraphedUpdates(object):
+class _GraphedSurface(object):
+    """What GraphedUpdates and GraphedMlpUpdates promise the trainer -- `warm`, `warm_from`, `update`, `update_from` over `agent`, `B`,
+    `slots` and `warmed` -- and the host work both do around a replay.  A subclass supplies the slot (`_slot(key, graph, L)` and
+    `_widths(L)`, the row widths of its obs and action tensors, which creates nothing), `_warm(key, graph, L, load, iters, first_it)`
+    and `_replay(sl, key, graph, it)`: everything of an update after the slot's static tensors have been filled."""
+
+    def _load(self, sl, data_batch):
+        for k, t in sl["batch"].items():
+            t.copy_(data_batch[k].reshape(t.shape))
+        sl["noise"].normal_(0, self.agent.args.policy_noise)
+
+    def _load_from(self, sl, buffer, seed, draw):
+        buffer.sample_into(sl["batch"], self.B, seed, draw, noise=sl["noise"], noise_std=self.agent.args.policy_noise)
+
+    def _morphology(self, graph):
+        if graph is not None:
+            self.agent.change_morphology(graph)
+
+    def warm(self, key, graph, L, data_batch, iters=3, first_it=0):
+        """Eager updates on the slot.  They are REAL updates: the caller passes the first `iters` iterations of its schedule
+        (`data_batch` may be a callable returning a fresh batch per iteration, `first_it` the index of the first one) instead of
+        adding updates of its own.  Returns the loss dicts."""
+        return self._warm(key, graph, L, lambda sl, n: self._load(sl, data_batch() if callable(data_batch) else data_batch), iters, first_it)
+
+    def warm_from(self, key, graph, L, buffer, seed, draw, iters=3, first_it=0):
+        """`warm` with the slot filled by `buffer.sample_into` (replay.DeviceReplayBuffer): iteration n of the `iters` uses draw
+        number `draw + n`.  The buffer must hold at least a full batch."""
+        if buffer.max_sample_size < self.B:
+            raise RuntimeError("warm_from needs at least %d rows in the buffer" % self.B)
+        return self._warm(key, graph, L, lambda sl, n: self._load_from(sl, buffer, seed, draw + n), iters, first_it)
+
+    def update(self, key, graph, L, data_batch, it):
+        """Same contract as Agent.update(data_batch, it) (a replay: with lazy_stats=True) for the morphology `graph` (dict)
+        identified by `key`."""
+        if data_batch["obs"].shape[0] != self.B:
+            self._morphology(graph)                     # short batch (buffer not yet filled): eager
+            return self.agent.update(data_batch, it)
+        sl = self._slot(key, graph, L)
+        self._load(sl, data_batch)
+        return self._replay(sl, key, graph, it)
+
+    def update_from(self, key, graph, L, buffer, it, seed, draw):
+        """`update` with the batch drawn by the library: the slot's static batch and noise tensors are filled by ONE
+        `buffer.sample_into(..., seed, draw, noise=...)` (replay.DeviceReplayBuffer, include/sgrl_replay.h) -- launched outside the
+        captured graph, before the replay (seed and draw are by-value arguments: not part of the graph) -- instead of sample() + five
+        copies + normal_().  What the graphs record is unchanged."""
+        if buffer.max_sample_size < self.B:             # short batch (buffer not yet filled): eager, on the k rows there are
+            self._morphology(graph)
+            k, dev, (n_obs, n_act) = buffer.max_sample_size, self.agent.device, self._widths(L)
+            e = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
+            batch = {"obs": e(k, n_obs), "action": e(k, n_act), "next_obs": e(k, n_obs), "reward": e(k, 1), "done": e(k, 1)}
+            noise = torch.zeros((k, n_act), dtype=torch.float32, device=dev)
+            buffer.sample_into(batch, k, seed, draw, noise=noise, noise_std=self.agent.args.policy_noise)
+            return self.agent.update(batch, it, noise=noise)
+        sl = self._slot(key, graph, L)
+        self._load_from(sl, buffer, seed, draw)
+        return self._replay(sl, key, graph, it)
+
+    def _announce(self, flag):
+        """A replay runs no host code: the writes of its optimizer / soft-update kernels are announced here."""
+        a = self.agent
+        touched = list(a.critic.parameters())
+        if flag == 0:
+            for mod in (a.actor, a.actor_target, a.critic_target):
+                touched.extend(mod.parameters())
+        _touched(touched)
+
+
+class GraphedUpdates(_GraphedSurface):
     """`Agent.update` captured into hipGraphs (MI355X: the update is ~3 400 small launches -- PyTorch autograd through three
     SET networks at batch 100 plus the HIP target kernels -- and launch-bound when issued eagerly: 50 ms; a replay is
     GPU-bound: 32 ms).  One graph per (morphology, with / without the delayed actor step); the batch is copied into static
@@ -894,12 +918,15 @@ class GraphedUpdates(object):
     def _slot(self, key, graph, L):
         sl = self.slots.get(key)
         if sl is None:
-            dev, B = self.agent.device, self.B
+            dev, B, (n_obs, n_act) = self.agent.device, self.B, self._widths(L)
             z = lambda *sh: torch.zeros(sh, dtype=torch.float32, device=dev)
-            sl = {"graph": graph, "batch": {"obs": z(B, 41 * L), "action": z(B, 3 * L), "next_obs": z(B, 41 * L), "reward": z(B, 1),
-                                            "done": z(B, 1)}, "noise": z(B, 3 * L), "graphs": {}, "out": {}, "stamp": {}}
+            sl = {"graph": graph, "batch": {"obs": z(B, n_obs), "action": z(B, n_act), "next_obs": z(B, n_obs), "reward": z(B, 1),
+                                            "done": z(B, 1)}, "noise": z(B, n_act), "graphs": {}, "out": {}, "stamp": {}}
             self.slots[key] = sl
         return sl
+
+    def _widths(self, L):
+        return 41 * L, 3 * L
 
     def _hip_handles(self):
         """The HIP handles whose forwards the update graphs record: the target actor and the two target critics."""
@@ -962,28 +989,8 @@ class GraphedUpdates(object):
             raise RuntimeError("the agent's dropout step tensor is not the one morphology %r was warmed with: warm(%r, ...) again before "
                                "the next graphed update" % (key, key))
 
-    def _load(self, sl, data_batch):
-        for k, t in sl["batch"].items():
-            t.copy_(data_batch[k].reshape(t.shape))
-        sl["noise"].normal_(0, self.agent.args.policy_noise)
-
-    def warm(self, key, graph, L, data_batch, iters=3, first_it=0):
-        """Eager updates on a side stream (PyTorch's capture protocol).  They are REAL updates: the caller passes the first
-        `iters` iterations of its schedule (`data_batch` may be a callable returning a fresh batch per iteration, `first_it`
-        the index of the first one) instead of adding updates of its own.  Returns the loss dicts."""
-        return self._warm(key, graph, L, lambda sl, n: self._load(sl, data_batch() if callable(data_batch) else data_batch), iters, first_it)
-
-    def warm_from(self, key, graph, L, buffer, seed, draw, iters=3, first_it=0):
-        """`warm` with the slot filled by `buffer.sample_into` (replay.DeviceReplayBuffer): iteration n of the `iters` uses draw
-        number `draw + n`.  The buffer must hold at least a full batch."""
-        if buffer.max_sample_size < self.B:
-            raise RuntimeError("warm_from needs at least %d rows in the buffer" % self.B)
-        return self._warm(key, graph, L, lambda sl, n: self._load_from(sl, buffer, seed, draw + n), iters, first_it)
-
-    def _load_from(self, sl, buffer, seed, draw):
-        buffer.sample_into(sl["batch"], self.B, seed, draw, noise=sl["noise"], noise_std=self.agent.args.policy_noise)
-
     def _warm(self, key, graph, L, load, iters, first_it):
+        """The eager updates of `warm` / `warm_from`, on a side stream (PyTorch's capture protocol)."""
         sl = self._slot(key, graph, L)
         self.agent.change_morphology(graph)
         s = torch.cuda.Stream()
@@ -1000,37 +1007,10 @@ class GraphedUpdates(object):
             sl["dropout_step"] = self.agent._dropout_step      # (dropout) created by the first eager update
         return outs
 
-    def update(self, key, graph, L, data_batch, it):
-        """Same contract as Agent.update(data_batch, it) for the morphology `graph` (dict) identified by `key`."""
-        if data_batch["obs"].shape[0] != self.B:
-            self.agent.change_morphology(graph)         # short batch (buffer not yet filled): eager
-            return self.agent.update(data_batch, it)
-        sl = self._slot(key, graph, L)
-        if key not in self.warmed:
-            raise RuntimeError("warm(%r, ...) every morphology before the first graphed update" % (key,))
-        self._load(sl, data_batch)
-        return self._replay(sl, key, graph, it)
-
-    def update_from(self, key, graph, L, buffer, it, seed, draw):
-        """`update` with the batch drawn by the library: the slot's static batch and noise tensors are filled by ONE
-        `buffer.sample_into(..., seed, draw, noise=...)` (replay.DeviceReplayBuffer, include/sgrl_replay.h) -- launched outside the
-        captured graph, before the replay -- instead of sample() + five copies + normal_().  What the graphs record is unchanged."""
-        if buffer.max_sample_size < self.B:             # short batch (buffer not yet filled): eager, on the k rows there are
-            self.agent.change_morphology(graph)
-            k, dev = buffer.max_sample_size, self.agent.device
-            e = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
-            batch = {"obs": e(k, 41 * L), "action": e(k, 3 * L), "next_obs": e(k, 41 * L), "reward": e(k, 1), "done": e(k, 1)}
-            noise = torch.zeros((k, 3 * L), dtype=torch.float32, device=dev)
-            buffer.sample_into(batch, k, seed, draw, noise=noise, noise_std=self.agent.args.policy_noise)
-            return self.agent.update(batch, it, noise=noise)
-        sl = self._slot(key, graph, L)
-        if key not in self.warmed:
-            raise RuntimeError("warm(%r, ...) every morphology before the first graphed update" % (key,))
-        self._load_from(sl, buffer, seed, draw)
-        return self._replay(sl, key, graph, it)
-
     def _replay(self, sl, key, graph, it):
         """Everything of a graphed update after the slot's static tensors have been filled."""
+        if key not in self.warmed:
+            raise RuntimeError("warm(%r, ...) every morphology before the first graphed update" % (key,))
         flag = 0 if it % self.agent.args.policy_freq == 0 else 1
         # A graph bakes the addresses of the SET handles' workspaces.  They only ever grow, and every morphology is run eagerly
         # before any capture -- but a graph captured before a LATER regrowth would fault on replay (a GPU memory fault, not an
@@ -1095,12 +1075,7 @@ class GraphedUpdates(object):
             g[2].replay()
         else:
             g.replay()
-        # a replay runs no host code: the writes of its optimizer / soft-update kernels are announced here
-        touched = list(self.agent.critic.parameters())
-        if flag == 0:
-            for mod in (self.agent.actor, self.agent.actor_target, self.agent.critic_target):
-                touched.extend(mod.parameters())
-        _touched(touched)
+        self._announce(flag)
         # the capture's output tensors are overwritten by the next replay: hand out copies
         return {k: (v.clone() if torch.is_tensor(v) else v) for k, v in sl["out"][flag].items()}
 
@@ -1143,7 +1118,7 @@ class _EveryKey(object):
         return self._owner._warmed
 
 
-class GraphedMlpUpdates(object):
+class GraphedMlpUpdates(_GraphedSurface):
     """The TD3 update of an mlp + mlp agent replayed from hipGraphs: the trainer-facing surface of `GraphedUpdates` (`warm`,
     `warm_from`, `update`, `update_from`, `warmed`, `slots`; fewer rows than B: an eager `agent.update`) over an update that is
     entirely this library's launches -- mlp_hip.batch_stats -> HipMlpTargets.target_q -> HipMlpGrads.critic_step ->
@@ -1197,25 +1172,19 @@ class GraphedMlpUpdates(object):
         self.replays = 0             # updates served by a graph replay so far
 
     # ---- the slot -------------------------------------------------------------------------------------
-    def _slot(self):
+    def _slot(self, key=None, graph=None, L=None):
         sl = self.slots.get(None)
         if sl is None:
-            a = self.agent
-            dev, B = a.device, self.B
-            n_in, n_out = self._mlp_hip.net_dims(a.actor.actor)[0], self._mlp_hip.net_dims(a.actor.actor)[-1]
+            dev, B, (n_in, n_out) = self.agent.device, self.B, self._widths(L)
             z = lambda *sh: torch.zeros(sh, dtype=torch.float32, device=dev)
             sl = {"batch": {"obs": z(B, n_in), "action": z(B, n_out), "next_obs": z(B, n_in), "reward": z(B, 1), "done": z(B, 1)},
                   "noise": z(B, n_out), "reward": z(B, 1), "target": z(B, 1), "rec": z(4), "graphs": {}, "stamp": {}}
             self.slots[None] = sl
         return sl
 
-    def _load(self, sl, data_batch):
-        for k, t in sl["batch"].items():
-            t.copy_(data_batch[k].reshape(t.shape))
-        sl["noise"].normal_(0, self.agent.args.policy_noise)
-
-    def _load_from(self, sl, buffer, seed, draw):
-        buffer.sample_into(sl["batch"], self.B, seed, draw, noise=sl["noise"], noise_std=self.agent.args.policy_noise)
+    def _widths(self, L):
+        dims = self._mlp_hip.net_dims(self.agent.actor.actor)
+        return dims[0], dims[-1]
 
     def _handles(self, sl):
         """(HipMlpTargets, HipMlpGrads, HipMlpOptim) of the agent -- its own, so that an eager `agent.update` and this object see the
@@ -1287,11 +1256,10 @@ class GraphedMlpUpdates(object):
         self._warmed = True
         return self._result(sl, flag == 0)
 
-    def _update(self, sl, graph, it):
+    def _replay(self, sl, key, graph, it):
         """Everything of an update after the slot's static tensors have been filled."""
         a = self.agent
-        if graph is not None:
-            a.change_morphology(graph)
+        self._morphology(graph)
         flag = 0 if it % a.args.policy_freq == 0 else 1
         hs = self._handles(sl)
         optim = hs[2]
@@ -1318,58 +1286,16 @@ class GraphedMlpUpdates(object):
         self.replays += 1
         # a replay runs no host code: the steps' host-side counts and the writes of their kernels are announced here
         optim.replayed(critic=True, actor=flag == 0)
-        touched = list(a.critic.parameters())
-        if flag == 0:
-            for mod in (a.actor, a.actor_target, a.critic_target):
-                touched.extend(mod.parameters())
-        _touched(touched)
+        self._announce(flag)
         return self._result(sl, flag == 0)
 
-    # ---- the surface of GraphedUpdates ----------------------------------------------------------------------
-    def warm(self, key, graph, L, data_batch, iters=3, first_it=0):
-        """`iters` REAL updates run eagerly on the slot (optional here: the first update of each kind is eager anyway).  data_batch
-        may be a callable returning a fresh batch per iteration.  Returns the loss dicts."""
-        return self._warm(graph, lambda sl, n: self._load(sl, data_batch() if callable(data_batch) else data_batch), iters, first_it)
-
-    def warm_from(self, key, graph, L, buffer, seed, draw, iters=3, first_it=0):
-        """`warm` with the slot filled by `buffer.sample_into`: iteration n uses draw number `draw + n`."""
-        if buffer.max_sample_size < self.B:
-            raise RuntimeError("warm_from needs at least %d rows in the buffer" % self.B)
-        return self._warm(graph, lambda sl, n: self._load_from(sl, buffer, seed, draw + n), iters, first_it)
-
-    def _warm(self, graph, load, iters, first_it):
+    def _warm(self, key, graph, L, load, iters, first_it):
+        """The `iters` updates of `warm` / `warm_from`, run eagerly on the slot (optional here: the first update of each kind is eager
+        anyway)."""
         sl = self._slot()
-        if graph is not None:
-            self.agent.change_morphology(graph)
+        self._morphology(graph)
         outs = []
         for n, it in enumerate(range(first_it, first_it + iters)):
             load(sl, n)
             outs.append(self._eager(sl, self._handles(sl), 0 if it % self.agent.args.policy_freq == 0 else 1))
         return outs
-
-    def update(self, key, graph, L, data_batch, it):
-        """Same contract as Agent.update(data_batch, it, lazy_stats=True)."""
-        if data_batch["obs"].shape[0] != self.B:
-            if graph is not None:
-                self.agent.change_morphology(graph)     # short batch (buffer not yet filled): eager
-            return self.agent.update(data_batch, it)
-        sl = self._slot()
-        self._load(sl, data_batch)
-        return self._update(sl, graph, it)
-
-    def update_from(self, key, graph, L, buffer, it, seed, draw):
-        """`update` with the batch and the noise drawn by ONE `buffer.sample_into(..., seed, draw, noise=...)` into the slot's static
-        tensors, launched before the replay (seed and draw are by-value arguments: not part of the graph)."""
-        if buffer.max_sample_size < self.B:             # short batch (buffer not yet filled): eager, on the k rows there are
-            if graph is not None:
-                self.agent.change_morphology(graph)
-            k, dev = buffer.max_sample_size, self.agent.device
-            sl = self._slot()
-            e = lambda t: torch.empty((k, t.shape[1]), dtype=torch.float32, device=dev)
-            batch = {name: e(t) for name, t in sl["batch"].items()}
-            noise = torch.zeros((k, sl["noise"].shape[1]), dtype=torch.float32, device=dev)
-            buffer.sample_into(batch, k, seed, draw, noise=noise, noise_std=self.agent.args.policy_noise)
-            return self.agent.update(batch, it, noise=noise)
-        sl = self._slot()
-        self._load_from(sl, buffer, seed, draw)
-        return self._update(sl, graph, it)

@@ -331,7 +331,7 @@ def test_device_trainer_replays_swat_updates_on_the_kernels():
         assert all(np.isfinite(float(v)) for v in loss.values()), loss
     assert max(float((p.detach() - q).abs().max()) for p, q in zip(agent.actor.parameters(), before)) > 0
     assert tr.graphed.captures and all(v == 1 for v in tr.graphed.captures.values())
-    assert agent.use_swat_hip and agent.use_swat_train_kernels and agent._swat_targets is not None
+    assert agent.use_swat_hip and agent.use_swat_train_kernels and agent._targets is not None
     # the rollout's HIP forward reads the live weights: it equals the module's forward on the same observations
     a1 = tr.ro.policy_forward(obs).clone()
     env, row = tr.ro.env, 0

@@ -58,7 +58,7 @@ def test_cpu_mlp_agent_never_builds_a_handle_and_deep_copies():
     from sgrl_amd.mlp_policy import MlpCritic
     from sgrl_amd.td3 import Agent, default_train_args
     agent = Agent(default_train_args(actor_type="mlp", critic_type="mlp", mlp_num_limbs=3), device="cpu")
-    assert agent.use_mlp_hip and agent._mlp_targets is None
+    assert agent.use_mlp_hip and agent._targets is None
     assert not Agent(default_train_args(actor_type="mlp", critic_type="mlp", mlp_num_limbs=3), device="cpu", use_hip=False).use_mlp_hip
     assert not Agent(default_train_args(), device="cpu", use_hip=False).use_mlp_hip
     g = torch.Generator().manual_seed(0)
@@ -69,18 +69,18 @@ def test_cpu_mlp_agent_never_builds_a_handle_and_deep_copies():
     reward, tq = agent.update_targets(batch, torch.randn((B, 9), generator=g) * 0.4)
     assert tq.shape == (B, 1) and bool(torch.isfinite(tq).all())
     assert torch.equal(tq[batch["done"] == 1], reward[batch["done"] == 1])
-    assert agent._mlp_targets is None and agent.actor_target._mlp_hip is None and agent.critic_target._mlp_hip is None
+    assert agent._targets is None and agent.actor_target._mlp_hip is None and agent.critic_target._mlp_hip is None
     assert isinstance(agent.critic_target, MlpCritic) and hasattr(agent.critic_target, "hip_handle")
     twin = copy.deepcopy(agent)
-    assert twin._mlp_targets is None and twin.critic_target._mlp_hip is None and twin.use_mlp_hip
+    assert twin._targets is None and twin.critic_target._mlp_hip is None and twin.use_mlp_hip
     _, tq2 = twin.update_targets(batch, torch.zeros((B, 9)))
     _, tq1 = agent.update_targets(batch, torch.zeros((B, 9)))
     assert torch.equal(tq1, tq2)
     # a stand-in for a live handle does not travel with a copy either
-    agent._mlp_targets = agent.critic_target._mlp_hip = object()
+    agent._targets = agent.critic_target._mlp_hip = object()
     twin = copy.deepcopy(agent)
-    assert twin._mlp_targets is None and twin.critic_target._mlp_hip is None
-    agent._mlp_targets = agent.critic_target._mlp_hip = None
+    assert twin._targets is None and twin.critic_target._mlp_hip is None
+    agent._targets = agent.critic_target._mlp_hip = None
 
 
 def test_exports_every_symbol_the_header_declares():

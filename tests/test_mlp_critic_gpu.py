@@ -431,18 +431,18 @@ def test_agent_update_targets_through_the_chain_and_on_float64(B):
             assert all(np.isfinite(float(v)) for v in out.values()), (tag, out)
             losses[tag] = float(out["loss/critic_loss"])
         print("B %d update %d critic loss: float64 %.9g  pytorch f32 %.9g  hip targets %.9g" % (B, it, losses["float64"], losses["pytorch"], losses["hip"]))
-    assert isinstance(hip_agent._mlp_targets, HipMlpTargets) and hip_agent.actor_target._mlp_hip is not None
+    assert isinstance(hip_agent._targets, HipMlpTargets) and hip_agent.actor_target._mlp_hip is not None
     assert hip_agent.critic_target._mlp_hip is not None and hip_agent.critic._mlp_hip is None
-    assert pt_agent._mlp_targets is None and pt_agent.actor_target._mlp_hip is None and pt_agent.critic_target._mlp_hip is None
-    assert f64_agent._mlp_targets is None and f64_agent.critic_target._mlp_hip is None
+    assert pt_agent._targets is None and pt_agent.actor_target._mlp_hip is None and pt_agent.critic_target._mlp_hip is None
+    assert f64_agent._targets is None and f64_agent.critic_target._mlp_hip is None
     # replaced target modules: the agent builds new handles
-    old = hip_agent._mlp_targets
+    old = hip_agent._targets
     hip_agent.critic_target = copy.deepcopy(hip_agent.critic_target)
     batch, noise = _batch(7, B, seed=70)
     _, tq = hip_agent.update_targets(batch, noise)
     ref = _chain64(hip_agent.actor_target, hip_agent.critic_target, batch["next_obs"], noise, batch["reward"], batch["done"],
                    discount=hip_agent.args.discount)[1]
-    assert hip_agent._mlp_targets is not old and hip_agent._mlp_targets.critic.module is hip_agent.critic_target
+    assert hip_agent._targets is not old and hip_agent._targets.critic.module is hip_agent.critic_target
     assert float(np.abs(_np64(tq) - ref).max()) < BAR * max(1.0, float(np.abs(ref).max()))
 
 
@@ -472,7 +472,7 @@ def test_hip_agent_replays_the_reference_update(golden_dir):
         ref_cl, got = float(z[tag + "critic_loss"]), float(loss["loss/critic_loss"])
         print("reference update %d: critic_loss %.9g  reference %.9g  relative difference %.3g" % (it, got, ref_cl, abs(got - ref_cl) / abs(ref_cl)))
         assert abs(got - ref_cl) < 1e-4 * abs(ref_cl), it
-        assert agent._mlp_targets is not None
+        assert agent._targets is not None
 
 
 def test_device_trainer_trains_through_the_chain():
@@ -481,12 +481,12 @@ def test_device_trainer_trains_through_the_chain():
     from sgrl_amd.train_loop import DeviceTrainer
     args = default_train_args(actor_type="mlp", critic_type="mlp")
     tr = DeviceTrainer(["3d_hopper_3_shin"], 4, args=args, seed=2, device="cuda:0", max_buffer_size=4096, batch_size=64)
-    assert tr.agent.use_mlp_hip and tr.agent._mlp_targets is None
+    assert tr.agent.use_mlp_hip and tr.agent._targets is None
     tr.warmup(8)
     s = tr.train_round(max_steps=40, max_iters=2)
     assert s["per_morph_iter"] == 2
-    assert isinstance(tr.agent._mlp_targets, HipMlpTargets) and tr.agent._mlp_targets.actor.n_env > 0
-    assert tr.agent._mlp_targets.critic.module is tr.agent.critic_target
+    assert isinstance(tr.agent._targets, HipMlpTargets) and tr.agent._targets.actor.n_env > 0
+    assert tr.agent._targets.critic.module is tr.agent.critic_target
     losses = tr.last_losses["3d_hopper_3_shin"]
     assert all(np.isfinite(float(v)) for v in losses.values())
 

@@ -446,7 +446,7 @@ def test_agent_keeps_the_pytorch_gradient_half_for_unserved_widths():
     out = agent.update(batch, 0)
     assert all(np.isfinite(float(v)) for v in out.values()) and "loss/actor_loss" in out
     assert not agent.use_mlp_hip_grads and agent._mlp_grads is None and "widths up to 512" in agent.mlp_hip_grads_refusal
-    assert agent._mlp_targets is not None                 # the target chain serves these widths
+    assert agent._targets is not None                     # the target chain serves these widths
 
 
 # ---- 6 ---------------------------------------------------------------------------------------------------------------------

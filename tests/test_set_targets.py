@@ -134,7 +134,7 @@ def test_cpu_agent_with_the_switch_is_the_agent_without_it():
         assert agent.use_set_hip == bool(flag)
         agent.change_morphology(gd)
         got.append(agent.update_targets(batch, noise))
-        assert agent._set_targets is None and agent.actor_target._hip is None and agent.critic_target._hip is None
+        assert agent._targets is None and agent.actor_target._hip is None and agent.critic_target._hip is None
         agents.append(agent)
     for r, t in got[1:]:
         assert torch.equal(r, got[0][0]) and torch.equal(t, got[0][1])
@@ -146,17 +146,17 @@ def test_cpu_agent_with_the_switch_is_the_agent_without_it():
     assert not Agent(default_train_args(set_hip_targets=True), set_hip_targets=False).use_set_hip
     assert not Agent(default_train_args(), use_hip=False, set_hip_targets=True).use_set_hip
     # the target object never travels with the agent
-    on._set_targets = _StubHandle()
+    on._targets = _StubHandle()
     on.actor.clear_buffer()
     on.actor_target.clear_buffer()
     for twin in (copy.deepcopy(on), pickle.loads(pickle.dumps(on))):
-        assert twin._set_targets is None and twin.use_set_hip
-    assert isinstance(on._set_targets, _StubHandle)
+        assert twin._targets is None and twin.use_set_hip
+    assert isinstance(on._targets, _StubHandle)
 
 
 def test_other_agent_types_ignore_the_switch():
     from sgrl_amd.td3 import Agent, default_train_args
     agent = Agent(default_train_args(actor_type="swat", critic_type="swat"), set_hip_targets=True)
-    assert not agent.use_set_hip and agent._set_targets is None
+    assert not agent.use_set_hip and agent._targets is None
     mixed = Agent(default_train_args(actor_type="swat", critic_type="set"), set_hip_targets=True)
     assert not mixed.use_set_hip

@@ -395,11 +395,11 @@ def test_agent_updates_are_those_of_the_switch_off_agent(ctx, target_route):
         print("SETTARGETS agent %s it %d | max |target on - off| %.3e" % (target_route, it, float((tq_on - tq_off).abs().max())))
         on.update(batch, it, noise=noise)
         off.update(batch, it, noise=noise)
-    assert off._set_targets is None
+    assert off._targets is None
     if target_route == "two_forwards":
-        assert isinstance(on._set_targets, HipSetTargets)           # the chain ran
+        assert isinstance(on._targets, HipSetTargets)               # the chain ran
     else:
-        assert on._set_targets is None                               # the chain yielded to the twin pass
+        assert on._targets is None                                   # the chain yielded to the twin pass
     _same_params(t, on, off, "eager agents, " + target_route)
 
 
@@ -423,8 +423,8 @@ def test_graphed_updates_with_the_switch_are_those_without_it(ctx, target_route)
                 gu.update(0, g, L, batch, it)
     t.cuda.synchronize()
     assert gus[0].captures == gus[1].captures == {(0, 0): 1, (0, 1): 1}          # it = 2, 4 replay graph 0; it = 3 graph 1
-    assert gus[0].slots[0]["targets"] is on._set_targets and gus[1].slots[0]["targets"] is None
-    assert (on._set_targets is not None) == (target_route == "two_forwards")
+    assert gus[0].slots[0]["targets"] is on._targets and gus[1].slots[0]["targets"] is None
+    assert (on._targets is not None) == (target_route == "two_forwards")
     _same_params(t, on, off, "graphed agents, " + target_route)
 
 
@@ -440,7 +440,7 @@ def test_a_replaced_target_module_makes_the_next_capture_raise(ctx, monkeypatch)
     on.models2train()
     gu.warm(0, g, L, _update_batch(L, B, 600), iters=1)
     warmed = gu.slots[0]["targets"]
-    assert warmed is on._set_targets and warmed is not None
+    assert warmed is on._targets and warmed is not None
     on.critic_target = copy.deepcopy(on.critic_target)               # a new module: its handles have run nothing yet
     with pytest.raises(RuntimeError, match="not the one morphology"):
         gu.update(0, g, L, _update_batch(L, B, 601), 1)

@@ -245,7 +245,7 @@ def test_target_chain_against_float64_update_targets():
         # the same through the agent (the same cached handles, its own HipSmpTargets)
         agent.change_morphology(g)
         _, via_agent = agent.update_targets(batch, noise)
-        assert torch.equal(via_agent, got) and agent._smp_targets is not None and agent._smp_targets is not hip
+        assert torch.equal(via_agent, got) and agent._targets is not None and agent._targets is not hip
     # mixed morphologies in one call, rows as wide as the largest
     counts = [50, 100, 106]
     nobs, _ = _inputs(counts, graphs, seed=9)
@@ -378,20 +378,20 @@ def test_agent_update_runs_through_the_chain_and_stays_on_float64():
             assert all(np.isfinite(float(v)) for v in out.values()), (tag, out)
             losses[tag] = float(out["loss/critic_loss"])
         print("update %d critic loss: float64 %.9g  pytorch f32 %.9g  hip targets %.9g" % (it, losses["float64"], losses["pytorch"], losses["hip"]))
-    assert isinstance(hip_agent._smp_targets, HipSmpTargets) and hip_agent.actor_target._smp_hip is not None
-    assert pt_agent._smp_targets is None and pt_agent.actor_target._smp_hip is None and pt_agent.critic_target._smp_hip is None
-    assert f64_agent._smp_targets is None and f64_agent.critic_target._smp_hip is None
+    assert isinstance(hip_agent._targets, HipSmpTargets) and hip_agent.actor_target._smp_hip is not None
+    assert pt_agent._targets is None and pt_agent.actor_target._smp_hip is None and pt_agent.critic_target._smp_hip is None
+    assert f64_agent._targets is None and f64_agent.critic_target._smp_hip is None
     # a CPU agent never constructs a handle either
     cpu_agent = _agent(seed=1, device="cpu")
     cpu_agent.change_morphology({"parents": list(g["parents"])})
     cb = {k: v[:8].cpu() for k, v in _batch(7, 8, seed=3)[0].items()}
     cpu_agent.update_targets(cb)
-    assert cpu_agent._smp_targets is None and cpu_agent.actor_target._smp_hip is None
+    assert cpu_agent._targets is None and cpu_agent.actor_target._smp_hip is None
     # the td-only mode keeps PyTorch
     td_only = _agent(seed=1, bu=False)
     td_only.change_morphology(g)
     td_only.update_targets(_batch(7, 8, seed=3)[0])
-    assert not td_only.use_smp_hip and td_only._smp_targets is None
+    assert not td_only.use_smp_hip and td_only._targets is None
 
 
 # ---- 7 ---------------------------------------------------------------------------------------------------------------------

@@ -92,7 +92,7 @@ def test_agent_picks_the_chain_for_smp_and_smp_with_td_and_bu_only():
 
     def flags(use_hip=True, **over):
         a = Agent(default_train_args(**over), use_hip=use_hip)
-        assert a._smp_targets is None and a._swat_targets is None
+        assert a._targets is None
         return a.use_smp_hip, a.use_swat_hip, a
 
     smp = dict(actor_type="smp", critic_type="smp")
@@ -106,11 +106,11 @@ def test_agent_picks_the_chain_for_smp_and_smp_with_td_and_bu_only():
     assert flags()[:2] == (False, False)                                            # SET
     # a CPU batch never reaches a handle, whatever the flag says; cached handles are not part of a pickled / copied agent
     assert agent._hip_targets(torch.zeros((2, 41))) is None
-    agent._smp_targets = object()
-    assert agent.__getstate__()["_smp_targets"] is None
+    agent._targets = object()
+    assert agent.__getstate__()["_targets"] is None
     agent.actor_target._smp_hip = object()
     assert agent.actor_target.__getstate__()["_smp_hip"] is None
-    agent.actor_target._smp_hip = agent._smp_targets = None
+    agent.actor_target._smp_hip = agent._targets = None
 
 
 # ---- the meaning of plan + schedule ---------------------------------------------------------------------------------------

@@ -368,9 +368,9 @@ def test_agent_update_uses_the_hip_chain_and_stays_on_float64():
         assert all(np.isfinite(float(v)) for v in out.values()), out
         for mod, old in zip((agent.actor, agent.critic), before):
             assert max(float((p.detach() - q).abs().max()) for p, q in zip(mod.parameters(), old)) > 0
-    assert isinstance(hip_agent._swat_targets, HipSwatTargets) and hip_agent.actor_target._swat_hip is not None
-    assert pt_agent._swat_targets is None and pt_agent.critic_target._swat_hip is None
-    assert f64_agent._swat_targets is None
+    assert isinstance(hip_agent._targets, HipSwatTargets) and hip_agent.actor_target._swat_hip is not None
+    assert pt_agent._targets is None and pt_agent.critic_target._swat_hip is None
+    assert f64_agent._targets is None
     ref = losses["float64"]
     dev_hip, dev_pt = abs(losses["hip"] - ref) / abs(ref), abs(losses["pytorch"] - ref) / abs(ref)
     print("critic loss: float64 %.9g  pytorch f32 %.9g (rel dev %.3g)  hip targets %.9g (rel dev %.3g)"

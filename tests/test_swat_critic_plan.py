@@ -129,15 +129,15 @@ def test_cpu_swat_agent_updates_in_pytorch_and_copies_without_handles():
         agent.change_morphology(gd)
         agent.models2train()
         out = agent.update(batch, 0, noise=noise)
-        assert agent._swat_targets is None and agent.actor_target._swat_hip is None and agent.critic_target._swat_hip is None
+        assert agent._targets is None and agent.actor_target._swat_hip is None and agent.critic_target._swat_hip is None
         losses.append((float(out["loss/critic_loss"]), float(out["loss/actor_loss"])))
         assert all(np.isfinite(v) for v in losses[-1])
     assert losses[0] == losses[1]
-    agent._swat_targets = _StubHandle()
+    agent._targets = _StubHandle()
     agent.actor.clear_buffer()                 # the last forward's output (a non-leaf tensor) cannot be deep-copied
     agent.actor_target.clear_buffer()
     twin = copy.deepcopy(agent)
-    assert twin._swat_targets is None and isinstance(agent._swat_targets, _StubHandle)
+    assert twin._targets is None and isinstance(agent._targets, _StubHandle)
     # mixed types never take the SWAT chain
     assert not Agent(default_train_args(actor_type="swat", critic_type="set"), use_hip=False).use_swat_hip
     assert not Agent(default_train_args(actor_type="set", critic_type="set"), use_hip=False).use_swat_hip

@@ -99,8 +99,8 @@ def main():
         ent["speedup_events_median"] = round(ent["events_torch"]["median_ms"] / ent["events_hip"]["median_ms"], 2)
         ent["speedup_wall_median"] = round(ent["wall_torch"]["median_ms_per_call"] / ent["wall_hip"]["median_ms_per_call"], 2)
         res["batches"][str(B)] = ent
-    res["launches"] = {"hip_chain": hip._mlp_targets.launches(), "hip_packs": 2 * hip._mlp_targets.actor.pack_launches()}
-    res["chain_plan"] = hip._mlp_targets.plan()
+    res["launches"] = {"hip_chain": hip._targets.launches(), "hip_packs": 2 * hip._targets.actor.pack_launches()}
+    res["chain_plan"] = hip._targets.plan()
     # a whole update (target chain + critic forward / backward / Adam, every second one with the actor step and the soft update)
     b, noise = batch(256, L, dev, seed=7)
     it = [0, 0]

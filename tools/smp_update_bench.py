@@ -147,7 +147,7 @@ def update(name, arm, updates):
     ms = np.asarray(ms)
     print(json.dumps({"mode": "update", "morphology": name, "limbs": L, "batch": B, "arm": arm,
                       "tree": os.environ.get("SGRL_BENCH_TREE", "this"),
-                      "hip_target_chain": getattr(agent, "_smp_targets", None) is not None,
+                      "hip_target_chain": getattr(agent, "_targets", None) is not None,
                       "train_kernels": bool(getattr(agent, "use_smp_train_kernels", False)),
                       "update_ms_mean": round(float(ms.mean()), 4), "update_ms_median": round(float(np.median(ms)), 4),
                       "update_ms_min": round(float(ms.min()), 4), "update_ms_max": round(float(ms.max()), 4),

@@ -175,7 +175,7 @@ def update(name, arm, updates, streams, dropout=0.0):
     launches = count_launches(step, 9 + updates - (updates % 2))        # an odd iteration first
     print(json.dumps({"mode": "update", "morphology": name, "limbs": L, "batch": B, "arm": arm, "dropout_rate": float(dropout),
                       "launches_per_two_updates": launches,
-                      "hip_target_chain": getattr(agent, "_swat_targets", None) is not None, "twin_streams": bool(streams),
+                      "hip_target_chain": getattr(agent, "_targets", None) is not None, "twin_streams": bool(streams),
                       "train_kernels": bool(getattr(agent, "use_swat_train_kernels", False)),
                       "update_ms_mean": round(float(ms.mean()), 4), "update_ms_median": round(float(np.median(ms)), 4),
                       "update_ms_min": round(float(ms.min()), 4), "critic_only_ms_median": round(float(np.median(ms[1::2])), 4),
