@@ -41,10 +41,8 @@ def soft_update_network(source_network, target_network, tau):
             dev = targets[0].device
             ent = _table("lerp", [(t.data_ptr(), s.data_ptr(), 0, 0, 0, t.numel()) for t, s in zip(targets, sources)], dev)
             if ent is not None:
-                L = _optim_lib()
-                train_ops._check(L, L.sgrl_optim_lerp(ctypes.c_void_p(ent["dev_tab"].data_ptr()), ctypes.c_void_p(ent["dev_chunks"].data_ptr()),
-                                                      ent["n_chunks"], float(tau), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                                 "sgrl_optim_lerp")
+                train_ops._call("sgrl_optim_lerp", ctypes.c_void_p(ent["dev_tab"].data_ptr()), ctypes.c_void_p(ent["dev_chunks"].data_ptr()),
+                                ent["n_chunks"], float(tau), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
                 _touched(list(target_network.parameters()))
                 return
         if targets and targets[0].is_cuda:
@@ -72,16 +70,9 @@ def _touched(params):
 
 
 def _optim_lib():
-    import ctypes
+    """The library with the sgrl_optim_* entry points bound (train_ops._ABI binds every prototype of include/sgrl_train.h)."""
     from . import train_ops
-    L = train_ops._L()
-    if not getattr(L, "_sgrl_optim_bound", False):
-        vp, ci, cf, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double
-        L.sgrl_optim_chunk.restype = ci
-        L.sgrl_optim_clip_adam.argtypes = [vp, ci, vp, ci, cd, cd, cd, cd, cf, vp, vp]
-        L.sgrl_optim_lerp.argtypes = [vp, vp, ci, cf, vp]
-        L._sgrl_optim_bound = True
-    return L
+    return train_ops._L()
 
 
 _spare_pinned = {}    # (dtype, shape) -> pinned host tensors allocated OUTSIDE captures (hipHostMalloc is not permitted inside one)
@@ -126,7 +117,7 @@ def _table(kind, rows, device):
             ent["dev_chunks"].copy_(ent["host_chunks"], non_blocking=True)
             ent["eager_valid"] = True
         return ent
-    chunk = int(_optim_lib().sgrl_optim_chunk())
+    chunk = int(train_ops._L().sgrl_optim_chunk())
     chunks = [(i, o) for i, r in enumerate(rows) for o in range(0, r[5], chunk)]
     host_tab = _pinned_copy(torch.tensor(rows, dtype=torch.int64))
     host_chunks = _pinned_copy(torch.tensor(chunks, dtype=torch.int32))
@@ -193,14 +184,12 @@ def clip_and_step(opt, max_norm):
         return adam_step(opt)
     import ctypes
     from . import train_ops
-    L = _optim_lib()
     beta1, beta2 = group["betas"]
     lr = group["lr"]
-    rc = L.sgrl_optim_clip_adam(ctypes.c_void_p(ent["dev_tab"].data_ptr()), ent["n"], ctypes.c_void_p(ent["dev_chunks"].data_ptr()),
-                                ent["n_chunks"], float(lr), float(beta1), float(beta2), float(group["eps"]),
-                                float(max_norm) if (max_norm and max_norm > 0) else 0.0, ctypes.c_void_p(ent["scratch"].data_ptr()),
-                                ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    train_ops._check(L, rc, "sgrl_optim_clip_adam")
+    train_ops._call("sgrl_optim_clip_adam", ctypes.c_void_p(ent["dev_tab"].data_ptr()), ent["n"], ctypes.c_void_p(ent["dev_chunks"].data_ptr()),
+                    ent["n_chunks"], float(lr), float(beta1), float(beta2), float(group["eps"]),
+                    float(max_norm) if (max_norm and max_norm > 0) else 0.0, ctypes.c_void_p(ent["scratch"].data_ptr()),
+                    ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     _touched(params)
 
 

@@ -19,54 +19,72 @@ import torch.nn.functional as F
 from . import _lib
 
 _bound = False
+_fns = {}              # name -> the bound entry point (_L)
 _ws = {}
 ENABLED = os.environ.get("SGRL_TRAIN_GEMM", "1") != "0"      # 0: vendor GEMMs (A/B comparisons)
+
+# Every prototype of include/sgrl_train.h: name -> (return type, argument types), one letter per type -- p: any pointer, i: int,
+# f: float, d: double, l: int64_t, u: uint64_t, s: const char*.  tests/test_train_ops_abi.py holds each entry to the header.
+_KIND = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float, "d": ctypes.c_double, "l": ctypes.c_int64, "u": ctypes.c_uint64,
+         "s": ctypes.c_char_p}
+_ABI = {
+    "sgrl_train_ws_floats": ("l", ""),
+    "sgrl_linear_forward": ("i", "pipipppiiiiip"),
+    "sgrl_linear_forward_fused": ("i", "pipipppipipiiiiip"),
+    "sgrl_linear_forward_twin_fused": ("i", "ppippippppppippippiiiiip"),
+    "sgrl_linear_backward": ("i", "pipiippipipipippiiipp"),
+    "sgrl_linear_backward_xrelu": ("i", "pipiippipipipippiiiipp"),
+    "sgrl_linear_backward_acc": ("i", "pipiippipipipippiiiiipp"),
+    "sgrl_linear_wgrad_group": ("i", "ippp"),
+    "sgrl_linear_forward_twin": ("i", "ppippippppppiiiiip"),
+    "sgrl_linear_dgrad_twin": ("i", "ppippiippppippippiiip"),
+    "sgrl_linear_dgrad_twin_xrelu": ("i", "ppippiippppippippppiiiip"),
+    "sgrl_linear_dgrad_twin_acc": ("i", "ppippiippppippippppiiiiip"),
+    "sgrl_gram_forward": ("i", "pppip"),
+    "sgrl_gram_backward": ("i", "pppppip"),
+    "sgrl_gram_tri_forward": ("i", "pppip"),
+    "sgrl_gram_tri_backward": ("i", "pppppip"),
+    "sgrl_sym_fold": ("i", "ipppip"),
+    "sgrl_zmat_forward": ("i", "pppip"),
+    "sgrl_zmat_backward": ("i", "pppppip"),
+    "sgrl_add_ln_forward": ("i", "pppppppppiifp"),
+    "sgrl_add_ln_backward": ("i", "ppppppppppiip"),
+    "sgrl_embed3_forward": ("i", "ppppiiipip"),
+    "sgrl_embed3_backward": ("i", "pppppiiiiip"),
+    "sgrl_optim_chunk": ("i", ""),
+    "sgrl_optim_clip_adam": ("i", "pipiddddfpp"),
+    "sgrl_optim_lerp": ("i", "ppifp"),
+    "sgrl_attention_forward": ("i", "ppppfpppiip"),
+    "sgrl_attention_backward": ("i", "pppfpppppppiip"),
+    "sgrl_swat_attention_forward": ("i", "ppfppiip"),
+    "sgrl_swat_attention_backward": ("i", "pfppppiip"),
+    "sgrl_dropout_forward": ("i", "pplfupip"),
+    "sgrl_dropout_backward": ("i", "pplfupip"),
+    "sgrl_swat_attention_forward_dropout": ("i", "ppfppiifupip"),
+    "sgrl_swat_attention_backward_dropout": ("i", "pfppppiifupip"),
+    "sgrl_smp_gather_forward": ("i", "piipiippiippiip"),
+    "sgrl_smp_gather_backward": ("i", "ppppiiiippiippiip"),
+    "sgrl_smp_up_tail_forward": ("i", "ppppppip"),
+    "sgrl_smp_up_tail_backward": ("i", "pppppppip"),
+    "sgrl_row_normalize_forward": ("i", "pppiip"),
+    "sgrl_row_normalize_backward": ("i", "ppppiip"),
+    "sgrl_td3_twin_mse_forward": ("i", "ppplpp"),
+    "sgrl_td3_twin_mse_backward": ("i", "ppplpppp"),
+    "sgrl_td3_neg_mean_forward": ("i", "plpp"),
+    "sgrl_td3_neg_mean_backward": ("i", "lppp"),
+    "sgrl_td3_loss_launches": ("i", ""),
+    "sgrl_train_last_error": ("s", ""),
+}
 
 
 def _L():
     global _bound
     L = _lib.lib()
     if not _bound:
-        vp, ci = ctypes.c_void_p, ctypes.c_int
-        L.sgrl_linear_forward.argtypes = [vp, ci, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, vp]
-        L.sgrl_linear_backward.argtypes = [vp, ci, vp, ci, ci, vp, vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, ci, ci, ci, vp, vp]
-        L.sgrl_linear_backward_xrelu.argtypes = [vp, ci, vp, ci, ci, vp, vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, ci, ci, ci, ci, vp, vp]
-        L.sgrl_linear_dgrad_twin_xrelu.argtypes = [vp, vp, ci, vp, vp, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, vp]
-        L.sgrl_linear_backward_acc.argtypes = [vp, ci, vp, ci, ci, vp, vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, ci, ci, ci, ci, ci, vp, vp]
-        L.sgrl_linear_dgrad_twin_acc.argtypes = [vp, vp, ci, vp, vp, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
-        L.sgrl_linear_forward_twin.argtypes = [vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
-        L.sgrl_linear_dgrad_twin.argtypes = [vp, vp, ci, vp, vp, ci, ci, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, ci, ci, ci, vp]
-        L.sgrl_gram_forward.argtypes = [vp, vp, vp, ci, vp]
-        L.sgrl_gram_backward.argtypes = [vp, vp, vp, vp, vp, ci, vp]
-        L.sgrl_gram_tri_forward.argtypes = [vp, vp, vp, ci, vp]
-        L.sgrl_gram_tri_backward.argtypes = [vp, vp, vp, vp, vp, ci, vp]
-        L.sgrl_sym_fold.argtypes = [ci, vp, vp, vp, ci, vp]
-        L.sgrl_linear_wgrad_group.argtypes = [ci, vp, vp, vp]
-        L.sgrl_zmat_forward.argtypes = [vp, vp, vp, ci, vp]
-        L.sgrl_zmat_backward.argtypes = [vp, vp, vp, vp, vp, ci, vp]
-        L.sgrl_attention_forward.argtypes = [vp, vp, vp, vp, ctypes.c_float, vp, vp, vp, ci, ci, vp]
-        L.sgrl_attention_backward.argtypes = [vp, vp, vp, ctypes.c_float, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp]
-        L.sgrl_swat_attention_forward.argtypes = [vp, vp, ctypes.c_float, vp, vp, ci, ci, vp]
-        L.sgrl_swat_attention_backward.argtypes = [vp, ctypes.c_float, vp, vp, vp, vp, ci, ci, vp]
-        cf, u64 = ctypes.c_float, ctypes.c_uint64
-        L.sgrl_dropout_forward.argtypes = [vp, vp, ctypes.c_int64, cf, u64, vp, ci, vp]
-        L.sgrl_dropout_backward.argtypes = [vp, vp, ctypes.c_int64, cf, u64, vp, ci, vp]
-        L.sgrl_swat_attention_forward_dropout.argtypes = [vp, vp, cf, vp, vp, ci, ci, cf, u64, vp, ci, vp]
-        L.sgrl_swat_attention_backward_dropout.argtypes = [vp, cf, vp, vp, vp, vp, ci, ci, cf, u64, vp, ci, vp]
-        L.sgrl_linear_forward_fused.argtypes = [vp, ci, vp, ci, vp, vp, vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, vp]
-        L.sgrl_linear_forward_twin_fused.argtypes = [vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp, ci, ci, ci, ci, ci, vp]
-        L.sgrl_embed3_forward.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, ci, vp]
-        L.sgrl_embed3_backward.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
-        L.sgrl_add_ln_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ctypes.c_float, vp]
-        L.sgrl_add_ln_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp]
-        L.sgrl_smp_gather_forward.argtypes = [vp, ci, ci, vp, ci, ci, vp, vp, ci, ci, vp, vp, ci, ci, vp]
-        L.sgrl_smp_gather_backward.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, ci, ci, vp, vp, ci, ci, vp]
-        L.sgrl_smp_up_tail_forward.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp]
-        L.sgrl_smp_up_tail_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, vp]
-        L.sgrl_row_normalize_forward.argtypes = [vp, vp, vp, ci, ci, vp]
-        L.sgrl_row_normalize_backward.argtypes = [vp, vp, vp, vp, ci, ci, vp]
-        L.sgrl_train_ws_floats.restype = ctypes.c_int64
-        L.sgrl_train_last_error.restype = ctypes.c_char_p
+        for name, (res, args) in _ABI.items():
+            fn = _fns[name] = getattr(L, name)
+            fn.restype = _KIND[res]
+            fn.argtypes = [_KIND[k] for k in args]
         _bound = True
     return L
 
@@ -74,6 +92,42 @@ def _L():
 def _check(L, rc, what):
     if rc != 0:
         raise _lib.SgrlError("%s failed (%d): %s" % (what, rc, L.sgrl_train_last_error().decode()))
+
+
+def _call(name, *args):
+    """The entry point `name` of the library; a non-zero return code raises SgrlError with the library's message."""
+    if not _bound:
+        _L()
+    rc = _fns[name](*args)
+    if rc != 0:
+        _check(_L(), rc, name)
+
+
+def _p(t):
+    return ctypes.c_void_p(0 if t is None else t.data_ptr())
+
+
+def _st(device):
+    """The current stream of `device` as the ABI's `void* stream`."""
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _f32(device, *shape):
+    return torch.empty(shape, dtype=torch.float32, device=device)
+
+
+def _c(t):
+    """None, or t itself if contiguous, or a contiguous copy."""
+    return t if (t is None or t.is_contiguous()) else t.contiguous()
+
+
+def _rows(t, width):
+    """t [rows, >= width] or stacked [2, rows, >= width] as the product kernels read it: a row-strided view (one part of a
+    concatenation, a slice of a wider tensor) is read as is -- last stride 1, rows at least `width` apart, the stacked pair not
+    reversed --, anything else is copied."""
+    if t.stride(-1) != 1 or t.stride(-2) < width or (t.dim() == 3 and t.stride(0) < 0):
+        return t.contiguous()
+    return t
 
 
 def _scratch(device):
@@ -112,32 +166,81 @@ def deferred_wgrads(enabled=True):
         flush_wgrads(todo)
 
 
+def _leaf_targets(weight, bias):
+    """Where deferred_wgrads may store a layer's postponed gradients: (the weight if it is a leaf, else None; the leaf behind a
+    FOLDED weight (tri_weights), else None; the bias) -- or None where they may not be postponed: the weight neither a leaf nor a
+    folded tensor whose leaf is known, or the bias not a leaf.  Kept by reference so that `.grad` can be set at the flush."""
+    if bias is not None and not bias.is_leaf:
+        return None
+    if weight.is_leaf:
+        return weight, None, bias
+    fold_leaf = getattr(weight, "_sgrl_fold_leaf", None)
+    return None if fold_leaf is None else (None, fold_leaf, bias)
+
+
+class _Wgrad(object):
+    """One layer's weight (+ bias) gradient as sgrl_linear_wgrad_group takes it: dw [N, K] = g^T x and db [N] = the column sums of
+    g, g = dy [M, N] masked by y > 0 (relu; y's rows ldy apart) or divided row-wise by rowdiv.  dw is allocated here, and db if the
+    bias wants a gradient (it rides on the weight's launch, so dw exists even for a frozen weight).  `targets`: _leaf_targets() of
+    the layer; w_param / fold_param / b_param are the tensors whose `.grad` flush_wgrads stores into if the record is POSTPONED
+    (_settle) -- only those among the targets that want a gradient; a folded weight's dw is unfolded into fold_param's.  st: the
+    stream of the backward() call, _st(dev)."""
+    __slots__ = ("dy", "y", "rowdiv", "x", "dw", "db", "ldy", "relu", "dev", "stream", "want_w", "postponable",
+                 "w_param", "fold_param", "b_param")
+
+    def __init__(self, dy, y, rowdiv, x, ldy, relu, targets, want_w, want_b, st):
+        dev = dy.device
+        self.dy, self.y, self.rowdiv, self.x, self.ldy, self.relu = dy, y, rowdiv, x, ldy, relu
+        self.dw = _f32(dev, dy.shape[1], x.shape[1])
+        self.db = _f32(dev, dy.shape[1]) if want_b else None
+        self.dev, self.stream = dev, st
+        self.want_w, self.postponable = want_w, targets is not None
+        w_leaf, fold_leaf, b_leaf = targets or (None, None, None)
+        self.w_param, self.fold_param = (w_leaf if want_w else None), (fold_leaf if want_w else None)
+        self.b_param = b_leaf if want_b else None
+
+
+def _settle(recs):
+    """The fate of the weight-gradient records of one backward() call -> (what autograd gets back for each, [(dw, db)]; the records
+    the caller has to issue NOW, together).  Under deferred_wgrads a record whose targets are known is postponed: autograd sees
+    (None, None), the flush stores into `.grad`.  The others are returned, dw only if the weight itself wanted it."""
+    out, now = [], []
+    for r in recs:
+        if _pending is not None and r.postponable:
+            _pending.append(r)
+            out.append((None, None))
+        else:
+            r.w_param = r.fold_param = r.b_param = None         # nothing is stored: autograd takes the gradients
+            now.append(r)
+            out.append((r.dw if r.want_w else None, r.db))
+    return out, now
+
+
 def flush_wgrads(todo):
     if not todo:
         return
-    L = _L()
     by_stream = {}
-    for rec in todo:
-        by_stream.setdefault((rec["dev"], rec["stream"]), []).append(rec)
-    for (dev, stream), recs in by_stream.items():
+    for r in todo:
+        by_stream.setdefault((r.dev, r.stream.value), []).append(r)
+    for (dev, _), recs in by_stream.items():
         d = np.zeros(len(recs), dtype=_DESC)
         for i, r in enumerate(recs):
-            d[i] = (r["dy"].data_ptr(), 0 if r["y"] is None else r["y"].data_ptr(), 0 if r["rowdiv"] is None else r["rowdiv"].data_ptr(),
-                    r["x"].data_ptr(), r["dw"].data_ptr(), 0 if r["db"] is None else r["db"].data_ptr(), r["dy"].stride(0),
-                    r.get("ldy", r["N"]), r["x"].stride(0), r["K"], r["M"], r["N"], r["K"], 1 if r["relu"] else 0)
-        _check(L, L.sgrl_linear_wgrad_group(len(recs), ctypes.c_void_p(d.ctypes.data), _p(_scratch(dev)), ctypes.c_void_p(stream)),
-               "sgrl_linear_wgrad_group")
+            (M, N), K = r.dy.shape, r.x.shape[1]
+            d[i] = (r.dy.data_ptr(), 0 if r.y is None else r.y.data_ptr(), 0 if r.rowdiv is None else r.rowdiv.data_ptr(),
+                    r.x.data_ptr(), r.dw.data_ptr(), 0 if r.db is None else r.db.data_ptr(), r.dy.stride(0), r.ldy, r.x.stride(0), K, M, N, K,
+                    1 if r.relu else 0)
+        _call("sgrl_linear_wgrad_group", len(recs), ctypes.c_void_p(d.ctypes.data), _p(_scratch(dev)), recs[0].stream)
         with torch.no_grad():
             # gradients of FOLDED weights (tri_weights): spread onto both mirror columns of their leaf parameters, one launch for all
-            folded = [r for r in recs if r.get("fold_param") is not None]
+            folded = [r for r in recs if r.fold_param is not None]
             for i0 in range(0, len(folded), 16):
                 part = folded[i0:i0 + 16]
-                full = [torch.empty_like(r["fold_param"]) for r in part]
-                _sym_fold_call(full, [r["dw"] for r in part], True, dev)
+                full = [torch.empty_like(r.fold_param) for r in part]
+                _sym_fold_call(full, [r.dw for r in part], True, dev)
                 for r, f in zip(part, full):
-                    r["w_param"], r["dw"] = r["fold_param"], f
+                    r.w_param, r.dw = r.fold_param, f
             for r in recs:
-                for prm, g in ((r["w_param"], r["dw"]), (r["b_param"], r["db"])):
+                for prm, g in ((r.w_param, r.dw), (r.b_param, r.db)):
                     if prm is None:
                         continue
                     g = g.view_as(prm)
@@ -145,10 +248,6 @@ def flush_wgrads(todo):
                         prm.grad = g
                     else:
                         prm.grad.add_(g)
-
-
-def _p(t):
-    return ctypes.c_void_p(0 if t is None else t.data_ptr())
 
 
 class _LinearFn(torch.autograd.Function):
@@ -159,49 +258,37 @@ class _LinearFn(torch.autograd.Function):
         # x_relu: x is the output of a ReLU layer whose backward is told `premasked` -- this layer's input gradient comes out masked
         # by x > 0 (the dgrad kernel's epilogue), and THAT layer's two backward products read no mask (include/sgrl_train.h
         # sgrl_linear_backward_xrelu).  Valid when nothing else consumes the ReLU layer's output (the SET feed-forward pairs).
-        L = _L()
         N, K = weight.shape
         assert not premasked or relu
-        x2 = x.reshape(-1, K)
-        if x2.stride(1) != 1 or x2.stride(0) < K:
-            x2 = x2.contiguous()
-        w = weight if weight.is_contiguous() else weight.contiguous()
+        x2 = _rows(x.reshape(-1, K), K)
+        w = _c(weight)
         M = x2.shape[0]
         rd = None
         if rowdiv is not None:
-            rd = rowdiv.reshape(-1)
-            rd = rd if rd.is_contiguous() else rd.contiguous()
+            rd = _c(rowdiv.reshape(-1))
             assert rd.shape[0] == M and not relu
         # fused followers (include/sgrl_train.h sgrl_linear_forward_fused): a residual added to the result, columns appended to it
         nt = 0 if tail is None else tail.shape[-1]
         ad2 = tl2 = None
         if addend is not None:
             assert not relu and rd is None and tail is None
-            ad2 = addend.reshape(M, N)
-            ad2 = ad2 if (ad2.stride(1) == 1 and ad2.stride(0) >= N) else ad2.contiguous()
+            ad2 = _rows(addend.reshape(M, N), N)
         if tail is not None:
-            tl2 = tail.reshape(M, nt)
-            tl2 = tl2 if tl2.is_contiguous() else tl2.contiguous()
-        y = torch.empty((M, N + nt), dtype=torch.float32, device=x.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+            tl2 = _c(tail.reshape(M, nt))
+        dev = x.device
+        y = _f32(dev, M, N + nt)
         if ad2 is None and tl2 is None:
-            _check(L, L.sgrl_linear_forward(_p(x2), x2.stride(0), _p(w), K, _p(bias), _p(rd), _p(y), N, M, N, K, 1 if relu else 0, st),
-                   "sgrl_linear_forward")
+            _call("sgrl_linear_forward", _p(x2), x2.stride(0), _p(w), K, _p(bias), _p(rd), _p(y), N, M, N, K, 1 if relu else 0, _st(dev))
         else:
-            _check(L, L.sgrl_linear_forward_fused(_p(x2), x2.stride(0), _p(w), K, _p(bias), _p(rd), _p(ad2), 0 if ad2 is None else ad2.stride(0),
-                                                  _p(tl2), nt, _p(y), N + nt, M, N, K, 1 if relu else 0, st), "sgrl_linear_forward_fused")
+            _call("sgrl_linear_forward_fused", _p(x2), x2.stride(0), _p(w), K, _p(bias), _p(rd), _p(ad2), 0 if ad2 is None else ad2.stride(0),
+                  _p(tl2), nt, _p(y), N + nt, M, N, K, 1 if relu else 0, _st(dev))
         ctx.ntail = nt
         ctx.ad_shape = None if addend is None else addend.shape
         ctx.tail_shape = None if tail is None else tail.shape
         ctx.save_for_backward(x2, w, y if (relu or rd is not None) else None, rd)
         ctx.has_bias, ctx.relu = bias is not None, bool(relu)
         ctx.x_relu, ctx.mask = bool(x_relu), bool(relu) and not premasked       # mask: dy still has to be masked by y > 0 here
-        # leaf parameters (what deferred_wgrads may postpone): kept by reference so that their .grad can be set at the flush
-        ctx.leaf = (weight, bias) if (weight.is_leaf and (bias is None or bias.is_leaf)) else None
-        # a folded weight (tri_weights) whose leaf is known: its gradient may be postponed too -- it is unfolded into the leaf's .grad
-        # at the flush, and autograd sees no gradient for the folded tensor
-        ctx.fold_leaf = getattr(weight, "_sgrl_fold_leaf", None) if (ctx.leaf is None and (bias is None or bias.is_leaf)) else None
-        ctx.bias_leaf = bias if (bias is not None and bias.is_leaf) else None
+        ctx.targets = _leaf_targets(weight, bias)                               # what deferred_wgrads may postpone
         ctx.x_shape = x.shape
         ctx.rd_shape = None if rowdiv is None else rowdiv.shape
         ctx.slot = slot
@@ -209,53 +296,42 @@ class _LinearFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        L = _L()
         x2, w, yo, rd = ctx.saved_tensors
         N, K = w.shape
         M = x2.shape[0]
         nt = ctx.ntail
-        dyf = dy.reshape(M, N + nt)
-        if dyf.stride(1) != 1 or dyf.stride(0) < N + nt:
-            dyf = dyf.contiguous()
+        dev = dy.device
+        dyf = _rows(dy.reshape(M, N + nt), N + nt)
         dy2 = dyf[:, :N] if nt else dyf             # the product's own columns: a row-strided view, read as is
         ldyo = N + nt                               # row stride of the saved output (ReLU mask / row-divisor gradient)
-        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
-        need_rd = rd is not None and ctx.needs_input_grad[4]
-        if need_b and not need_w:
-            need_w = True                       # the bias gradient rides on the weight-gradient kernel
+        need = ctx.needs_input_grad
+        need_x, need_b = need[0], ctx.has_bias and need[2]
+        need_rd = rd is not None and need[4]
         acc_dx = False
         slot = ctx.slot if need_x else None
         if slot is not None and slot.buf is not None:          # a sibling consumer was here first: add onto its gradient
             dx, acc_dx = slot.buf.view(M, K), True
         else:
-            dx = torch.empty((M, K), dtype=torch.float32, device=dy.device) if need_x else None
+            dx = _f32(dev, M, K) if need_x else None
             if slot is not None:
                 slot.buf = dx
-        dw = torch.empty((N, K), dtype=torch.float32, device=dy.device) if need_w else None
-        db = torch.empty((N,), dtype=torch.float32, device=dy.device) if need_b else None
-        drd = torch.empty((M,), dtype=torch.float32, device=dy.device) if need_rd else None
-        stream = torch.cuda.current_stream(dy.device).cuda_stream
-        st = ctypes.c_void_p(stream)
-        now_w, now_b = dw, db
-        deferred = _pending is not None and need_w and (ctx.leaf is not None or ctx.fold_leaf is not None)
-        if deferred:                              # postponed: computed and stored into .grad when the deferred_wgrads context exits
-            folded = ctx.leaf is None
-            _pending.append({"dy": dy2, "y": yo if ctx.mask else None, "rowdiv": rd, "x": x2, "dw": dw, "db": db, "M": M, "N": N,
-                             "K": K, "relu": ctx.mask, "dev": dy.device, "stream": stream, "ldy": ldyo,
-                             "w_param": ctx.leaf[0] if (not folded and ctx.needs_input_grad[1]) else None,
-                             "fold_param": ctx.fold_leaf if (folded and ctx.needs_input_grad[1]) else None,
-                             "b_param": (ctx.bias_leaf if need_b else None)})
-            now_w = now_b = None
-        if dx is not None or now_w is not None or now_b is not None or drd is not None:
-            _check(L, L.sgrl_linear_backward_acc(_p(dy2), dy2.stride(0), _p(yo), ldyo, 1 if ctx.mask else 0, _p(rd), _p(x2), x2.stride(0),
-                                                 _p(w), K, _p(dx), K, _p(now_w), K, _p(now_b), _p(drd), M, N, K, 1 if ctx.x_relu else 0,
-                                                 1 if acc_dx else 0, _p(_scratch(dy.device)), st), "sgrl_linear_backward_acc")
-        dadd = dy.reshape(ctx.ad_shape) if (ctx.ad_shape is not None and ctx.needs_input_grad[5]) else None
-        dtail = dyf[:, N:].reshape(ctx.tail_shape) if (nt and ctx.needs_input_grad[6]) else None
+        # the bias gradient rides on the weight-gradient kernel, so a record exists for either
+        st = _st(dev)
+        recs = [_Wgrad(dy2, yo if ctx.mask else None, rd, x2, ldyo, ctx.mask, ctx.targets, need[1], need_b, st)] if (need[1] or need_b) else []
+        drd = _f32(dev, M) if need_rd else None
+        grads, now = _settle(recs)
+        gw, gb = grads[0] if grads else (None, None)
+        now_w, now_b = (now[0].dw, now[0].db) if now else (None, None)     # not postponed: the launch below computes them with dx
+        if dx is not None or now_w is not None or drd is not None:
+            _call("sgrl_linear_backward_acc", _p(dy2), dy2.stride(0), _p(yo), ldyo, 1 if ctx.mask else 0, _p(rd), _p(x2), x2.stride(0),
+                  _p(w), K, _p(dx), K, _p(now_w), K, _p(now_b), _p(drd), M, N, K, 1 if ctx.x_relu else 0, 1 if acc_dx else 0,
+                  _p(_scratch(dev)), st)
+        dadd = dy.reshape(ctx.ad_shape) if (ctx.ad_shape is not None and need[5]) else None
+        dtail = dyf[:, N:].reshape(ctx.tail_shape) if (nt and need[6]) else None
         # (a slot consumer hands its gradient to the fan-out through the slot: the first one also returns it so that the fan-out's
         # backward is certain to run; the others return nothing)
-        return (dx.view(ctx.x_shape) if (need_x and not acc_dx) else None), (None if deferred else (dw if ctx.needs_input_grad[1] else None)), \
-               (None if deferred else db), None, (drd.view(ctx.rd_shape) if need_rd else None), dadd, dtail, None, None, None
+        return (dx.view(ctx.x_shape) if (need_x and not acc_dx) else None), gw, gb, None, (drd.view(ctx.rd_shape) if need_rd else None), \
+            dadd, dtail, None, None, None
 
 
 class _Linear2Fn(torch.autograd.Function):
@@ -264,59 +340,47 @@ class _Linear2Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w0, w1, b0, b1, relu, rowdiv, shared, addend=None, tail=None, x_relu=False, premasked=False, slot=None):
-        L = _L()
         assert slot is None or not shared
         N, K = w0.shape
         assert w1.shape == w0.shape and (b0 is None) == (b1 is None)
         assert (not premasked or relu) and not (x_relu and shared)        # x_relu / premasked: see _LinearFn
         lead = x.shape[:-1] if shared else x.shape[1:-1]
-        xs = x.reshape(-1, K) if shared else x.reshape(2, -1, K)
-        if xs.stride(-1) != 1 or xs.stride(-2) < K or (not shared and xs.stride(0) < 0):
-            xs = xs.contiguous()
+        xs = _rows(x.reshape(-1, K) if shared else x.reshape(2, -1, K), K)
         M = xs.shape[-2]
         x0, x1 = (xs, xs) if shared else (xs[0], xs[1])
-        params = ((w0, b0), (w1, b1))               # the tensors autograd knows (leaf parameters, or e.g. a concatenation of some)
-        w0 = w0 if w0.is_contiguous() else w0.contiguous()
-        w1 = w1 if w1.is_contiguous() else w1.contiguous()
+        # the tensors autograd knows (leaf parameters, or e.g. a concatenation of some): what deferred_wgrads may postpone
+        ctx.targets = [_leaf_targets(w0, b0), _leaf_targets(w1, b1)]
+        w0, w1 = _c(w0), _c(w1)
         rd = None
         if rowdiv is not None:
-            rd = rowdiv.reshape(2, -1)
-            rd = rd if rd.is_contiguous() else rd.contiguous()
+            rd = _c(rowdiv.reshape(2, -1))
             assert rd.shape[1] == M and not relu
+        rd0, rd1 = (None, None) if rd is None else (rd[0], rd[1])
         # fused followers: addend [2, ..., N] (a residual per network), tail [..., nt] or [2, ..., nt] (columns appended to each result)
         nt = 0 if tail is None else tail.shape[-1]
         ad2 = tl = None
         if addend is not None:
             assert not relu and rd is None and tail is None
-            ad2 = addend.reshape(2, M, N)
-            ad2 = ad2 if ad2.is_contiguous() else ad2.contiguous()
+            ad2 = _c(addend.reshape(2, M, N))
         if tail is not None:
-            tl = tail.reshape(-1, M, nt)             # one tail both networks share, or one each
-            tl = tl if tl.is_contiguous() else tl.contiguous()
+            tl = _c(tail.reshape(-1, M, nt))         # one tail both networks share, or one each
             tl = (tl[0], tl[0]) if tl.shape[0] == 1 else (tl[0], tl[1])
-        y = torch.empty((2, M, N + nt), dtype=torch.float32, device=x.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        dev = x.device
+        y = _f32(dev, 2, M, N + nt)
         if ad2 is None and tl is None:
-            _check(L, L.sgrl_linear_forward_twin(_p(x0), _p(x1), xs.stride(-2), _p(w0), _p(w1), K, _p(b0), _p(b1),
-                                                 _p(None if rd is None else rd[0]), _p(None if rd is None else rd[1]), _p(y[0]), _p(y[1]),
-                                                 N, M, N, K, 1 if relu else 0, st), "sgrl_linear_forward_twin")
+            _call("sgrl_linear_forward_twin", _p(x0), _p(x1), xs.stride(-2), _p(w0), _p(w1), K, _p(b0), _p(b1), _p(rd0), _p(rd1),
+                  _p(y[0]), _p(y[1]), N, M, N, K, 1 if relu else 0, _st(dev))
         else:
-            _check(L, L.sgrl_linear_forward_twin_fused(_p(x0), _p(x1), xs.stride(-2), _p(w0), _p(w1), K, _p(b0), _p(b1),
-                                                       _p(None if rd is None else rd[0]), _p(None if rd is None else rd[1]),
-                                                       _p(None if ad2 is None else ad2[0]), _p(None if ad2 is None else ad2[1]), N,
-                                                       _p(None if tl is None else tl[0]), _p(None if tl is None else tl[1]), nt,
-                                                       _p(y[0]), _p(y[1]), N + nt, M, N, K, 1 if relu else 0, st),
-                   "sgrl_linear_forward_twin_fused")
+            _call("sgrl_linear_forward_twin_fused", _p(x0), _p(x1), xs.stride(-2), _p(w0), _p(w1), K, _p(b0), _p(b1), _p(rd0), _p(rd1),
+                  _p(None if ad2 is None else ad2[0]), _p(None if ad2 is None else ad2[1]), N,
+                  _p(None if tl is None else tl[0]), _p(None if tl is None else tl[1]), nt,
+                  _p(y[0]), _p(y[1]), N + nt, M, N, K, 1 if relu else 0, _st(dev))
         ctx.ntail = nt
         ctx.ad_shape = None if addend is None else addend.shape
         ctx.tail_shape = None if tail is None else tail.shape
         ctx.save_for_backward(xs, w0, w1, y if (relu or rd is not None) else None, rd)
         ctx.has_bias, ctx.relu, ctx.shared = b0 is not None, bool(relu), bool(shared)
         ctx.x_relu, ctx.mask = bool(x_relu), bool(relu) and not premasked
-        ctx.leaf = [((w, b) if (w.is_leaf and (b is None or b.is_leaf)) else None) for w, b in params]
-        ctx.fold_leaf = [(getattr(w, "_sgrl_fold_leaf", None) if (lf is None and (b is None or b.is_leaf)) else None)
-                         for (w, b), lf in zip(params, ctx.leaf)]
-        ctx.params = params
         ctx.x_shape = x.shape
         ctx.rd_shape = None if rowdiv is None else rowdiv.shape
         ctx.slot = slot
@@ -324,76 +388,85 @@ class _Linear2Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        L = _L()
         xs, w0, w1, yo, rd = ctx.saved_tensors
         N, K = w0.shape
         M = xs.shape[-2]
         nt = ctx.ntail
-        dyf = dy.reshape(2, M, N + nt)               # a row-strided view (the gradient of one part of a concatenation) is read as is
-        if dyf.stride(2) != 1 or dyf.stride(1) < N + nt or dyf.stride(0) < 0:
-            dyf = dyf.contiguous()
+        dyf = _rows(dy.reshape(2, M, N + nt), N + nt)      # a row-strided view (the gradient of one part of a concatenation) is read as is
         dy2 = dyf[:, :, :N] if nt else dyf
         lddy = dy2.stride(1)
         ldyo = N + nt
-        need_x = ctx.needs_input_grad[0]
-        need_w = [ctx.needs_input_grad[1], ctx.needs_input_grad[2]]
-        need_b = [ctx.has_bias and ctx.needs_input_grad[3], ctx.has_bias and ctx.needs_input_grad[4]]
-        need_rd = rd is not None and ctx.needs_input_grad[6]
+        need = ctx.needs_input_grad
+        need_x = need[0]
+        need_w = [need[1], need[2]]
+        need_b = [ctx.has_bias and need[3], ctx.has_bias and need[4]]
+        need_rd = rd is not None and need[6]
         dev = dy.device
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        st = ctypes.c_void_p(stream)
+        st = _st(dev)
         acc_dx = False
         slot = ctx.slot if need_x else None
         if slot is not None and slot.buf is not None:
             dx, acc_dx = slot.buf.view(2, M, K), True
         else:
-            dx = torch.empty((2, M, K), dtype=torch.float32, device=dev) if need_x else None
+            dx = _f32(dev, 2, M, K) if need_x else None
             if slot is not None:
                 slot.buf = dx
-        drd = torch.empty((2, M), dtype=torch.float32, device=dev) if need_rd else None
+        drd = _f32(dev, 2, M) if need_rd else None
         if need_x:
             xm = (xs[0], xs[1]) if ctx.x_relu else (None, None)
-            _check(L, L.sgrl_linear_dgrad_twin_acc(_p(dy2[0]), _p(dy2[1]), lddy, _p(None if yo is None else yo[0]),
-                                                   _p(None if yo is None else yo[1]), ldyo, 1 if ctx.mask else 0,
-                                                   _p(None if rd is None else rd[0]), _p(None if rd is None else rd[1]),
-                                                   _p(w0), _p(w1), K, _p(dx[0]), _p(dx[1]), K, _p(None if drd is None else drd[0]),
-                                                   _p(None if drd is None else drd[1]), _p(xm[0]), _p(xm[1]), xs.stride(-2), M, N, K,
-                                                   1 if acc_dx else 0, st), "sgrl_linear_dgrad_twin_acc")
+            _call("sgrl_linear_dgrad_twin_acc", _p(dy2[0]), _p(dy2[1]), lddy, _p(None if yo is None else yo[0]),
+                  _p(None if yo is None else yo[1]), ldyo, 1 if ctx.mask else 0,
+                  _p(None if rd is None else rd[0]), _p(None if rd is None else rd[1]),
+                  _p(w0), _p(w1), K, _p(dx[0]), _p(dx[1]), K, _p(None if drd is None else drd[0]),
+                  _p(None if drd is None else drd[1]), _p(xm[0]), _p(xm[1]), xs.stride(-2), M, N, K,
+                  1 if acc_dx else 0, st)
         elif need_rd:                               # the row divisor's gradient without an input gradient: the single-network kernel twice
             for i in range(2):
-                _check(L, L.sgrl_linear_backward(_p(dy2[i]), lddy, _p(yo[i]), ldyo, 0, _p(rd[i]), _p(None), 0, _p(None), 0, _p(None), 0,
-                                                 _p(None), 0, _p(None), _p(drd[i]), M, N, K, _p(_scratch(dev)), st), "sgrl_linear_backward")
-        # weight / bias gradients: one descriptor per network -- postponed (deferred_wgrads) or issued together now
-        grads_w, grads_b, recs = [None, None], [None, None], []
-        for i, (w, b) in enumerate(ctx.params):
-            if not (need_w[i] or need_b[i]):
-                continue
-            x_i = xs if ctx.shared else xs[i]
-            dw = torch.empty((N, K), dtype=torch.float32, device=dev)
-            db = torch.empty((N,), dtype=torch.float32, device=dev) if need_b[i] else None
-            folded = ctx.leaf[i] is None and ctx.fold_leaf[i] is not None
-            deferred = _pending is not None and (ctx.leaf[i] is not None or folded)
-            rec = {"dy": dy2[i], "y": yo[i] if ctx.mask else None, "rowdiv": None if rd is None else rd[i], "x": x_i, "dw": dw, "db": db,
-                   "M": M, "N": N, "K": K, "relu": ctx.mask, "dev": dev, "stream": stream, "ldy": ldyo,
-                   "w_param": (w if need_w[i] else None) if (deferred and not folded) else None,
-                   "fold_param": (ctx.fold_leaf[i] if need_w[i] else None) if (deferred and folded) else None,
-                   "b_param": (b if need_b[i] else None) if deferred else None}
-            if deferred:
-                _pending.append(rec)
-            else:
-                recs.append(rec)
-                grads_w[i], grads_b[i] = (dw if need_w[i] else None), db
-        if recs:
-            flush_wgrads(recs)                      # w_param / b_param are None: nothing is stored, the gradients are returned below
+                _call("sgrl_linear_backward", _p(dy2[i]), lddy, _p(yo[i]), ldyo, 0, _p(rd[i]), _p(None), 0, _p(None), 0, _p(None), 0,
+                      _p(None), 0, _p(None), _p(drd[i]), M, N, K, _p(_scratch(dev)), st)
+        # weight / bias gradients: one record per network -- postponed (deferred_wgrads) or issued together now
+        nets = [i for i in range(2) if need_w[i] or need_b[i]]
+        recs = [_Wgrad(dy2[i], yo[i] if ctx.mask else None, None if rd is None else rd[i], xs if ctx.shared else xs[i], ldyo, ctx.mask,
+                       ctx.targets[i], need_w[i], need_b[i], st) for i in nets]
+        grads, now = _settle(recs)
+        flush_wgrads(now)
+        grads_w, grads_b = [None, None], [None, None]
+        for i, (gw, gb) in zip(nets, grads):
+            grads_w[i], grads_b[i] = gw, gb
         dx_out = None
         if need_x and not acc_dx:
             dx_out = (dx[0] + dx[1]).view(ctx.x_shape) if ctx.shared else dx.view(ctx.x_shape)
-        dadd = dy.reshape(ctx.ad_shape) if (ctx.ad_shape is not None and ctx.needs_input_grad[8]) else None
+        dadd = dy.reshape(ctx.ad_shape) if (ctx.ad_shape is not None and need[8]) else None
         dtail = None
-        if nt and ctx.needs_input_grad[9]:
+        if nt and need[9]:
             dtail = dyf[:, :, N:].reshape(2, *ctx.x_shape[(0 if ctx.shared else 1):-1], nt).sum_to_size(ctx.tail_shape)
         return dx_out, grads_w[0], grads_w[1], grads_b[0], grads_b[1], None, (drd.view(ctx.rd_shape) if need_rd else None), None, dadd, dtail, \
             None, None, None
+
+
+TRI = 528      # lower triangle of a symmetric 32 x 32 matrix, packed k = a (a + 1) / 2 + b (include/sgrl_train.h)
+
+
+def _gram_forward(ctx, name, width, z):
+    z2 = _c(z.reshape(-1, 96))
+    M = z2.shape[0]
+    gram = _f32(z.device, M, width)
+    fn = _f32(z.device, M)
+    _call(name, _p(z2), _p(gram), _p(fn), M, _st(z.device))
+    ctx.save_for_backward(z2, fn)
+    ctx.z_shape = z.shape
+    lead = z.shape[:-2]
+    return gram.view(*lead, width), fn.view(*lead, 1)
+
+
+def _gram_backward(ctx, name, width, dgram, dfn):
+    z2, fn = ctx.saved_tensors
+    M = z2.shape[0]
+    dg = None if dgram is None else _c(dgram.reshape(M, width))
+    df = None if dfn is None else _c(dfn.reshape(M))
+    dz = _f32(z2.device, M, 96)
+    _call(name, _p(z2), _p(dg), _p(df), _p(fn), _p(dz), M, _st(z2.device))
+    return dz.view(ctx.z_shape)
 
 
 class _GramFn(torch.autograd.Function):
@@ -401,37 +474,11 @@ class _GramFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z):
-        L = _L()
-        z2 = z.reshape(-1, 96)
-        z2 = z2 if z2.is_contiguous() else z2.contiguous()
-        M = z2.shape[0]
-        gram = torch.empty((M, 1024), dtype=torch.float32, device=z.device)
-        fn = torch.empty((M,), dtype=torch.float32, device=z.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(z.device).cuda_stream)
-        _check(L, L.sgrl_gram_forward(_p(z2), _p(gram), _p(fn), M, st), "sgrl_gram_forward")
-        ctx.save_for_backward(z2, fn)
-        ctx.z_shape = z.shape
-        lead = z.shape[:-2]
-        return gram.view(*lead, 1024), fn.view(*lead, 1)
+        return _gram_forward(ctx, "sgrl_gram_forward", 1024, z)
 
     @staticmethod
     def backward(ctx, dgram, dfn):
-        L = _L()
-        z2, fn = ctx.saved_tensors
-        M = z2.shape[0]
-        dg = None if dgram is None else dgram.reshape(M, 1024)
-        if dg is not None and not dg.is_contiguous():
-            dg = dg.contiguous()
-        df = None if dfn is None else dfn.reshape(M)
-        if df is not None and not df.is_contiguous():
-            df = df.contiguous()
-        dz = torch.empty((M, 96), dtype=torch.float32, device=z2.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(z2.device).cuda_stream)
-        _check(L, L.sgrl_gram_backward(_p(z2), _p(dg), _p(df), _p(fn), _p(dz), M, st), "sgrl_gram_backward")
-        return dz.view(ctx.z_shape)
-
-
-TRI = 528      # lower triangle of a symmetric 32 x 32 matrix, packed k = a (a + 1) / 2 + b (include/sgrl_train.h)
+        return _gram_backward(ctx, "sgrl_gram_backward", 1024, dgram, dfn)
 
 
 class _GramTriFn(torch.autograd.Function):
@@ -439,34 +486,11 @@ class _GramTriFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z):
-        L = _L()
-        z2 = z.reshape(-1, 96)
-        z2 = z2 if z2.is_contiguous() else z2.contiguous()
-        M = z2.shape[0]
-        tri = torch.empty((M, TRI), dtype=torch.float32, device=z.device)
-        fn = torch.empty((M,), dtype=torch.float32, device=z.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(z.device).cuda_stream)
-        _check(L, L.sgrl_gram_tri_forward(_p(z2), _p(tri), _p(fn), M, st), "sgrl_gram_tri_forward")
-        ctx.save_for_backward(z2, fn)
-        ctx.z_shape = z.shape
-        lead = z.shape[:-2]
-        return tri.view(*lead, TRI), fn.view(*lead, 1)
+        return _gram_forward(ctx, "sgrl_gram_tri_forward", TRI, z)
 
     @staticmethod
     def backward(ctx, dtri, dfn):
-        L = _L()
-        z2, fn = ctx.saved_tensors
-        M = z2.shape[0]
-        dg = None if dtri is None else dtri.reshape(M, TRI)
-        if dg is not None and not dg.is_contiguous():
-            dg = dg.contiguous()
-        df = None if dfn is None else dfn.reshape(M)
-        if df is not None and not df.is_contiguous():
-            df = df.contiguous()
-        dz = torch.empty((M, 96), dtype=torch.float32, device=z2.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(z2.device).cuda_stream)
-        _check(L, L.sgrl_gram_tri_backward(_p(z2), _p(dg), _p(df), _p(fn), _p(dz), M, st), "sgrl_gram_tri_backward")
-        return dz.view(ctx.z_shape)
+        return _gram_backward(ctx, "sgrl_gram_tri_backward", TRI, dtri, dfn)
 
 
 def _sym_fold_call(full, tri, unfold, device):
@@ -474,8 +498,7 @@ def _sym_fold_call(full, tri, unfold, device):
     pw = (ctypes.c_void_p * n)(*[t.data_ptr() for t in full])
     pt = (ctypes.c_void_p * n)(*[t.data_ptr() for t in tri])
     rows = (ctypes.c_int * n)(*[t.shape[0] for t in full])
-    st = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    _check(_L(), _L().sgrl_sym_fold(n, pw, pt, rows, 1 if unfold else 0, st), "sgrl_sym_fold")
+    _call("sgrl_sym_fold", n, pw, pt, rows, 1 if unfold else 0, _st(device))
 
 
 class _FoldFn(torch.autograd.Function):
@@ -485,8 +508,8 @@ class _FoldFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, *ws):
         ctx.set_materialize_grads(False)       # a folded weight whose gradient was postponed (deferred_wgrads) gets None here, not zeros to unfold
-        ws = [w if w.is_contiguous() else w.contiguous() for w in ws]
-        out = [torch.empty((w.shape[0], TRI), dtype=torch.float32, device=w.device) for w in ws]
+        ws = [_c(w) for w in ws]
+        out = [_f32(w.device, w.shape[0], TRI) for w in ws]
         _sym_fold_call(ws, out, False, ws[0].device)
         ctx.shapes = [w.shape for w in ws]
         return tuple(out)
@@ -496,8 +519,8 @@ class _FoldFn(torch.autograd.Function):
         idx = [i for i, d in enumerate(ds) if d is not None and ctx.needs_input_grad[i]]
         res = [None] * len(ds)
         if idx:
-            src = [ds[i] if ds[i].is_contiguous() else ds[i].contiguous() for i in idx]
-            full = [torch.empty(tuple(ctx.shapes[i]), dtype=torch.float32, device=src[0].device) for i in idx]
+            src = [_c(ds[i]) for i in idx]
+            full = [_f32(src[0].device, *ctx.shapes[i]) for i in idx]
             _sym_fold_call(full, src, True, src[0].device)
             for i, f in zip(idx, full):
                 res[i] = f
@@ -509,28 +532,21 @@ class _ZmatFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, mat):
-        L = _L()
-        z2, m2 = z.reshape(-1, 96), mat.reshape(-1, 1024)
-        z2 = z2 if z2.is_contiguous() else z2.contiguous()
-        m2 = m2 if m2.is_contiguous() else m2.contiguous()
+        z2, m2 = _c(z.reshape(-1, 96)), _c(mat.reshape(-1, 1024))
         M = z2.shape[0]
-        t = torch.empty((M, 96), dtype=torch.float32, device=z.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(z.device).cuda_stream)
-        _check(L, L.sgrl_zmat_forward(_p(z2), _p(m2), _p(t), M, st), "sgrl_zmat_forward")
+        t = _f32(z.device, M, 96)
+        _call("sgrl_zmat_forward", _p(z2), _p(m2), _p(t), M, _st(z.device))
         ctx.save_for_backward(z2, m2)
         ctx.shapes = (z.shape, mat.shape)
         return t.view(z.shape)
 
     @staticmethod
     def backward(ctx, dt):
-        L = _L()
         z2, m2 = ctx.saved_tensors
         M = z2.shape[0]
-        d = dt.reshape(M, 96)
-        d = d if d.is_contiguous() else d.contiguous()
+        d = _c(dt.reshape(M, 96))
         dz, dm = torch.empty_like(z2), torch.empty_like(m2)
-        st = ctypes.c_void_p(torch.cuda.current_stream(z2.device).cuda_stream)
-        _check(L, L.sgrl_zmat_backward(_p(z2), _p(m2), _p(d), _p(dz), _p(dm), M, st), "sgrl_zmat_backward")
+        _call("sgrl_zmat_backward", _p(z2), _p(m2), _p(d), _p(dz), _p(dm), M, _st(z2.device))
         return dz.view(ctx.shapes[0]), dm.view(ctx.shapes[1])
 
 
@@ -539,35 +555,61 @@ class _AttnFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, vgp, gdir, bias, scale):
-        L = _L()
         B, Ln = qkv.shape[0], qkv.shape[1]
-        qkv, vgp, gdir = (t if t.is_contiguous() else t.contiguous() for t in (qkv, vgp, gdir))
-        bz = None if bias is None else (bias if bias.is_contiguous() else bias.contiguous())
-        w = torch.empty((B, 2, Ln, Ln), dtype=torch.float32, device=qkv.device)
-        o = torch.empty((B, Ln, 256), dtype=torch.float32, device=qkv.device)
-        og = torch.empty((B, Ln, 3, 256), dtype=torch.float32, device=qkv.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream)
-        _check(L, L.sgrl_attention_forward(_p(qkv), _p(vgp), _p(gdir), _p(bz), ctypes.c_float(scale), _p(w), _p(o), _p(og), B, Ln, st),
-               "sgrl_attention_forward")
+        qkv, vgp, gdir, bz = _c(qkv), _c(vgp), _c(gdir), _c(bias)
+        dev = qkv.device
+        w = _f32(dev, B, 2, Ln, Ln)
+        o = _f32(dev, B, Ln, 256)
+        og = _f32(dev, B, Ln, 3, 256)
+        _call("sgrl_attention_forward", _p(qkv), _p(vgp), _p(gdir), _p(bz), ctypes.c_float(scale), _p(w), _p(o), _p(og), B, Ln, _st(dev))
         ctx.save_for_backward(qkv, vgp, gdir, w)
         ctx.has_bias, ctx.scale = bias is not None, float(scale)
         return o, og
 
     @staticmethod
     def backward(ctx, d_o, d_og):
-        L = _L()
         qkv, vgp, gdir, w = ctx.saved_tensors
         B, Ln = qkv.shape[0], qkv.shape[1]
-        d_o = torch.zeros((B, Ln, 256), dtype=torch.float32, device=qkv.device) if d_o is None else (d_o if d_o.is_contiguous() else d_o.contiguous())
-        d_og = torch.zeros((B, Ln, 3, 256), dtype=torch.float32, device=qkv.device) if d_og is None else (d_og if d_og.is_contiguous() else d_og.contiguous())
+        dev = qkv.device
+        d_o = torch.zeros((B, Ln, 256), dtype=torch.float32, device=dev) if d_o is None else _c(d_o)
+        d_og = torch.zeros((B, Ln, 3, 256), dtype=torch.float32, device=dev) if d_og is None else _c(d_og)
         dqkv, dvgp, ds = torch.empty_like(qkv), torch.empty_like(vgp), torch.empty_like(w)
-        dgdh = torch.empty((B, Ln, 3, 2, 2), dtype=torch.float32, device=qkv.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream)
-        _check(L, L.sgrl_attention_backward(_p(qkv), _p(vgp), _p(gdir), ctypes.c_float(ctx.scale), _p(w), _p(d_o), _p(d_og), _p(dqkv),
-                                            _p(dvgp), _p(dgdh), _p(ds), B, Ln, st), "sgrl_attention_backward")
+        dgdh = _f32(dev, B, Ln, 3, 2, 2)
+        _call("sgrl_attention_backward", _p(qkv), _p(vgp), _p(gdir), ctypes.c_float(ctx.scale), _p(w), _p(d_o), _p(d_og), _p(dqkv),
+              _p(dvgp), _p(dgdh), _p(ds), B, Ln, _st(dev))
         dgdir = dgdh.sum(3) if ctx.needs_input_grad[2] else None
         dbias = ds.sum(0) if (ctx.has_bias and ctx.needs_input_grad[3]) else None
         return dqkv, dvgp, dgdir, dbias, None
+
+
+def _drop_args(call):
+    """The ABI arguments of a counter-RNG dropout call (p, seed, step tensor, site); none for an empty call."""
+    if not call:
+        return ()
+    p, seed, step, site = call
+    return ctypes.c_float(p), ctypes.c_uint64(seed), _p(step), site
+
+
+def _swat_attn_forward(ctx, name, qkv, bias, scale, *call):
+    B, Ln = qkv.shape[0], qkv.shape[1]
+    qkv, bz = _c(qkv), _c(bias)
+    dev = qkv.device
+    w = _f32(dev, B, 2, Ln, Ln)
+    o = _f32(dev, B, Ln, 128)
+    _call(name, _p(qkv), _p(bz), ctypes.c_float(scale), _p(w), _p(o), B, Ln, *_drop_args(call), _st(dev))
+    ctx.save_for_backward(qkv, w)
+    ctx.has_bias, ctx.scale, ctx.call = bias is not None, float(scale), call
+    return o
+
+
+def _swat_attn_backward(ctx, name, d_o):
+    qkv, w = ctx.saved_tensors
+    B, Ln = qkv.shape[0], qkv.shape[1]
+    d_o = _c(d_o)
+    dqkv, ds = torch.empty_like(qkv), torch.empty_like(w)
+    _call(name, _p(qkv), ctypes.c_float(ctx.scale), _p(w), _p(d_o), _p(dqkv), _p(ds), B, Ln, *_drop_args(ctx.call), _st(qkv.device))
+    dbias = ds.sum(0) if (ctx.has_bias and ctx.needs_input_grad[1]) else None
+    return ((dqkv if ctx.needs_input_grad[0] else None), dbias, None) + (None,) * len(ctx.call)
 
 
 class _SwatAttnFn(torch.autograd.Function):
@@ -576,30 +618,11 @@ class _SwatAttnFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, bias, scale):
-        L = _L()
-        B, Ln = qkv.shape[0], qkv.shape[1]
-        qkv = qkv if qkv.is_contiguous() else qkv.contiguous()
-        bz = None if bias is None else (bias if bias.is_contiguous() else bias.contiguous())
-        w = torch.empty((B, 2, Ln, Ln), dtype=torch.float32, device=qkv.device)
-        o = torch.empty((B, Ln, 128), dtype=torch.float32, device=qkv.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream)
-        _check(L, L.sgrl_swat_attention_forward(_p(qkv), _p(bz), ctypes.c_float(scale), _p(w), _p(o), B, Ln, st), "sgrl_swat_attention_forward")
-        ctx.save_for_backward(qkv, w)
-        ctx.has_bias, ctx.scale = bias is not None, float(scale)
-        return o
+        return _swat_attn_forward(ctx, "sgrl_swat_attention_forward", qkv, bias, scale)
 
     @staticmethod
     def backward(ctx, d_o):
-        L = _L()
-        qkv, w = ctx.saved_tensors
-        B, Ln = qkv.shape[0], qkv.shape[1]
-        d_o = d_o if d_o.is_contiguous() else d_o.contiguous()
-        dqkv, ds = torch.empty_like(qkv), torch.empty_like(w)
-        st = ctypes.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream)
-        _check(L, L.sgrl_swat_attention_backward(_p(qkv), ctypes.c_float(ctx.scale), _p(w), _p(d_o), _p(dqkv), _p(ds), B, Ln, st),
-               "sgrl_swat_attention_backward")
-        dbias = ds.sum(0) if (ctx.has_bias and ctx.needs_input_grad[1]) else None
-        return (dqkv if ctx.needs_input_grad[0] else None), dbias, None
+        return _swat_attn_backward(ctx, "sgrl_swat_attention_backward", d_o)
 
 
 class _AddLNFn(torch.autograd.Function):
@@ -608,41 +631,32 @@ class _AddLNFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, res, w0, b0, w1, b1, eps):
-        L = _L()
         nets = 2 if w1 is not None else 1
-        x2 = x.reshape(-1, 128)
-        x2 = x2 if x2.is_contiguous() else x2.contiguous()
-        r2 = None
-        if res is not None:
-            r2 = res.expand_as(x).reshape(-1, 128)
-            r2 = r2 if r2.is_contiguous() else r2.contiguous()
+        x2 = _c(x.reshape(-1, 128))
+        r2 = None if res is None else _c(res.expand_as(x).reshape(-1, 128))
         total = x2.shape[0]
         assert total % nets == 0
         y = torch.empty_like(x2)
         xhat = torch.empty_like(x2)
-        rstd = torch.empty((total,), dtype=torch.float32, device=x.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _check(L, L.sgrl_add_ln_forward(_p(x2), _p(r2), _p(w0), _p(b0), _p(w1), _p(b1), _p(y), _p(xhat), _p(rstd), total // nets, nets,
-                                        ctypes.c_float(eps), st), "sgrl_add_ln_forward")
+        rstd = _f32(x.device, total)
+        _call("sgrl_add_ln_forward", _p(x2), _p(r2), _p(w0), _p(b0), _p(w1), _p(b1), _p(y), _p(xhat), _p(rstd), total // nets, nets,
+              ctypes.c_float(eps), _st(x.device))
         ctx.save_for_backward(xhat, rstd, w0, w1)
         ctx.nets, ctx.x_shape, ctx.res_shape = nets, x.shape, None if res is None else res.shape
         return y.view(x.shape)
 
     @staticmethod
     def backward(ctx, dy):
-        L = _L()
         xhat, rstd, w0, w1 = ctx.saved_tensors
         total, nets = xhat.shape[0], ctx.nets
-        dy2 = dy.reshape(total, 128)
-        dy2 = dy2 if dy2.is_contiguous() else dy2.contiguous()
+        dy2 = _c(dy.reshape(total, 128))
         need = ctx.needs_input_grad
         dx = torch.empty_like(xhat)
-        new = lambda want: torch.empty((128,), dtype=torch.float32, device=dy.device) if want else None
+        new = lambda want: _f32(dy.device, 128) if want else None
         dw0, db0 = new(need[2]), new(need[3])
         dw1, db1 = new(nets == 2 and need[4]), new(nets == 2 and need[5])
-        st = ctypes.c_void_p(torch.cuda.current_stream(dy.device).cuda_stream)
-        _check(L, L.sgrl_add_ln_backward(_p(dy2), _p(xhat), _p(rstd), _p(w0), _p(w1), _p(dx), _p(dw0), _p(db0), _p(dw1), _p(db1),
-                                         total // nets, nets, st), "sgrl_add_ln_backward")
+        _call("sgrl_add_ln_backward", _p(dy2), _p(xhat), _p(rstd), _p(w0), _p(w1), _p(dx), _p(dw0), _p(db0), _p(dw1), _p(db1),
+              total // nets, nets, _st(dy.device))
         dxv = dx.view(ctx.x_shape)
         dres = None
         if ctx.res_shape is not None and need[1]:
@@ -655,27 +669,22 @@ class _Embed3Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, idx, w0, w1, w2):
-        L = _L()
         n = (w0.shape[1], w1.shape[1], w2.shape[1])
-        ws = [w if w.is_contiguous() else w.contiguous() for w in (w0, w1, w2)]
+        ws = [_c(w) for w in (w0, w1, w2)]
         Ln = idx.shape[1]
-        out = torch.empty((Ln, sum(n)), dtype=torch.float32, device=w0.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(w0.device).cuda_stream)
-        _check(L, L.sgrl_embed3_forward(_p(idx), _p(ws[0]), _p(ws[1]), _p(ws[2]), n[0], n[1], n[2], _p(out), Ln, st), "sgrl_embed3_forward")
+        out = _f32(w0.device, Ln, sum(n))
+        _call("sgrl_embed3_forward", _p(idx), _p(ws[0]), _p(ws[1]), _p(ws[2]), n[0], n[1], n[2], _p(out), Ln, _st(w0.device))
         ctx.save_for_backward(idx)
         ctx.n, ctx.rows = n, w0.shape[0]
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        L = _L()
         (idx,) = ctx.saved_tensors
-        d = dout if dout.is_contiguous() else dout.contiguous()
+        d = _c(dout)
         n, rows = ctx.n, ctx.rows
-        dws = [torch.empty((rows, n[t]), dtype=torch.float32, device=dout.device) if ctx.needs_input_grad[1 + t] else None for t in range(3)]
-        st = ctypes.c_void_p(torch.cuda.current_stream(dout.device).cuda_stream)
-        _check(L, L.sgrl_embed3_backward(_p(idx), _p(d), _p(dws[0]), _p(dws[1]), _p(dws[2]), n[0], n[1], n[2], idx.shape[1], rows, st),
-               "sgrl_embed3_backward")
+        dws = [_f32(dout.device, rows, n[t]) if ctx.needs_input_grad[1 + t] else None for t in range(3)]
+        _call("sgrl_embed3_backward", _p(idx), _p(d), _p(dws[0]), _p(dws[1]), _p(dws[2]), n[0], n[1], n[2], idx.shape[1], rows, _st(dout.device))
         return None, dws[0], dws[1], dws[2]
 
 
@@ -960,24 +969,17 @@ class _DropoutFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, p, seed, step, site):
-        L = _L()
-        x2 = x if x.is_contiguous() else x.contiguous()
+        x2 = _c(x)
         y = torch.empty_like(x2)
-        st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _check(L, L.sgrl_dropout_forward(_p(x2), _p(y), x2.numel(), ctypes.c_float(p), ctypes.c_uint64(seed), _p(step), site, st),
-               "sgrl_dropout_forward")
         ctx.call = (p, seed, step, site)
+        _call("sgrl_dropout_forward", _p(x2), _p(y), x2.numel(), *_drop_args(ctx.call), _st(x.device))
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        L = _L()
-        p, seed, step, site = ctx.call
-        dy2 = dy if dy.is_contiguous() else dy.contiguous()
+        dy2 = _c(dy)
         dx = torch.empty_like(dy2)
-        st = ctypes.c_void_p(torch.cuda.current_stream(dy.device).cuda_stream)
-        _check(L, L.sgrl_dropout_backward(_p(dy2), _p(dx), dy2.numel(), ctypes.c_float(p), ctypes.c_uint64(seed), _p(step), site, st),
-               "sgrl_dropout_backward")
+        _call("sgrl_dropout_backward", _p(dy2), _p(dx), dy2.numel(), *_drop_args(ctx.call), _st(dy.device))
         return dx, None, None, None, None
 
 
@@ -1004,33 +1006,11 @@ class _SwatAttnDropFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, bias, scale, p, seed, step, site):
-        L = _L()
-        B, Ln = qkv.shape[0], qkv.shape[1]
-        qkv = qkv if qkv.is_contiguous() else qkv.contiguous()
-        bz = None if bias is None else (bias if bias.is_contiguous() else bias.contiguous())
-        w = torch.empty((B, 2, Ln, Ln), dtype=torch.float32, device=qkv.device)
-        o = torch.empty((B, Ln, 128), dtype=torch.float32, device=qkv.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream)
-        _check(L, L.sgrl_swat_attention_forward_dropout(_p(qkv), _p(bz), ctypes.c_float(scale), _p(w), _p(o), B, Ln, ctypes.c_float(p),
-                                                        ctypes.c_uint64(seed), _p(step), site, st), "sgrl_swat_attention_forward_dropout")
-        ctx.save_for_backward(qkv, w)
-        ctx.has_bias, ctx.scale, ctx.call = bias is not None, float(scale), (p, seed, step, site)
-        return o
+        return _swat_attn_forward(ctx, "sgrl_swat_attention_forward_dropout", qkv, bias, scale, p, seed, step, site)
 
     @staticmethod
     def backward(ctx, d_o):
-        L = _L()
-        qkv, w = ctx.saved_tensors
-        p, seed, step, site = ctx.call
-        B, Ln = qkv.shape[0], qkv.shape[1]
-        d_o = d_o if d_o.is_contiguous() else d_o.contiguous()
-        dqkv, ds = torch.empty_like(qkv), torch.empty_like(w)
-        st = ctypes.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream)
-        _check(L, L.sgrl_swat_attention_backward_dropout(_p(qkv), ctypes.c_float(ctx.scale), _p(w), _p(d_o), _p(dqkv), _p(ds), B, Ln,
-                                                         ctypes.c_float(p), ctypes.c_uint64(seed), _p(step), site, st),
-               "sgrl_swat_attention_backward_dropout")
-        dbias = ds.sum(0) if (ctx.has_bias and ctx.needs_input_grad[1]) else None
-        return (dqkv if ctx.needs_input_grad[0] else None), dbias, None, None, None, None, None
+        return _swat_attn_backward(ctx, "sgrl_swat_attention_backward_dropout", d_o)
 
 
 SWAT_MAX_LIMBS = 15      # SGRL_SWAT_MAX_LIMBS (include/sgrl_swat.h): what k_swat_attn_* hold in registers
@@ -1138,20 +1118,16 @@ class _SmpGatherFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, own, src, tab, normalize, act_tanh, B):
-        L = _L()
-        ref = own if own is not None else src
+        dev = (own if own is not None else src).device
         n, S = tab.n, tab.S
         W0 = 0 if own is None else own.shape[-1]
-        own_c = None if own is None else (own if own.is_contiguous() else own.contiguous())
-        src_c = None if src is None else (src if src.is_contiguous() else src.contiguous())
+        own_c, src_c = _c(own), _c(src)
         n_src, Wsrc = (0, 0) if src is None else (src.shape[0], src.shape[-1])
         normalize = bool(normalize) and W0 > 0
-        out = torch.empty((n, B, W0 + SMP_MSG * S), dtype=torch.float32, device=ref.device)
-        inv = torch.empty((n, B), dtype=torch.float32, device=ref.device) if normalize else None
-        st = ctypes.c_void_p(torch.cuda.current_stream(ref.device).cuda_stream)
-        _check(L, L.sgrl_smp_gather_forward(_p(own_c), W0, 1 if normalize else 0, _p(src_c), n_src, Wsrc, ctypes.c_void_p(tab.node.ctypes.data),
-                                            ctypes.c_void_p(tab.off.ctypes.data), S, 1 if act_tanh else 0, _p(out), _p(inv), n, B, st),
-               "sgrl_smp_gather_forward")
+        out = _f32(dev, n, B, W0 + SMP_MSG * S)
+        inv = _f32(dev, n, B) if normalize else None
+        _call("sgrl_smp_gather_forward", _p(own_c), W0, 1 if normalize else 0, _p(src_c), n_src, Wsrc, ctypes.c_void_p(tab.node.ctypes.data),
+              ctypes.c_void_p(tab.off.ctypes.data), S, 1 if act_tanh else 0, _p(out), _p(inv), n, B, _st(dev))
         ctx.save_for_backward(own_c if normalize else None, inv, out if act_tanh else None)
         ctx.tab, ctx.normalize, ctx.act, ctx.B, ctx.W0 = tab, normalize, bool(act_tanh), B, W0
         ctx.own_shape = None if own is None else own.shape
@@ -1160,20 +1136,18 @@ class _SmpGatherFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_out):
-        L = _L()
         own, inv, out = ctx.saved_tensors
         tab, B, W0 = ctx.tab, ctx.B, ctx.W0
-        d = d_out if d_out.is_contiguous() else d_out.contiguous()
+        d = _c(d_out)
         need_own = ctx.own_shape is not None and ctx.needs_input_grad[0]
         need_src = ctx.src_shape is not None and ctx.needs_input_grad[1]
-        d_own = torch.empty((tab.n, B, W0), dtype=torch.float32, device=d.device) if need_own else None
-        d_src = torch.empty(tuple(ctx.src_shape), dtype=torch.float32, device=d.device) if need_src else None
+        d_own = _f32(d.device, tab.n, B, W0) if need_own else None
+        d_src = _f32(d.device, *ctx.src_shape) if need_src else None
         n_src, Wsrc = (0, 0) if ctx.src_shape is None else (ctx.src_shape[0], ctx.src_shape[-1])
-        st = ctypes.c_void_p(torch.cuda.current_stream(d.device).cuda_stream)
         if need_own or need_src:
-            _check(L, L.sgrl_smp_gather_backward(_p(d), _p(out), _p(own), _p(inv), W0, 1 if ctx.normalize else 0, n_src, Wsrc,
-                                                 ctypes.c_void_p(tab.node.ctypes.data), ctypes.c_void_p(tab.off.ctypes.data), tab.S,
-                                                 1 if ctx.act else 0, _p(d_own), _p(d_src), tab.n, B, st), "sgrl_smp_gather_backward")
+            _call("sgrl_smp_gather_backward", _p(d), _p(out), _p(own), _p(inv), W0, 1 if ctx.normalize else 0, n_src, Wsrc,
+                  ctypes.c_void_p(tab.node.ctypes.data), ctypes.c_void_p(tab.off.ctypes.data), tab.S, 1 if ctx.act else 0,
+                  _p(d_own), _p(d_src), tab.n, B, _st(d.device))
         return (None if d_own is None else d_own.view(ctx.own_shape)), d_src, None, None, None, None
 
 
@@ -1216,49 +1190,35 @@ class _SmpUpTailFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a, weight, bias):
-        L = _L()
-        a2 = a.reshape(-1, 64)
-        a2 = a2 if a2.is_contiguous() else a2.contiguous()
-        w = weight if weight.is_contiguous() else weight.contiguous()
+        a2 = _c(a.reshape(-1, 64))
+        w = _c(weight)
         R = a2.shape[0]
-        t = torch.empty((R, 64), dtype=torch.float32, device=a.device)
-        u = torch.empty((R, 32), dtype=torch.float32, device=a.device)
-        inv = torch.empty((R,), dtype=torch.float32, device=a.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
-        _check(L, L.sgrl_smp_up_tail_forward(_p(a2), _p(w), _p(bias), _p(t), _p(u), _p(inv), R, st), "sgrl_smp_up_tail_forward")
+        dev = a.device
+        t = _f32(dev, R, 64)
+        u = _f32(dev, R, 32)
+        inv = _f32(dev, R)
+        _call("sgrl_smp_up_tail_forward", _p(a2), _p(w), _p(bias), _p(t), _p(u), _p(inv), R, _st(dev))
         ctx.save_for_backward(t, u, inv, w)
-        ctx.leaf = (weight, bias) if (weight.is_leaf and bias.is_leaf) else None
+        ctx.targets = _leaf_targets(weight, bias) if weight.is_leaf else None       # fc3 is never a folded weight
         ctx.a_shape = a.shape
         return u.view(*a.shape[:-1], 32)
 
     @staticmethod
     def backward(ctx, du):
-        L = _L()
         t, u, inv, w = ctx.saved_tensors
         R = t.shape[0]
-        d = du.reshape(R, 32)
-        d = d if d.is_contiguous() else d.contiguous()
+        d = _c(du.reshape(R, 32))
         dev = d.device
-        dz = torch.empty((R, 32), dtype=torch.float32, device=dev)
-        da = torch.empty((R, 64), dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(L, L.sgrl_smp_up_tail_backward(_p(d), _p(u), _p(inv), _p(t), _p(w), _p(dz), _p(da), R, ctypes.c_void_p(stream)),
-               "sgrl_smp_up_tail_backward")
+        dz = _f32(dev, R, 32)
+        da = _f32(dev, R, 64)
+        st = _st(dev)
+        _call("sgrl_smp_up_tail_backward", _p(d), _p(u), _p(inv), _p(t), _p(w), _p(dz), _p(da), R, st)
         need_w, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        dw = db = None
-        deferred = False
+        gw = gb = None
         if need_w or need_b:
-            dw = torch.empty((32, 64), dtype=torch.float32, device=dev)
-            db = torch.empty((32,), dtype=torch.float32, device=dev) if need_b else None
-            deferred = _pending is not None and ctx.leaf is not None
-            rec = {"dy": dz, "y": None, "rowdiv": None, "x": t, "dw": dw, "db": db, "M": R, "N": 32, "K": 64, "relu": False, "dev": dev,
-                   "stream": stream, "ldy": 32, "w_param": (ctx.leaf[0] if need_w else None) if deferred else None, "fold_param": None,
-                   "b_param": (ctx.leaf[1] if need_b else None) if deferred else None}
-            if deferred:
-                _pending.append(rec)
-            else:
-                flush_wgrads([rec])
-        return (da.view(ctx.a_shape) if ctx.needs_input_grad[0] else None), (None if deferred or not need_w else dw), (None if deferred else db)
+            ((gw, gb),), now = _settle([_Wgrad(dz, None, None, t, 32, False, ctx.targets, need_w, need_b, st)])
+            flush_wgrads(now)
+        return (da.view(ctx.a_shape) if ctx.needs_input_grad[0] else None), gw, gb
 
 
 def smp_up_tail(a, weight, bias):
@@ -1275,41 +1235,24 @@ class _NormalizeRowsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x):
-        L = _L()
         W = x.shape[-1]
-        x2 = x.reshape(-1, W)
-        x2 = x2 if x2.is_contiguous() else x2.contiguous()
+        x2 = _c(x.reshape(-1, W))
         R = x2.shape[0]
-        y = torch.empty((R, W), dtype=torch.float32, device=x.device)
-        inv = torch.empty((R,), dtype=torch.float32, device=x.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _check(L, L.sgrl_row_normalize_forward(_p(x2), _p(y), _p(inv), R, W, st), "sgrl_row_normalize_forward")
+        y = _f32(x.device, R, W)
+        inv = _f32(x.device, R)
+        _call("sgrl_row_normalize_forward", _p(x2), _p(y), _p(inv), R, W, _st(x.device))
         ctx.save_for_backward(y, inv)
         ctx.x_shape = x.shape
         return y.view(x.shape)
 
     @staticmethod
     def backward(ctx, dy):
-        L = _L()
         y, inv = ctx.saved_tensors
         R, W = y.shape
-        d = dy.reshape(R, W)
-        d = d if d.is_contiguous() else d.contiguous()
+        d = _c(dy.reshape(R, W))
         dx = torch.empty_like(y)
-        st = ctypes.c_void_p(torch.cuda.current_stream(d.device).cuda_stream)
-        _check(L, L.sgrl_row_normalize_backward(_p(d), _p(y), _p(inv), _p(dx), R, W, st), "sgrl_row_normalize_backward")
+        _call("sgrl_row_normalize_backward", _p(d), _p(y), _p(inv), _p(dx), R, W, _st(d.device))
         return dx.view(ctx.x_shape)
-
-
-def _bind_losses(L):
-    if not getattr(L, "_sgrl_td3_loss_bound", False):
-        vp, i64 = ctypes.c_void_p, ctypes.c_int64
-        L.sgrl_td3_twin_mse_forward.argtypes = [vp, vp, vp, i64, vp, vp]
-        L.sgrl_td3_twin_mse_backward.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
-        L.sgrl_td3_neg_mean_forward.argtypes = [vp, i64, vp, vp]
-        L.sgrl_td3_neg_mean_backward.argtypes = [i64, vp, vp, vp]
-        L._sgrl_td3_loss_bound = True
-    return L
 
 
 def _upstream(g):
@@ -1323,23 +1266,18 @@ class _TwinMseFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q1, q2, target):
-        L = _bind_losses(_L())
-        loss = torch.empty((), dtype=torch.float32, device=q1.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(q1.device).cuda_stream)
-        _check(L, L.sgrl_td3_twin_mse_forward(_p(q1), _p(q2), _p(target), q1.numel(), _p(loss), st), "sgrl_td3_twin_mse_forward")
+        loss = _f32(q1.device)
+        _call("sgrl_td3_twin_mse_forward", _p(q1), _p(q2), _p(target), q1.numel(), _p(loss), _st(q1.device))
         ctx.save_for_backward(q1, q2, target)
         return loss
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        L = _bind_losses(_L())
         q1, q2, target = ctx.saved_tensors
         g = _upstream(g)
         dq1, dq2 = torch.empty_like(q1), torch.empty_like(q2)
-        st = ctypes.c_void_p(torch.cuda.current_stream(q1.device).cuda_stream)
-        _check(L, L.sgrl_td3_twin_mse_backward(_p(q1), _p(q2), _p(target), q1.numel(), _p(g), _p(dq1), _p(dq2), st),
-               "sgrl_td3_twin_mse_backward")
+        _call("sgrl_td3_twin_mse_backward", _p(q1), _p(q2), _p(target), q1.numel(), _p(g), _p(dq1), _p(dq2), _st(q1.device))
         return (dq1 if ctx.needs_input_grad[0] else None), (dq2 if ctx.needs_input_grad[1] else None), None
 
 
@@ -1348,21 +1286,17 @@ class _NegMeanFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q):
-        L = _bind_losses(_L())
-        loss = torch.empty((), dtype=torch.float32, device=q.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
-        _check(L, L.sgrl_td3_neg_mean_forward(_p(q), q.numel(), _p(loss), st), "sgrl_td3_neg_mean_forward")
+        loss = _f32(q.device)
+        _call("sgrl_td3_neg_mean_forward", _p(q), q.numel(), _p(loss), _st(q.device))
         ctx.q_shape = q.shape
         return loss
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        L = _bind_losses(_L())
         g = _upstream(g)
-        dq = torch.empty(ctx.q_shape, dtype=torch.float32, device=g.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(g.device).cuda_stream)
-        _check(L, L.sgrl_td3_neg_mean_backward(dq.numel(), _p(g), _p(dq), st), "sgrl_td3_neg_mean_backward")
+        dq = _f32(g.device, *ctx.q_shape)
+        _call("sgrl_td3_neg_mean_backward", dq.numel(), _p(g), _p(dq), _st(g.device))
         return dq
 
 

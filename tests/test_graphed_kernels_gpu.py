@@ -45,7 +45,7 @@ def _guarded(n):
 def test_loss_kernels_match_the_restatement(n, g):
     import torch
     from sgrl_amd import train_ops
-    L = train_ops._bind_losses(train_ops._L())
+    L = train_ops._L()
     rs = np.random.RandomState(n)
     q1, q2, t = [(0.6 * rs.standard_normal(n)).astype(np.float32) for _ in range(3)]
     dq1, dq2, dq, gt = (torch.from_numpy(x).cuda() for x in (q1, q2, t, np.asarray([g], dtype=np.float32)))

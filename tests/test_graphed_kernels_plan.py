@@ -78,7 +78,7 @@ def test_cpu_tensors_take_the_pytorch_expressions_to_the_bit(dtype):
 
 # ---- the C ABI --------------------------------------------------------------------------------------------------------------
 def test_argument_errors_and_launch_count_need_no_device():
-    L = train_ops._bind_losses(train_ops._L())
+    L = train_ops._L()
     assert L.sgrl_td3_loss_launches() == 1
     ERR_ARG = -1
     buf = np.zeros((6, 64), dtype=np.float32)

@@ -690,3 +690,74 @@ def test_fan_out_sums_the_consumers_input_gradients_in_one_buffer(twin):
         assert torch.equal(a, b)                              # the weight gradients do not know about the fan-out
     g1b, _ = run(True)
     assert torch.equal(g1, g1b)                               # same order of accumulation every time: bit-reproducible
+
+
+# ---- which inputs need a gradient: the branches of linear's and linear2's backward() bookkeeping ---------------------------------
+NEED_SHAPES = [(13, 126, 30), (65, 256, 1)]          # (M, K, N): ragged, below one 64-row tile and across it
+NEED_CASES = [("linear", need) for need in (("x",), ("w",), ("b",), ("rd",), ("x", "rd"), ("x", "w", "b", "rd"))] + \
+             [(kind, need) for kind in ("twin_stacked", "twin_shared") for need in (("x",), ("w0",), ("b1",), ("x", "w0", "w1", "b0", "b1"))] + \
+             [("twin_rowdiv", ("rd",))]      # stacked, no bias, no ReLU: the row divisor's gradient alone, sgrl_linear_backward per network
+_need_refs = {}
+
+
+def _need_reference(kind, M, K, N):
+    """Inputs (float32, CPU) and the float64 PyTorch gradient of EVERY input, computed once per (form, shape) and left unchanged."""
+    key = (kind, M, K, N)
+    if key not in _need_refs:
+        g = torch.Generator().manual_seed(len(kind) + 3 * M + 5 * K + 7 * N)
+        twin = kind != "linear"
+        t = {"x": torch.randn((M, K) if kind in ("linear", "twin_shared") else (2, M, K), generator=g)}
+        for n in (("w0", "w1") if twin else ("w",)):
+            t[n] = torch.randn(N, K, generator=g) / np.sqrt(K)
+        if kind != "twin_rowdiv":
+            for n in (("b0", "b1") if twin else ("b",)):
+                t[n] = torch.randn(N, generator=g)
+        if kind in ("linear", "twin_rowdiv"):
+            t["rd"] = torch.rand((2, M, 1) if twin else (M, 1), generator=g) + 0.5
+        dy = torch.randn((2, M, N) if twin else (M, N), generator=g)
+        r = {n: v.double().requires_grad_() for n, v in t.items()}
+        if twin:
+            ys = [torch.nn.functional.linear(r["x"] if kind == "twin_shared" else r["x"][i], r["w%d" % i], r.get("b%d" % i)) for i in range(2)]
+            yr = torch.stack(ys)
+        else:
+            yr = torch.nn.functional.linear(r["x"], r["w"], r["b"])
+        yr = yr / r["rd"] if "rd" in r else yr
+        yr.backward(dy.double())
+        _need_refs[key] = (t, dy, {n: v.grad for n, v in r.items()})
+    return _need_refs[key]
+
+
+def _need_run(kind, tensors, dy, need, deferred):
+    from sgrl_amd import train_ops
+    d = {n: v.cuda().requires_grad_(n in need) for n, v in tensors.items()}
+    with train_ops.deferred_wgrads(deferred):
+        if kind == "linear":
+            y = train_ops.linear(d["x"], d["w"], d["b"], rowdiv=d["rd"])
+            assert type(y.grad_fn).__name__.startswith("_LinearFn")
+        else:
+            y = train_ops.linear2(d["x"], d["w0"], d["w1"], d.get("b0"), d.get("b1"), rowdiv=d.get("rd"), shared=kind == "twin_shared")
+            assert type(y.grad_fn).__name__.startswith("_Linear2Fn")
+        y.backward(dy.cuda())
+    return {n: v.grad for n, v in d.items()}
+
+
+@pytest.mark.parametrize("M,K,N", NEED_SHAPES)
+@pytest.mark.parametrize("kind,need", NEED_CASES, ids=["%s-%s" % (k, "+".join(n)) for k, n in NEED_CASES])
+def test_need_grad_matrix(kind, need, M, K, N):
+    """linear / linear2 with only SOME inputs requiring a gradient, backward run immediately and inside deferred_wgrads(): every
+    requested gradient against float64 PyTorch (the bar of test_linear2_matches_float64), every other one None, and the postponed
+    weight / bias gradients equal to the immediate ones bit for bit (at these sizes neither launch splits its contraction)."""
+    tensors, dy, ref = _need_reference(kind, M, K, N)
+    now = _need_run(kind, tensors, dy, need, False)
+    later = _need_run(kind, tensors, dy, need, True)
+    for n in tensors:
+        if n not in need:
+            assert now[n] is None and later[n] is None, n
+            continue
+        assert now[n] is not None and later[n] is not None, n
+        assert now[n].shape == ref[n].shape, n
+        tol = 3e-6 * (float(ref[n].abs().max()) + 1.0) * (np.sqrt(M / 64 + 1) if n[0] in "wb" else 1.0)
+        err = float((now[n].cpu().double() - ref[n]).abs().max())
+        print("need-grad %s %s (%d, %d, %d) %s: err %.3g bar %.3g" % (kind, "+".join(need), M, K, N, n, err, tol))
+        assert err < tol, n
+        assert torch.equal(later[n], now[n]), n
