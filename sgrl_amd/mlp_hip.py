@@ -669,6 +669,31 @@ class HipMlpOptim(object):
                 if c is not None:
                     side.opt.state[p]["step"].fill_(c)
 
+    def resync(self):
+        """Somebody wrote the optimizers' step counts by value (td3.restore_optimizer: a checkpoint load): bring this object's
+        mirrors back in line, so that counts_current() holds again and a captured step keeps running on the restored count.
+        Plain groups: the device counter this object owns is filled with the state's CPU count, IN PLACE (recorded steps hold its
+        address), and `host_step` follows.  Capturable groups: the host mirror `_sgrl_step_class` is read again from the device
+        counters (one synchronisation per parameter, here and never in a step).  A side whose state is gone or whose parameters
+        disagree forgets its count: its next step fills the counter, as after a bind."""
+        for side in (self._critic, self._actor):
+            params = side.h._params()
+            states = [side.opt.state.get(p) for p in params]
+            if any(not st for st in states):
+                side.host_step = None
+                continue
+            if states[0]["step"].is_cuda:
+                host = side.opt.__dict__.setdefault("_sgrl_step_class", {})
+                for p, st in zip(params, states):
+                    host[id(p)] = int(st["step"].item())
+                continue
+            counts = [float(st["step"]) for st in states]
+            if side.counter is None or any(c != counts[0] for c in counts):
+                side.host_step = None
+                continue
+            side.counter.fill_(counts[0])
+            side.host_step = counts[0]
+
     def _state(self, side, params):
         """opt.state[p] of every parameter, created where empty; -> (states, True when the counters live on the device)."""
         opt = side.opt

@@ -463,6 +463,26 @@ class TransitionSink(object):
         self._stored += int(sum(counts))
         self._pos_host = tuple(b._curr for b in self.buffers)
 
+    def rings_loaded(self):
+        """The rings' host-side pointers were just assigned (checkpoint.load_checkpoint; the `curr` setter has folded what the
+        ingest still held into the pointer it replaced): the device-side write pointers take the new values IN PLACE and nothing
+        stays pending, so the next one-launch ingest writes where the restored `curr` says.  A sink whose device ingest has not run
+        yet uploads the pointers with its first block anyway."""
+        if not self.is_learner or self.buffers is None:
+            return
+        self.fold_counters()
+        if getattr(self, "_pos_dev", None) is not None:
+            pos = tuple(int(b._curr) for b in self.buffers)
+            self._pos_dev.copy_(torch.tensor(pos, dtype=torch.long))
+            self._pos_host = pos
+
+    def device_pointers(self):
+        """(device-side write pointers as a list -- None before the first one-launch ingest --, rows still pending on the device).
+        Synchronises; for checkpoints and tests."""
+        pos = getattr(self, "_pos_dev", None)
+        return (None if pos is None else [int(v) for v in pos.tolist()],
+                0 if self._pend is None else int(sum(self._pend.tolist())))
+
     @property
     def stored(self):
         """Transitions written on the learner so far (tot_env_steps bookkeeping, trainer.py:229); reading it synchronises."""

@@ -253,6 +253,83 @@ def adam_step(opt):
                 torch._foreach_addcdiv_([p.data for p in members], exp_avgs, denom)
 
 
+_GROUP_KEYS = ("lr", "betas", "eps", "weight_decay")
+
+
+def optimizer_state(opt):
+    """What checkpoint.save_checkpoint keeps of a torch.optim.Adam with ONE group: the group's hyper-parameters and, per parameter
+    in the group's order (= `parameters()` order), None where it has no state yet or its `step` as a VALUE (a float, wherever the
+    counter lives) with CPU copies of the moment tensors.  Plain values and tensors only (torch.load(weights_only=True))."""
+    if len(opt.param_groups) != 1:
+        raise ValueError("optimizer_state serves optimizers with one parameter group (got %d)" % len(opt.param_groups))
+    g = opt.param_groups[0]
+    if isinstance(g["lr"], torch.Tensor):
+        raise ValueError("optimizer_state does not serve a tensor learning rate")
+    group = {"lr": float(g["lr"]), "betas": [float(b) for b in g["betas"]], "eps": float(g["eps"]),
+             "weight_decay": float(g.get("weight_decay", 0))}
+    states = []
+    for p in g["params"]:
+        st = opt.state.get(p)
+        if not st:
+            states.append(None)
+            continue
+        states.append({k: (float(v) if k == "step" else v.detach().cpu().clone()) for k, v in st.items()})
+    return {"group": group, "state": states}
+
+
+def restore_optimizer(opt, saved):
+    """`optimizer_state(...)`'s record back into `opt`, IN PLACE: no tensor that exists before the call changes its data_ptr(), so
+    the address tables of clip_and_step, the binds of mlp_hip.HipMlpOptim and captured hipGraphs stay valid.
+      state on both sides   copy_ / fill_ into the optimizer's own tensors (device and dtype stay as the optimizer has them; a step
+                            count is a value, whether it lives in a 0-dim CPU tensor or on the device)
+      only in `saved`       created in the form the group asks for: a capturable (or fused) group gets a device step tensor, as
+                            clip_and_step creates it, a plain group the 0-dim CPU tensor torch.optim.Adam creates
+      only in `opt`         deleted: the saved run had not stepped this parameter yet
+    Then every host mirror of a step count is dropped (`_sgrl_step_class`; a mirror left behind would give Adam a wrong bias
+    correction without any error): a plain group keeps none, a group with device counters gets a new one holding the restored
+    counts.  A live mlp_hip.HipMlpOptim keeps mirrors of its own: call its resync() afterwards (Agent.load_resume_state does).
+    Returns True when state was DELETED: the tensors a captured GraphedUpdates graph steps are then gone
+    (GraphedUpdates.forget_graphs)."""
+    if len(opt.param_groups) != 1:
+        raise ValueError("restore_optimizer serves optimizers with one parameter group (got %d)" % len(opt.param_groups))
+    g = opt.param_groups[0]
+    params = g["params"]
+    if len(saved["state"]) != len(params):
+        raise ValueError("restore_optimizer: the record holds %d parameters, the optimizer %d" % (len(saved["state"]), len(params)))
+    for p, s in zip(params, saved["state"]):
+        for k, v in (s or {}).items():
+            if k != "step" and tuple(v.shape) != tuple(p.shape):
+                raise ValueError("restore_optimizer: %s of shape %s for a parameter of shape %s" % (k, tuple(v.shape), tuple(p.shape)))
+    for k in _GROUP_KEYS:
+        if k in saved["group"]:
+            g[k] = tuple(saved["group"][k]) if k == "betas" else saved["group"][k]
+    on_device = bool(g.get("capturable", False) or g.get("fused", False))
+    deleted = False
+    with torch.no_grad():
+        for p, s in zip(params, saved["state"]):
+            if s is None:
+                if opt.state.get(p):
+                    del opt.state[p]
+                    deleted = True
+                continue
+            st = opt.state[p]
+            for k, v in s.items():
+                if k == "step":
+                    if not torch.is_tensor(st.get(k)):
+                        st[k] = torch.zeros((), dtype=torch.float32, device=p.device) if on_device else torch.tensor(0.0, dtype=torch.float32)
+                    st[k].fill_(float(v))
+                else:
+                    if not torch.is_tensor(st.get(k)):
+                        st[k] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st[k].copy_(v)
+    opt.__dict__.pop("_sgrl_step_class", None)
+    if on_device:
+        # device counters: the mirror is made again from the counts just written, here, where nothing is being captured -- left
+        # absent, the next clip_and_step would read every counter back with .item(), which a stream capture does not permit
+        opt.__dict__["_sgrl_step_class"] = {id(p): int(s["step"]) for p, s in zip(params, saved["state"]) if s is not None}
+    return deleted
+
+
 def default_train_args(**over):
     """The reference's TD3 / SET hyper-parameters (reference arguments.py:55-160, configs/default.py:9-12).
 
@@ -404,7 +481,8 @@ class Agent(nn.Module):
         # dropout_rate: read by the swat networks only (the reference forces the SET networks to 0, SEActor.py:185; smp and mlp have
         # none).  With a rate > 0 every update() runs inside a train_ops.dropout_rng context: seed = args.seed (0 when absent), step =
         # a one-element int64 tensor on the batch's device, created by the first update and incremented once at the top of each one,
-        # on the update's stream.  A plain attribute: no parameter, no buffer, not in state_dict()
+        # on the update's stream.  A plain attribute: no parameter, no buffer, not in state_dict() -- a reference-format snapshot does
+        # not hold it, a checkpoint (checkpoint.py, resume_state / load_resume_state) carries its value
         self.dropout_rate = float(getattr(args, "dropout_rate", 0.0) or 0.0) if "swat" in (atype, ctype) else 0.0
         self.dropout_seed = int(getattr(args, "seed", 0) or 0)
         self._dropout_step = None
@@ -546,7 +624,8 @@ class Agent(nn.Module):
 
     def _dropout_rng(self, device):
         """The train_ops.dropout_rng context of one update: the step counter moves first (one launch on the current stream), every
-        dropout call of the update's three parts then numbers itself from site 0."""
+        dropout call of the update's three parts then numbers itself from site 0.  The counter's value is part of a checkpoint
+        (resume_state; load_resume_state writes it back into this tensor), not of a reference-format snapshot."""
         step = self._dropout_step
         if step is None or step.device != device:
             step = self._dropout_step = torch.zeros(1, dtype=torch.int64, device=device)
@@ -690,6 +769,32 @@ class Agent(nn.Module):
     def models2train(self):
         for m in (self.actor, self.actor_target, self.critic, self.critic_target):
             m.train()
+
+    # ---- what a checkpoint keeps of the agent besides state_dict() (checkpoint.py) -----------------------------------
+    def resume_state(self):
+        """Plain values and tensors only: `tot_update_count`, the VALUE of the dropout step (None while no update has created the
+        tensor; reading it synchronises) and both optimizers (optimizer_state)."""
+        step = self._dropout_step
+        return {"tot_update_count": int(self.tot_update_count), "dropout_step": None if step is None else int(step.item()),
+                "actor_optimizer": optimizer_state(self.actor_optimizer), "critic_optimizer": optimizer_state(self.critic_optimizer)}
+
+    def load_resume_state(self, d):
+        """`resume_state()` back, in place.  The dropout step is written INTO the existing tensor -- captured graphs hold its address
+        and record its increment -- or, where no update has made one yet, into a new one on the agent's device; a record without a
+        step zeroes an existing tensor (the first update's increment then makes it 1, as in a fresh agent).  The optimizers go
+        through restore_optimizer; a live mlp_hip.HipMlpOptim is then brought back in line with the restored counts (resync).
+        Returns True when optimizer state was deleted (see restore_optimizer)."""
+        self.tot_update_count = int(d["tot_update_count"])
+        step = d["dropout_step"]
+        if self._dropout_step is not None:
+            self._dropout_step.fill_(0 if step is None else int(step))
+        elif step is not None:
+            self._dropout_step = torch.full((1,), int(step), dtype=torch.int64, device=self.device)
+        deleted = restore_optimizer(self.actor_optimizer, d["actor_optimizer"])
+        deleted = restore_optimizer(self.critic_optimizer, d["critic_optimizer"]) or deleted
+        if self._mlp_optim is not None:
+            self._mlp_optim.resync()
+        return deleted
 
 
 def _concurrent_stream(cur, tries=8):
@@ -958,6 +1063,17 @@ class GraphedUpdates(_GraphedSurface):
         if sl is None or flag not in sl["graphs"]:
             return False
         return sl["stamp"].get(flag) != self._stamp(sl)
+
+    def forget_graphs(self):
+        """Drop every captured graph and every warm-up: Adam state tensors the graphs step have been freed (restore_optimizer
+        deleted them -- a checkpoint from before the first update loaded into an agent that has stepped; the stamp does not
+        carry their addresses).  The next round warms every morphology again, eagerly, before anything is captured."""
+        for key, sl in self.slots.items():
+            for flag in list(sl["graphs"]):
+                del sl["graphs"][flag]
+                release_tables((id(self), key, flag))
+            sl["stamp"].clear()
+        self.warmed.clear()
 
     def _check_capture(self, sl, key):
         """What must hold on the host before torch.cuda.graph(...) is entered for a graph on this slot."""

@@ -36,14 +36,15 @@ class DeviceTrainer(object):
         device_sampler (learner): every update of update_after_round takes its batch and its target-policy noise from ONE library call
         (replay.DeviceReplayBuffer.sample_into, include/sgrl_replay.h) with seed = `seed` and draw = a counter incremented once per
         update, instead of sample(generator=self.gen) and normal_().  Off by default: it changes which rows a seeded run samples,
-        and the learning curves have not been re-run on the new stream.  The draw counter is NOT part of a
-        snapshot: assigning tot_env_steps (how a resumed run restores its count) restarts it at draw = tot_env_steps.
+        and the learning curves have not been re-run on the new stream.  A reference-format snapshot
+        (snapshot.py) has no field for the draw counter: assigning tot_env_steps (how a run resumed from one restores its count)
+        restarts it at draw = tot_env_steps.  A checkpoint (save_checkpoint / load_checkpoint) carries the counter itself.
         device_noise (the training rollout only; evaluation never adds noise): the exploration noise and the warm-up actions of
         collect_step come from ONE library call each (Rollout.explore_into / random_actions, include/sgrl_explore.h) as a function of
         (`seed`, the rollout's noise_step, global environment number, slot), instead of torch.randn / uniform_ on the rollout's
         generator.  Off by default for the same reason: it changes what a seeded run explores, and the learning curves have not
-        been re-run on it.  noise_step is NOT part of a snapshot either and follows the same rule as the draw counter: assigning
-        tot_env_steps sets the rollout's noise_step to the restored value."""
+        been re-run on it.  noise_step follows the same rule as the draw counter: a snapshot has no field for it and assigning
+        tot_env_steps sets the rollout's noise_step to the restored value; a checkpoint carries it."""
         import torch.distributed as dist
         self.dist = dist
         self.rank = dist.get_rank() if dist.is_initialized() else 0
@@ -115,6 +116,7 @@ class DeviceTrainer(object):
             self.graphed = GraphedMlpUpdates(self.agent, self.batch_size) if mlp else \
                 GraphedUpdates(self.agent, self.batch_size, hip_kernels=bool(graph_hip_kernels))
             self._graphed_lazy = mlp
+        self._steps_in_round = 0     # collect_step calls since the last begin_round (a checkpoint is taken at 0 only)
         self.begin_round()
 
     @property
@@ -129,13 +131,14 @@ class DeviceTrainer(object):
     @tot_env_steps.setter
     def tot_env_steps(self, v):
         """Resume from a snapshot (snapshot.load_snapshot returns the count, reference common/trainer.py:296-322): the restored
-        value becomes the base the live counters are added to."""
+        value becomes the base the live counters are added to.  The two counter-RNG positions a snapshot has no field for restart
+        at the restored value; load_checkpoint, whose files carry them, assigns the saved positions after this rule."""
         if self.is_learner:
             self._tot_base = int(v) - (self.sink.stored + self._updates)
         self._tot_synced = int(v)
-        self.draw = int(v)           # the draw counter is not in a snapshot: a resumed run starts at draw = tot_env_steps
+        self.draw = int(v)           # a snapshot has no draw counter: a run resumed from one starts at draw = tot_env_steps
         if hasattr(self.ro, "noise_step"):
-            self.ro.noise_step = int(v)      # ... and neither is the exploration's step number: same rule
+            self.ro.noise_step = int(v)      # ... and no exploration step number: same rule
 
     def sync_step_count(self):
         """Every rank learns the learner's count (called at the round ends and after the warm-up: rank-local logic that reads the
@@ -150,10 +153,12 @@ class DeviceTrainer(object):
         """`obs_list = envs.reset()` + fresh done / timestep lists (trainer.py:155-160, 268-275)."""
         self.ro.reset()
         self.sink.begin_round()
+        self._steps_in_round = 0
 
     def collect_step(self, random_actions=False):
         """One time step of every environment + replay push.  Returns True when the collection round is complete."""
         env = self.ro.env
+        self._steps_in_round += 1
         self.prev_obs.copy_(env.obs)
         if random_actions:                       # Trainer.warmup: uniform actions (trainer.py:95-102)
             a = self.ro.random_actions()
@@ -316,3 +321,19 @@ class DeviceTrainer(object):
         self.begin_round()
         return {"steps": steps, "per_morph_iter": iters, "performance/train_return": returns,
                 "performance/train_length": lengths, "tot_env_steps": self.tot_env_steps}
+
+    # ---- checkpoints -----------------------------------------------------------------------------------
+    def save_checkpoint(self, ckpt_dir, replay="reference"):
+        """Everything that decides what this run does next, written at a ROUND BOUNDARY (after train_round() has returned, after a
+        warmup() that ended with a round, straight after construction; RuntimeError otherwise): checkpoint.save_checkpoint has
+        the file list and the contract.  Every rank calls it.  Returns the list of paths this rank wrote."""
+        from . import checkpoint
+        return checkpoint.save_checkpoint(self, ckpt_dir, replay=replay)
+
+    def load_checkpoint(self, ckpt_dir):
+        """Restore a checkpoint IN PLACE into this trainer (built with the constructor arguments of the one that saved it; any
+        mismatch is a ValueError before anything is written): no parameter, Adam or ring tensor moves, captured update graphs stay
+        valid.  A trainer that goes on from here computes bit for bit what the saved one went on to compute
+        (checkpoint.load_checkpoint).  Every rank calls it.  Returns tot_env_steps."""
+        from . import checkpoint
+        return checkpoint.load_checkpoint(self, ckpt_dir)
