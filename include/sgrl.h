@@ -134,6 +134,16 @@ int64_t sgrl_ingest_ws_words(int n_rows);
 int sgrl_ingest_block(const float* block, int n_rows, int obs_len, int act_len, const sgrl_ring* rings, int n_rings, int64_t* pos,
                       const int64_t* cap, int64_t* pending, int64_t* slot_ws, void* stream);
 
+/* Test hook: the step kernel's register solver for one right-hand side (the wave policies' chol_solve_packed, csrc/wave_hip.h and
+ * csrc/wave_half.h) in ONE 64-lane workgroup on LDS operands.  All pointers HOST.  `flags` bit 0: the half-wave policy, two problems
+ * at once (lanes 0..31 / 32..63, each half its own n, matrix and right-hand side), else one problem on the full-wave policy; bit 1:
+ * the explicit-inverse path instead (chol_inv_packed, then x = T'(T rhs) as the step kernel ran it), for comparisons.  Problem p
+ * (0, or 0 and 1) has n[p] rows (0 <= n[p] <= 26), the packed lower triangle of its SPD matrix at C + p * SGRL_DEBUG_CHOL_LD and its
+ * right-hand side at rhs + p * 32; the matrix as the call leaves it comes back in C_out, the solution in x_out (same strides; every
+ * array holds both problems' slots, 2 * SGRL_DEBUG_CHOL_LD / 64 / 2 entries, whatever the flags), and ok[p] = 1 if the policy has a register instance for n[p] (0: it returned false; C_out / x_out then show the inputs untouched). */
+#define SGRL_DEBUG_CHOL_LD 352
+int sgrl_debug_chol_solve(int flags, const int32_t* n, const double* C, const double* rhs, double* C_out, double* x_out, int32_t* ok);
+
 const char* sgrl_last_error(void);
 const char* sgrl_version(void);
 

@@ -67,6 +67,51 @@ __global__ __launch_bounds__(64) void k_env_refresh(BatchArgs a, StepOut out) {
   sgrl::env_refresh(w, m, o, S, I, io);
 }
 
+// ---- test hook (sgrl_debug_chol_solve): the register solver for one right-hand side on either wave policy, one workgroup --------
+template <class Wv>
+__device__ __forceinline__ void debug_chol_solve(Wv& w, int n, double* C, double* x, double* wv, bool inverse, int32_t* ok) {
+  bool done;
+  if (!inverse) {
+    done = w.chol_solve_packed(n, C, x, sgrl::kMinVal);
+  } else {                     // the explicit-inverse path as lcp_block_pivot ran it: x = T'(T rhs), two lane-per-entry products
+    done = w.chol_inv_packed(n, C, sgrl::kMinVal);
+    if (done) {
+      w.lanes(n, [&](int i) {
+        double z = 0;
+        for (int c = 0; c <= i; c++) z += C[i * (i + 1) / 2 + c] * x[c];
+        wv[i] = z;
+      });
+      w.lanes(n, [&](int k) {
+        double s = 0;
+        for (int i = k; i < n; i++) s += C[i * (i + 1) / 2 + k] * wv[i];
+        x[k] = s;
+      });
+    }
+  }
+  if (w.lane == 0) *ok = done ? 1 : 0;
+}
+__global__ __launch_bounds__(64) void k_debug_chol_solve(int flags, const int32_t* n, const double* C, const double* rhs, double* C_out,
+                                                         double* x_out, int32_t* ok) {
+  constexpr int LD = SGRL_DEBUG_CHOL_LD;
+  __shared__ double sC[2 * LD], sx[64], swv[64];
+  const int t = threadIdx.x;
+  for (int i = t; i < 2 * LD; i += 64) sC[i] = C[i];
+  sx[t] = rhs[t];
+  swv[t] = 0.0;
+  __syncthreads();
+  if (flags & 1) {
+    sgrl::HalfWaveT<15, sgrl::HipHalfPrim<sgrl::DimsAny>> w;
+    const int h = w.half;
+    debug_chol_solve(w, n[h], sC + h * LD, sx + h * 32, swv + h * 32, (flags & 2) != 0, ok + h);
+  } else {
+    sgrl::HipWave w;
+    debug_chol_solve(w, n[0], sC, sx, swv, (flags & 2) != 0, ok);
+  }
+  __syncthreads();
+  for (int i = t; i < 2 * LD; i += 64) C_out[i] = sC[i];
+  x_out[t] = sx[t];
+}
+
 // ---- fixed-dimension kernels of the step (step_spec.hip; table generated by sgrl_amd/_lib.py build()) ------------------------
 typedef int (*SpecLaunch)(int, int, void*, const void*, const void*);
 struct SpecFamily { int waves; int n; SpecLaunch launch; int itab_global; };      // itab_global: the kernel reads the int tables from global memory (no LDS copy)
@@ -395,6 +440,34 @@ int sgrl_phase_prof(unsigned long long* host, int n_env, int reset) {
   return 0;
 }
 #endif
+
+int sgrl_debug_chol_solve(int flags, const int32_t* n, const double* C, const double* rhs, double* C_out, double* x_out, int32_t* ok) {
+  constexpr int LD = SGRL_DEBUG_CHOL_LD;
+  if (!n || !C || !rhs || !C_out || !x_out || !ok) return fail(SGRL_ERR_ARG, "sgrl_debug_chol_solve: null pointer");
+  for (int p = 0; p < ((flags & 1) ? 2 : 1); p++)
+    if (n[p] < 0 || n[p] * (n[p] + 1) / 2 > LD) return fail(SGRL_ERR_ARG, "sgrl_debug_chol_solve: n out of range");
+  const size_t bytes = sizeof(double) * (4 * LD + 128) + sizeof(int32_t) * 4;
+  char* d = nullptr;
+  HIP_TRY(hipMalloc((void**)&d, bytes));
+  double* dC = (double*)d; double* dCo = dC + 2 * LD; double* dr = dCo + 2 * LD; double* dx = dr + 64;
+  int32_t* dn = (int32_t*)(dx + 64); int32_t* dok = dn + 2;
+  const int32_t n2[2] = {n[0], (flags & 1) ? n[1] : 0};
+  hipError_t e = hipMemset(d, 0, bytes);
+  if (e == hipSuccess) e = hipMemcpy(dC, C, sizeof(double) * 2 * LD, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dr, rhs, sizeof(double) * 64, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dn, n2, sizeof(n2), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    k_debug_chol_solve<<<1, 64>>>(flags, dn, dC, dr, dCo, dx, dok);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(C_out, dCo, sizeof(double) * 2 * LD, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(x_out, dx, sizeof(double) * 64, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(ok, dok, sizeof(int32_t) * 2, hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  if (e != hipSuccess) return fail(SGRL_ERR_HIP, std::string("sgrl_debug_chol_solve: ") + hipGetErrorString(e));
+  return SGRL_OK;
+}
 
 void sgrl_engine_destroy(sgrl_engine* e) {
   if (!e) return;

@@ -369,6 +369,16 @@ SGRL_DEV double rng_uniform01(uint64_t seed, uint32_t env_id, uint32_t episode, 
 #define SGRL_TICK(id)
 #endif
 
+// does the wave policy solve a small SPD system with one right-hand side on registers (chol_solve_packed(n, C, x, minval))?
+// The GPU policies do (wave_hip.h, wave_half.h); a policy without it keeps the explicit-inverse path of lcp_block_pivot.
+template <class T> T& ref_of();      // unevaluated contexts only
+template <class Wv, class = void>
+struct HasCholSolve { static constexpr bool value = false; };
+template <class Wv>
+struct HasCholSolve<Wv, decltype((void)ref_of<Wv>().chol_solve_packed(0, ref_of<double*>(), ref_of<double*>(), 0.0))> {
+  static constexpr bool value = true;
+};
+
 // ------------------------------------------------------------------------------------------------
 template <class W>
 struct Engine {
@@ -1110,6 +1120,13 @@ struct Engine {
     });
   }
 
+  // C x = rhs in place on the wave policy's register solver, where it has one and the operands lie in LDS (false: not solved)
+  template <bool SMALL>
+  SGRL_DEV bool chol_solve_small(int nf, double* C, double* x) {
+    if constexpr (SMALL && HasCholSolve<W>::value) return w.chol_solve_packed(nf, C, x, kMinVal);
+    else return false;
+  }
+
   // Exact solve of the dual LCP  0 <= f  _|_  A f + b >= 0  (A = Y Y' + R, SPD) by block principal pivoting (Judice &
   // Pires): guess the free set F, solve A_FF x = -b_F by a lane-parallel root-free Cholesky, exchange every index that
   // violates x_F >= 0 or (A x + b)_G >= 0 (a single index once the number of violations has stopped shrinking), repeat.
@@ -1143,8 +1160,8 @@ struct Engine {
         }
       });
       // A_FF = Y_F Y_F' + diag(R_F), compact packed lower triangle: on the FP64 matrix cores where the wave policy has them
-      // and the free set is large enough to pay, else one lane per entry
-      if (!w.aff_rows(nf, nv, R.Y, ldy, R.flist, R.eR, C))
+      // and the free set is large enough to pay, else one lane per entry.  An empty free set has no block to form or factor.
+      if (nf > 0 && !w.aff_rows(nf, nv, R.Y, ldy, R.flist, R.eR, C))
       w.lanes(nf * (nf + 1) / 2, [&](int p) {
         int i, j;
         tri_decode(p, &i, &j);
@@ -1164,9 +1181,13 @@ struct Engine {
         C[p] = a;
       });
       SGRL_TICK(12);
-      // factor A_FF and solve.  Small free sets in LDS: Cholesky + explicit inverse of the factor on registers (wave
-      // policy), then x = T'(T rhs) as two recurrence-free products; otherwise the lane-parallel root-free elimination
-      if (SMALL && w.chol_inv_packed(nf, C, kMinVal)) {
+      // factor A_FF and solve, ONE right-hand side per round.  Small free sets in LDS: Cholesky on registers with the right-hand
+      // side riding as one more column, then a back substitution on registers (wave policy, chol_solve_packed); a policy without
+      // that primitive takes Cholesky + explicit inverse of the factor on registers and x = T'(T rhs) as two recurrence-free
+      // products; otherwise the lane-parallel root-free elimination
+      if (nf == 0) {
+      } else if (chol_solve_small<SMALL>(nf, C, xwp)) {
+      } else if (SMALL && !HasCholSolve<W>::value && w.chol_inv_packed(nf, C, kMinVal)) {
         w.lanes(nf, [&](int i) {
           double z = 0;
           for (int c = 0; c <= i; c++) z += C[i * (i + 1) / 2 + c] * xwp[c];

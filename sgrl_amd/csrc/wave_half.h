@@ -100,6 +100,63 @@ struct HalfWaveT : P {
     return true;
   }
 
+  // ---- Cholesky and one right-hand side, x <- M^-1 x (HipWaveT::chol_solve_reg, same arithmetic in the same order): the pivot loop
+  // above without the inverse rows, the right-hand side as one more column, then the back substitution on the columns of L reloaded
+  // from Pm (column k scaled by d_k, zero diagonal slots).  Lanes 16..31 compute on their own row's values, never stored.
+  template <int NMAX>
+  SGRL_DEV void chol_solve_reg(int n, double* Pm, double* x, double minval) {
+    const bool act = lane < n;
+    const int li = act ? lane : 0;
+    double* rowp = Pm + li * (li + 1) / 2;
+    double a[NMAX];
+#pragma unroll
+    for (int k = 0; k < NMAX; k++) a[k] = rowp[k < li ? k : li];
+    double r = x[li];
+#pragma unroll
+    for (int j = 0; j < NMAX; j++) {
+      if (j < n) {
+        const double c = a[j];
+        double pj = P::bcast16(c, j);
+        pj = pj < minval ? minval : pj;
+        const double dj = inv_sqrt(pj);
+        const double l = c * dj;
+        const double lb = lane > j ? l : 0.0;
+        const double zj = P::bcast16(r, j) * dj;
+        r = lane == j ? zj * dj : r - lb * zj;
+        a[j] = lb * dj;
+#pragma unroll
+        for (int k = j + 1; k < NMAX; k++) a[k] -= l * P::bcast16(l, k);
+      }
+    }
+    if (act) {
+#pragma unroll
+      for (int k = NMAX - 1; k >= 0; k--) rowp[k < li ? k : li] = a[k];
+    }
+    P::sync();
+    const int nl = n > 0 ? n - 1 : 0;
+#pragma unroll
+    for (int j = 1; j < NMAX; j++) {
+      const int jj = j < nl ? j : nl;
+      a[j] = Pm[jj * (jj + 1) / 2 + (lane < jj ? lane : jj)];
+    }
+#pragma unroll
+    for (int j = NMAX - 1; j >= 1; j--) {
+      if (j < n) r -= a[j] * P::bcast16(r, j);
+    }
+    if (act) x[lane] = r;
+    P::sync();
+  }
+  // per half, like chol_inv_packed; false leaves Pm and x untouched
+  SGRL_DEV bool chol_solve_packed(int n, double* Pm, double* x, double minval) {
+    if (n <= 3) chol_solve_reg<3>(n, Pm, x, minval);                    // HipWaveT::chol_solve_packed: the free sets are small
+    else if (n <= 6) chol_solve_reg<6>(n, Pm, x, minval);
+    else if (NVCAP >= 9 && n <= 9) chol_solve_reg<9>(n, Pm, x, minval);
+    else if (NVCAP >= 12 && n <= 12) chol_solve_reg<12>(n, Pm, x, minval);
+    else if (NVCAP >= 15 && n <= 15) chol_solve_reg<15>(n, Pm, x, minval);
+    else return false;
+    return true;
+  }
+
   // Y_r <- T Y_r for the rows r < nrhs (HipWaveT::trmm_rows_reg): two lanes share one right-hand side, 16 right-hand sides of each
   // environment per pass
   template <int NMAX>

@@ -255,6 +255,73 @@ struct HipWaveT {
     else return false;
     return true;
   }
+  // Cholesky and ONE right-hand side: x <- M^-1 x.  The pivot loop of chol_inv_reg (same clamp, same rsqrt, same trailing update
+  // in the same order) without the inverse rows: the explicit inverse pays for the mass matrix's many right-hand sides, for one
+  // it is 3 n NMAX / 2 wasted instructions.  The right-hand side rides as one more column (z_j = rhs_j d_j on lane j, rhs_i -=
+  // l_ij z_j below it).  Back substitution, L' x = z: the rows of L go to P with column k scaled by d_k (the multiplier l d_j is
+  // at hand at pivot j) and a ZERO on the diagonal, so lane k reloads column k as P[tri(j) + min(k, j)] -- entries at and above
+  // the diagonal read that zero and need no mask -- and every step is one broadcast of x_j and one FMA:
+  //   x_k = z_k d_k - sum_{j > k} (l_jk d_k) x_j.
+  // On return P holds that scaled strict lower triangle of L (diagonal slots zero), x the solution.
+  template <int NMAX>
+  __device__ __forceinline__ void chol_solve_reg(int n, double* P, double* x, double minval) {
+    const bool act = lane < n;
+    const int li = act ? lane : 0;
+    double* rowp = P + li * (li + 1) / 2;
+    double a[NMAX];
+#pragma unroll
+    for (int k = 0; k < NMAX; k++) a[k] = rowp[k < li ? k : li];          // k > i re-reads the diagonal: unused filler
+    double r = x[li];
+#pragma unroll
+    for (int j = 0; j < NMAX; j++) {
+      if (j < n) {
+        const double c = a[j];
+        double pj = read_lane(c, j);
+        pj = pj < minval ? minval : pj;
+        const double dj = rsqrt(pj);
+        const double l = c * dj;
+        const double lb = lane > j ? l : 0.0;              // column j of L strictly below the diagonal
+        const double zj = read_lane(r, j) * dj;
+        r = lane == j ? zj * dj : r - lb * zj;
+        a[j] = lb * dj;
+#pragma unroll
+        for (int k = j + 1; k < NMAX; k++) a[k] -= l * read_lane(l, k);
+      }
+    }
+    if (act) {
+#pragma unroll
+      for (int k = NMAX - 1; k >= 0; k--) rowp[k < li ? k : li] = a[k];   // k > i lands on the diagonal slot first, k = i zeroes it
+    }
+    __syncthreads();
+    const int nl = n > 0 ? n - 1 : 0;
+#pragma unroll
+    for (int j = 1; j < NMAX; j++) {                                      // rows beyond n: a valid address, never used
+      const int jj = j < nl ? j : nl;
+      a[j] = P[jj * (jj + 1) / 2 + (lane < jj ? lane : jj)];
+    }
+#pragma unroll
+    for (int j = NMAX - 1; j >= 1; j--) {
+      if (j < n) r -= a[j] * read_lane(r, j);
+    }
+    if (act) x[lane] = r;
+    __syncthreads();
+  }
+  // true when a register version covers n; false leaves P and x untouched
+  __device__ __forceinline__ bool chol_solve_packed(int n_in, double* P, double* x, double minval) {
+    const int n = __builtin_amdgcn_readfirstlane(n_in);
+    // the size classes of chol_inv_packed, and two below them: the free sets of lcp_block_pivot, this primitive's one caller, are
+    // small (walker mix: 55 % of the pivoting rounds have at most 3 rows, 85 % at most 6; profiles/lcp_solve_ab.txt)
+    if (n <= 3) chol_solve_reg<3>(n, P, x, minval);
+    else if (n <= 6) chol_solve_reg<6>(n, P, x, minval);
+    else if (NVCAP >= 9 && n <= 9) chol_solve_reg<9>(n, P, x, minval);
+    else if (NVCAP >= 12 && n <= 12) chol_solve_reg<12>(n, P, x, minval);
+    else if (NVCAP >= 15 && n <= 15) chol_solve_reg<15>(n, P, x, minval);
+    else if (NVCAP >= 18 && n <= 18) chol_solve_reg<18>(n, P, x, minval);
+    else if (NVCAP >= 21 && n <= 21) chol_solve_reg<21>(n, P, x, minval);
+    else if (NVCAP >= 24 && n <= 24) chol_solve_reg<24>(n, P, x, minval);
+    else return false;
+    return true;
+  }
   // Y_r <- T Y_r for the rows r < nrhs, T = packed lower-triangular matrix (the explicit L^-1).  Two lanes share one
   // right-hand side: lane h of the pair keeps the entries c = h (mod 2) of the row in registers and accumulates its half
   // of every output; the halves meet over one DPP exchange.  Every entry of T is an LDS read shared by all pairs, all
