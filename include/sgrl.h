@@ -69,6 +69,14 @@ int sgrl_paired_envs(const sgrl_engine* e);
 /* VecEnv.reset(): every env starts a new episode.  obs: DEV float[n_env*obs_max_len]; obs64: DEV double[...] or NULL. */
 int sgrl_reset(sgrl_engine* e, float* obs, double* obs64, void* stream);
 
+/* The partial reset (`reset_idx` of batched simulators): for every env i with mask[i] != 0 exactly what the step's auto-reset does --
+ * a new episode number, the start state from the counter RNG (seed, env_id_base + i, episode), kinematics, row i of obs / obs64, the
+ * record, step count 0.  For mask[i] == 0 nothing of env i is read or written: its record, its counters and its rows of obs / obs64
+ * stay as they are.  mask: DEV uint8[n_env].  Launches as sgrl_reset does (one per launch group), no host synchronisation, capturable.
+ * After sgrl_step(auto_reset = 0) and sgrl_reset_where(done) the engine is where sgrl_step(auto_reset = 1) leaves it, and in between
+ * obs holds the observation the finished episodes really ended on.  SGRL_ERR_ARG (nothing launched) for a null engine, mask or obs. */
+int sgrl_reset_where(sgrl_engine* e, const uint8_t* mask, float* obs, double* obs64, void* stream);
+
 /* VecEnv.step(actions).  actions: DEV float[n_env*action_max_len] (policy order, zero padded).
  * Outputs (DEV, any may be NULL except obs): obs float[n_env*obs_max_len] -- the post-step observation, or the
  * reset observation for envs that finished and auto_reset != 0 (reference subproc_vec_env.py:12-15);
@@ -108,6 +116,18 @@ int sgrl_pack_transitions(const float* obs, int ld_obs, const float* action, int
  * all_done (one int32: non-zero when every environment has finished its first episode). */
 int sgrl_round_record(const float* reward, const uint8_t* done, uint8_t* done_list, int64_t* ep_steps, float* ep_reward, float* reward_buf,
                       uint8_t* store, float* done_bool, int32_t* all_done, int n_env, int max_episode_steps, void* stream);
+
+/* The same bookkeeping for a round that keeps EVERY episode, not only each environment's first.  done_list, ep_steps, ep_reward,
+ * reward_buf and all_done follow sgrl_round_record's rule bit for bit (episode statistics, update count and round end do not move).
+ * One more state array, cur_steps int64[n_env] (steps of the episode in progress, zero at the start of a round), dates the time limit
+ * of the later episodes: timeout = cur_steps + 1 == max_episode_steps; done_bool = done && !timeout; cur_steps = 0 after a done or a
+ * timeout, else + 1.  store = 1 for every environment, except in a step taken after the round was already complete (all_done set by
+ * the previous call of the round), which stores nothing: a caller that reads the flag one step late fills its buffers as one that
+ * reads it at once.  all_done is therefore in/out here and was_complete (one int32) receives its previous value: zero both when a
+ * round begins.  Launches as sgrl_round_record does. */
+int sgrl_round_record_all(const float* reward, const uint8_t* done, uint8_t* done_list, int64_t* ep_steps, float* ep_reward, float* reward_buf,
+                          int64_t* cur_steps, uint8_t* store, float* done_bool, int32_t* all_done, int32_t* was_complete, int n_env,
+                          int max_episode_steps, void* stream);
 
 /* The learner's side of the replay push: the kept rows of one gathered block (format above) go into the ring buffers of their
  * morphologies -- reference common/buffer.py:75-84 `add_transition` once per stored row, one buffer per morphology

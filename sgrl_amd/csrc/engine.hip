@@ -49,8 +49,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
   env_step_wave<DimsAny, sgrl::HipWaveT<kLightNv>>(a, out, __builtin_amdgcn_readfirstlane(a.block_env[blockIdx.x]));
 }
 
+// sgrl_reset: every environment.  sgrl_reset_where: `out.done` carries the caller's mask [n_env] (the reset writes no `done`, so the
+// field is free here); a workgroup whose environment is not selected leaves before it reads or writes anything of that environment.
 __global__ __launch_bounds__(64) void k_env_reset(BatchArgs a, StepOut out) {
   const int env = __builtin_amdgcn_readfirstlane(a.block_env[blockIdx.x]);
+  if (out.done && !__builtin_amdgcn_readfirstlane((int)out.done[env])) return;
   SgrlModelView m; sgrl::Layout o; double* S; int32_t* I;
   setup<DimsAny>(a, env, &m, &o, &S, &I);
   sgrl::HipWave w;
@@ -309,6 +312,42 @@ __global__ __launch_bounds__(256) void k_round_record(const float* __restrict__ 
   const bool now = was || d;
   done_list[i] = now ? 1 : 0;
   if (!now) *all_done = 0;
+}
+
+// The round record that keeps EVERY episode (sgrl.h sgrl_round_record_all).  The first-episode block is k_round_record's, on the same
+// state, so the episode statistics, the update count and the round end do not move; what is stored does:
+//   timeout = cur_steps + 1 == max_steps;  done_bool = done && !timeout;  cur_steps = (done || timeout) ? 0 : cur_steps + 1
+//   store = 1, except in a step taken after the round was already complete (`was_complete`: the `all_done` of the previous step of the
+//   round, moved over by k_round_carry before this kernel clears `all_done` again)
+__global__ void k_round_carry(int* all_done, int* was_complete) {
+  if (threadIdx.x == 0) { *was_complete = *all_done; *all_done = 1; }
+}
+
+__global__ __launch_bounds__(256) void k_round_record_all(const float* __restrict__ reward, const uint8_t* __restrict__ done, uint8_t* done_list,
+                                                          long long* ep_steps, float* ep_reward, float* reward_buf, long long* cur_steps,
+                                                          uint8_t* store, float* done_bool, int* all_done, const int* was_complete, int n,
+                                                          int max_steps) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const bool raw = done[i] != 0;
+  bool d = raw;
+  const long long st = ep_steps[i];
+  if (st + 1 == (long long)max_steps) d = true;
+  float rb = reward_buf[i] + reward[i];
+  float er = ep_reward[i];
+  if (d && er == 0.f) { er = rb; rb = 0.f; }
+  ep_reward[i] = er;
+  reward_buf[i] = rb;
+  const bool was = done_list[i] != 0;
+  if (!was) ep_steps[i] = st + 1;
+  const bool now = was || d;
+  done_list[i] = now ? 1 : 0;
+  if (!now) *all_done = 0;
+  const long long cs = cur_steps[i];
+  const bool timeout = cs + 1 == (long long)max_steps;
+  done_bool[i] = (raw && !timeout) ? 1.f : 0.f;
+  cur_steps[i] = (raw || timeout) ? 0 : cs + 1;
+  store[i] = *was_complete ? 0 : 1;
 }
 
 // replay ingest: one workgroup per row of the gathered block; the row's morphology picks the ring, slot[] the place in it
@@ -809,6 +848,14 @@ int sgrl_reset(sgrl_engine* e, float* obs, double* obs64, void* stream) {
   return launch_groups(e, k_env_reset, out, (hipStream_t)stream);
 }
 
+int sgrl_reset_where(sgrl_engine* e, const uint8_t* mask, float* obs, double* obs64, void* stream) {
+  if (!e || !mask || !obs) return fail(SGRL_ERR_ARG, "sgrl_reset_where: null engine, mask or obs");
+  StepOut out{};
+  out.obs32 = obs; out.obs64 = obs64;
+  out.done = const_cast<uint8_t*>(mask);     // read only: k_env_reset takes its mask here
+  return launch_groups(e, k_env_reset, out, (hipStream_t)stream);
+}
+
 int sgrl_step(sgrl_engine* e, const float* actions, float* obs, float* reward, uint8_t* done, float* dist,
               uint8_t* truncated, double* obs64, double* reward64, int auto_reset, void* stream) {
   if (!e || !actions || !obs) return fail(SGRL_ERR_ARG, "sgrl_step: null engine, actions or obs");
@@ -905,6 +952,20 @@ int sgrl_round_record(const float* reward, const uint8_t* done, uint8_t* done_li
   hipLaunchKernelGGL(k_round_record, dim3((n_env + 255) / 256), dim3(256), 0, (hipStream_t)stream, reward, done, done_list,
                      reinterpret_cast<long long*>(ep_steps), ep_reward, reward_buf, store, done_bool, reinterpret_cast<int*>(all_done), n_env,
                      max_episode_steps);
+  HIP_TRY(hipGetLastError());
+  return SGRL_OK;
+}
+
+int sgrl_round_record_all(const float* reward, const uint8_t* done, uint8_t* done_list, int64_t* ep_steps, float* ep_reward, float* reward_buf,
+                          int64_t* cur_steps, uint8_t* store, float* done_bool, int32_t* all_done, int32_t* was_complete, int n_env,
+                          int max_episode_steps, void* stream) {
+  if (!reward || !done || !done_list || !ep_steps || !ep_reward || !reward_buf || !cur_steps || !store || !done_bool || !all_done ||
+      !was_complete || n_env <= 0)
+    return fail(SGRL_ERR_ARG, "sgrl_round_record_all: bad argument");
+  hipLaunchKernelGGL(k_round_carry, dim3(1), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<int*>(all_done), reinterpret_cast<int*>(was_complete));
+  hipLaunchKernelGGL(k_round_record_all, dim3((n_env + 255) / 256), dim3(256), 0, (hipStream_t)stream, reward, done, done_list,
+                     reinterpret_cast<long long*>(ep_steps), ep_reward, reward_buf, reinterpret_cast<long long*>(cur_steps), store, done_bool,
+                     reinterpret_cast<int*>(all_done), reinterpret_cast<const int*>(was_complete), n_env, max_episode_steps);
   HIP_TRY(hipGetLastError());
   return SGRL_OK;
 }

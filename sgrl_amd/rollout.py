@@ -175,8 +175,14 @@ class Rollout(object):
         self.noise_step += 1
         return self.actions
 
-    def step(self, actions):
-        return self.env.step_device(actions)
+    def step(self, actions, auto_reset=True):
+        """auto_reset=False: finished environments keep their post-step observation until `reset_where` restarts them."""
+        return self.env.step_device(actions, auto_reset=auto_reset)
+
+    def reset_where(self, mask):
+        """Start a new episode in the environments with mask[i] != 0, leave the others alone (vec_env.reset_where)."""
+        self.obs = self.env.reset_where(mask)
+        return self.obs
 
 
 class ReplayGather(object):
@@ -344,12 +350,22 @@ class RoundCollector(object):
         done_bool = curr_done[i];  if episode_timesteps[i] + 1 == max_episode_steps: done_bool = 0, curr_done[i] = True
         if not done_list[i]:  episode_timesteps[i] += 1;  store (obs, action, next_obs, reward, done_bool);
                               done_list[i] |= curr_done[i]
+
+    store_all=True (off by default; no learning curve has been run with it) keeps EVERY episode of the round instead: the block
+    above runs unchanged on the same lists, so the round end, `episode_reward`, `episode_timesteps` and `per_morph_iter` are what
+    they are without the switch, and every step is stored with the `done` of the episode it belongs to -- `cur_steps` counts the
+    episode in progress:
+        timeout = cur_steps[i] + 1 == max_episode_steps;  done_bool = curr_done[i] and not timeout
+        cur_steps[i] = 0 if curr_done[i] or timeout else cur_steps[i] + 1
+        store every i -- except in a step taken after the round was already complete (a flag read one step late, TransitionSink
+        lag_flag), which stores nothing, as in the default mode
     """
 
-    def __init__(self, n_env, max_episode_steps=1000, device="cpu"):
+    def __init__(self, n_env, max_episode_steps=1000, device="cpu", store_all=False):
         self.n = n_env
         self.max_episode_steps = int(max_episode_steps)
         self.device = torch.device(device)
+        self.store_all = bool(store_all)
         self.begin_round()
 
     def begin_round(self):
@@ -357,6 +373,12 @@ class RoundCollector(object):
         self.episode_timesteps = torch.zeros(self.n, dtype=torch.long, device=self.device)
         self.episode_reward = torch.zeros(self.n, dtype=torch.float32, device=self.device)
         self._reward_buf = torch.zeros(self.n, dtype=torch.float32, device=self.device)
+        if self.store_all:
+            self.cur_steps = torch.zeros(self.n, dtype=torch.long, device=self.device)
+            self._complete = torch.zeros((), dtype=torch.bool, device=self.device)      # "the previous step found the round complete"
+            if getattr(self, "_all_done", None) is not None:      # the one-launch form carries that word in its flag pair
+                self._all_done.zero_()
+                self._was_complete.zero_()
 
     def record(self, reward, curr_done, sync=True):
         """reward float[n], curr_done bool/uint8[n] as returned by VecEnv.step.  Returns (store_mask bool[n],
@@ -365,7 +387,8 @@ class RoundCollector(object):
         (TransitionSink reads it a step late through pinned memory instead of stalling the step on it)."""
         if self.device.type == "cuda" and FUSED_RECORD:
             return self._record_hip(reward, curr_done, sync)
-        curr_done = curr_done.to(torch.bool).clone()
+        raw_done = curr_done.to(torch.bool)
+        curr_done = raw_done.clone()
         done_bool = curr_done.to(torch.float32)
         timeout = (self.episode_timesteps + 1) == self.max_episode_steps
         done_bool = torch.where(timeout, torch.zeros_like(done_bool), done_bool)
@@ -378,6 +401,12 @@ class RoundCollector(object):
         self.episode_timesteps += store.to(torch.long)
         self.done_list |= store & curr_done
         fin = self.done_list.all()
+        if self.store_all:
+            timeout = (self.cur_steps + 1) == self.max_episode_steps
+            done_bool = (raw_done & ~timeout).to(torch.float32)
+            self.cur_steps = torch.where(raw_done | timeout, torch.zeros_like(self.cur_steps), self.cur_steps + 1)
+            store = ~self._complete.expand(self.n)
+            self._complete = fin
         return store, done_bool, (bool(fin) if sync else fin)
 
     def _record_hip(self, reward, curr_done, sync):
@@ -394,11 +423,31 @@ class RoundCollector(object):
             self._store_u8 = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
             self._done_bool = torch.zeros(self.n, dtype=torch.float32, device=self.device)
             self._all_done = torch.zeros(1, dtype=torch.int32, device=self.device)
+            if self.store_all:
+                self._was_complete = torch.zeros(1, dtype=torch.int32, device=self.device)
         p = lambda t: ctypes.c_void_p(t.data_ptr())
+        if self.store_all:
+            _lib.check(L.sgrl_round_record_all(p(r), p(d), p(self.done_list), p(self.episode_timesteps), p(self.episode_reward),
+                                               p(self._reward_buf), p(self.cur_steps), p(self._store_u8), p(self._done_bool),
+                                               p(self._all_done), p(self._was_complete), self.n, self.max_episode_steps,
+                                               ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
+                       "sgrl_round_record_all")
+            return self._store_u8.view(torch.bool), self._done_bool, (bool(self._all_done.item()) if sync else self._all_done)
         _lib.check(L.sgrl_round_record(p(r), p(d), p(self.done_list), p(self.episode_timesteps), p(self.episode_reward), p(self._reward_buf),
                                        p(self._store_u8), p(self._done_bool), p(self._all_done), self.n, self.max_episode_steps,
                                        ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "sgrl_round_record")
         return self._store_u8.view(torch.bool), self._done_bool, (bool(self._all_done.item()) if sync else self._all_done)
+
+    def set_complete(self, flag):
+        """store_all over several ranks: `flag` (int32[1] tensor on this device, or a bool) is the round-complete word reduced over
+        ALL ranks; it replaces this rank's own, so a rank that finished early goes on storing until the slowest one has finished."""
+        if not self.store_all:
+            return
+        if not torch.is_tensor(flag):
+            flag = torch.tensor([1 if flag else 0], dtype=torch.int32, device=self.device)
+        self._complete = flag.reshape(()) != 0
+        if getattr(self, "_all_done", None) is not None and flag.data_ptr() != self._all_done.data_ptr():
+            self._all_done.copy_(flag.reshape(1))
 
     def per_morph_iter(self):
         """Number of TD3 updates per morphology after the round (reference trainer.py:244)."""
@@ -419,8 +468,9 @@ class TransitionSink(object):
     (sgrl_amd.replay.DeviceReplayBuffer) on the learner rank, None elsewhere."""
 
     def __init__(self, env_morph, num_limbs, obs_max_len, action_max_len, max_episode_steps=1000, device="cpu", buffers=None,
-                 dst=0, lag_flag=False):
-        """lag_flag: push() answers with the round-finished flag of the PREVIOUS step, fetched through pinned memory, instead of
+                 dst=0, lag_flag=False, store_all=False):
+        """store_all: keep every row of every episode of a round, not only each environment's first episode (RoundCollector
+        store_all); round end, episode statistics and update count are unchanged.  lag_flag: push() answers with the round-finished flag of the PREVIOUS step, fetched through pinned memory, instead of
         synchronising the host with the device on every step (and, at N > 1, waiting for a 4-byte all-reduce).  The round then ends
         one step late; that step's rows carry store = False on every rank (every environment had finished), so buffers, episode
         statistics and update counts are exactly those of the immediate flag -- only the environments take one more, discarded,
@@ -431,7 +481,8 @@ class TransitionSink(object):
         self.env_morph = torch.as_tensor(env_morph, dtype=torch.long, device=self.device)
         self.num_limbs = [int(l) for l in num_limbs]
         n = int(self.env_morph.numel())
-        self.collector = RoundCollector(n, max_episode_steps, device=self.device)
+        self.store_all = bool(store_all)
+        self.collector = RoundCollector(n, max_episode_steps, device=self.device, store_all=self.store_all)
         self.gather = ReplayGather(n, obs_max_len, action_max_len, self.device, dst=dst)
         self.is_learner = self.gather.rank == dst
         self.buffers = buffers
@@ -507,6 +558,7 @@ class TransitionSink(object):
             flag = finished if finished.dtype == torch.int32 else finished.to(torch.int32).reshape(1)      # (the fused record hands out its int32 flag)
             if self.gather.world > 1:
                 self.dist.all_reduce(flag, op=self.dist.ReduceOp.MIN)      # on the stream; nobody waits for it on the host
+                self.collector.set_complete(flag)
             host, ev = self._lag_spare.pop() if self._lag_spare else (torch.zeros(1, dtype=torch.int32).pin_memory(), torch.cuda.Event())
             host.copy_(flag, non_blocking=True)
             ev.record(torch.cuda.current_stream(self.device))
@@ -521,6 +573,7 @@ class TransitionSink(object):
             flag = torch.tensor([1 if finished else 0], dtype=torch.int32, device=self.device)
             self.dist.all_reduce(flag, op=self.dist.ReduceOp.MIN)
             finished = bool(flag.item())
+            self.collector.set_complete(flag)
         return finished
 
     # ---- learner: one pair of launches per step (CUDA) -------------------------------------------------------------------

@@ -24,7 +24,7 @@ from .td3 import Agent, default_train_args
 class DeviceTrainer(object):
     def __init__(self, env_names, envs_per_morph, args=None, seed=0, device="cuda:0", max_buffer_size=1000000,
                  batch_size=None, dst=0, graph_updates=False, tune_gemms=False, rollout=None, lag_flag=True, device_sampler=False,
-                 device_noise=False, graph_hip_kernels=False, **env_kw):
+                 device_noise=False, graph_hip_kernels=False, store_all_episodes=False, true_next_obs=False, **env_kw):
         """graph_updates: replay the TD3 update from hipGraphs (td3.GraphedUpdates; td3.GraphedMlpUpdates
         for an `mlp` agent); graph_hip_kernels (with graph_updates; ignored for `mlp`): td3.GraphedUpdates(hip_kernels=True) -- a
         swat or smp agent keeps its HIP target chain and its `*_train_kernels` switch under the graphs instead of being switched
@@ -44,7 +44,17 @@ class DeviceTrainer(object):
         (`seed`, the rollout's noise_step, global environment number, slot), instead of torch.randn / uniform_ on the rollout's
         generator.  Off by default for the same reason: it changes what a seeded run explores, and the learning curves have not
         been re-run on it.  noise_step follows the same rule as the draw counter: a snapshot has no field for it and assigning
-        tot_env_steps sets the rollout's noise_step to the restored value; a checkpoint carries it."""
+        tot_env_steps sets the rollout's noise_step to the restored value; a checkpoint carries it.
+        store_all_episodes: the replay rings receive every row of every episode of a round, not only each environment's first episode
+        (rollout.RoundCollector store_all; DESIGN section 5: at config 5 about 70 of 250 simulated steps per environment are kept
+        otherwise).  Round end, updates per morphology and the train statistics are those of the default; tot_env_steps counts what is
+        stored, so it grows faster.  true_next_obs: the `next_obs` stored for the last transition of an episode is the observation the
+        episode ended on, not the next episode's reset observation (which the reference stores, subproc_vec_env.py:12-15, and which
+        a time-limit cut with done_bool = 0 bootstraps from): collect_step steps with auto_reset=False, pushes, then restarts the
+        finished environments (Rollout.reset_where) -- one more launch per launch group, no synchronisation; an injected rollout
+        driver without reset_where is a ValueError.  Both are independent, constructor arguments like device_noise (a checkpoint is
+        taken at a round end, where the collector's state is fresh, and carries neither), and off by default: they change what a
+        seeded run learns from, and NO learning curve has been run with either."""
         import torch.distributed as dist
         self.dist = dist
         self.rank = dist.get_rank() if dist.is_initialized() else 0
@@ -80,6 +90,11 @@ class DeviceTrainer(object):
                               max_episode_steps=self.args.max_episode_steps, hold_weights=True, device_noise=device_noise, **env_kw)
         # an injected driver without explore_into keeps the tensor-op path
         self.device_noise = bool(device_noise) and hasattr(self.ro, "explore_into")
+        self.store_all_episodes = bool(store_all_episodes)
+        self.true_next_obs = bool(true_next_obs)
+        if self.true_next_obs and not hasattr(self.ro, "reset_where"):
+            raise ValueError("true_next_obs=True needs a rollout driver with reset_where(mask) and step(actions, auto_reset=False); "
+                             "%s has none" % type(self.ro).__name__)
         env = self.ro.env
         self.device = env.device
         self.graph_dicts = self.ro.graph_dicts
@@ -92,7 +107,7 @@ class DeviceTrainer(object):
             self.buffers = [DeviceReplayBuffer(41 * L, 3 * L, max_buffer_size, device=self.device) for L in env.num_limbs]
         self.sink = TransitionSink(env.env_morph, env.num_limbs, env.obs_max_len, env.action_max_len,
                                    max_episode_steps=self.args.max_episode_steps, device=self.device, buffers=self.buffers,
-                                   dst=dst, lag_flag=lag_flag)
+                                   dst=dst, lag_flag=lag_flag, store_all=self.store_all_episodes)
         self.prev_obs = torch.zeros_like(env.obs)
         self.num_envs_global = env.num_envs * self.world
         self._updates = 0            # TD3 updates so far (the reference adds them to tot_env_steps: trainer.py:250)
@@ -171,6 +186,12 @@ class DeviceTrainer(object):
                     a = self.ro.add_exploration_noise(a, self.args.expl_noise)
                 self.ro.actions.copy_(a)
                 a = self.ro.actions
+        if self.true_next_obs:
+            # the packer copies the observation every episode really ended on; only then do the finished environments start anew
+            obs, rew, done, _ = self.ro.step(a, auto_reset=False)
+            finished = self.sink.push(self.prev_obs, a, obs, rew, done)
+            self.ro.reset_where(done)
+            return finished
         obs, rew, done, _ = self.ro.step(a)
         return self.sink.push(self.prev_obs, a, obs, rew, done)    # the round-finished flag (GPU: read one step late, no stall)
 

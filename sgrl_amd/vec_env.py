@@ -201,9 +201,32 @@ class BatchedModularVecEnv(VecEnv):
         _lib.check(self._L.sgrl_reset(self._h, self._p(self.obs), self._p(self.obs64), self._stream()), "sgrl_reset")
         return self.obs
 
+    def reset_where(self, mask):
+        """Reset the environments with mask[i] != 0 exactly as the step's auto-reset does (new episode number, start state from the
+        counter RNG, row i of `obs`); nothing of the others is read or written (include/sgrl.h sgrl_reset_where).  mask: bool or uint8
+        CUDA tensor [n] on this environment's device -- `self.done` after `step_device(actions, auto_reset=False)` is the usual one,
+        and between the two calls `obs` holds the observation each finished episode really ended on.  No synchronisation.  Returns
+        `self.obs`."""
+        t = self.torch
+        if not isinstance(mask, t.Tensor) or mask.dtype not in (t.bool, t.uint8):
+            raise ValueError("reset_where: mask must be a bool or uint8 tensor, not %s"
+                             % (mask.dtype if isinstance(mask, t.Tensor) else type(mask).__name__))
+        if tuple(mask.shape) != (self.num_envs,):
+            raise ValueError("reset_where: mask must have shape (%d,), not %s" % (self.num_envs, tuple(mask.shape)))
+        if mask.device != self.obs.device:
+            raise ValueError("reset_where: mask must live on %s, not %s" % (self.obs.device, mask.device))
+        if not mask.is_contiguous():
+            mask = mask.contiguous()
+        if mask.dtype == t.bool:
+            mask = mask.view(t.uint8)
+        _lib.check(self._L.sgrl_reset_where(self._h, self._p(mask), self._p(self.obs), self._p(self.obs64), self._stream()),
+                   "sgrl_reset_where")
+        return self.obs
+
     def step_device(self, actions, auto_reset=True):
         """actions: float32 CUDA tensor [n, action_max_len] (contiguous).  Returns (obs, rew, done, dist) tensors
-        that are overwritten by the next call."""
+        that are overwritten by the next call.  auto_reset=False: a finished environment keeps its post-step observation and
+        state until `reset_where` (or the next reset) starts its next episode."""
         assert actions.is_cuda and actions.dtype == self.torch.float32 and actions.is_contiguous()
         assert tuple(actions.shape) == (self.num_envs, self.action_max_len)
         _lib.check(self._L.sgrl_step(self._h, self._p(actions), self._p(self.obs), self._p(self.rew), self._p(self.done),
