@@ -163,6 +163,13 @@ int sgrl_ingest_block(const float* block, int n_rows, int obs_len, int act_len, 
  * array holds both problems' slots, 2 * SGRL_DEBUG_CHOL_LD / 64 / 2 entries, whatever the flags), and ok[p] = 1 if the policy has a register instance for n[p] (0: it returned false; C_out / x_out then show the inputs untouched). */
 #define SGRL_DEBUG_CHOL_LD 352
 int sgrl_debug_chol_solve(int flags, const int32_t* n, const double* C, const double* rhs, double* C_out, double* x_out, int32_t* ok);
+/* The same with the FORM of the register linear algebra chosen: 1 = what the step kernels run and sgrl_debug_chol_solve shows (lane
+ * broadcast inside the FMA instruction, wave_hip.h fnma_bcast16_run), 0 = the lane-read form it replaced, built into these hooks only
+ * so that a test can hold the two against each other bit for bit. */
+int sgrl_debug_chol_solve_form(int form, int flags, const int32_t* n, const double* C, const double* rhs, double* C_out, double* x_out, int32_t* ok);
+/* chol_inv_packed alone: C_out = the packed L^-1 (diagonal included) of each problem.  `policy` 0 = full wave (one problem), 1 = half
+ * wave (two problems); n, C, C_out, ok laid out as above. */
+int sgrl_debug_chol_inv(int form, int policy, const int32_t* n, const double* C, double* C_out, int32_t* ok);
 
 const char* sgrl_last_error(void);
 const char* sgrl_version(void);

@@ -212,7 +212,7 @@ def bind_explore(L):
 
 EXPORTS = ["sgrl_engine_create", "sgrl_engine_destroy", "sgrl_num_envs", "sgrl_record_stride", "sgrl_lds_bytes", "sgrl_launch_groups", "sgrl_fixed_dim_groups", "sgrl_paired_envs",
            "sgrl_reset", "sgrl_reset_where", "sgrl_step", "sgrl_get_records", "sgrl_set_records", "sgrl_refresh", "sgrl_time_steps", "sgrl_pack_transitions", "sgrl_round_record", "sgrl_round_record_all", "sgrl_ingest_rows", "sgrl_ingest_block", "sgrl_ingest_ws_words",
-           "sgrl_debug_chol_solve", "sgrl_last_error", "sgrl_version"]
+           "sgrl_debug_chol_solve", "sgrl_debug_chol_solve_form", "sgrl_debug_chol_inv", "sgrl_last_error", "sgrl_version"]
 
 
 def check(rc, what):

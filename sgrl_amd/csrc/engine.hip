@@ -70,14 +70,17 @@ __global__ __launch_bounds__(64) void k_env_refresh(BatchArgs a, StepOut out) {
   sgrl::env_refresh(w, m, o, S, I, io);
 }
 
-// ---- test hook (sgrl_debug_chol_solve): the register solver for one right-hand side on either wave policy, one workgroup --------
-template <class Wv>
-__device__ __forceinline__ void debug_chol_solve(Wv& w, int n, double* C, double* x, double* wv, bool inverse, int32_t* ok) {
+// ---- test hooks (sgrl_debug_chol_solve, sgrl_debug_chol_inv): the register solvers on either wave policy, one workgroup.  FORM 1 is
+// what the step kernels run (broadcast inside the FMA instruction), FORM 0 the lane-read form it replaced: only these hooks build it.
+template <int FORM, class Wv>
+__device__ __forceinline__ void debug_chol_solve(Wv& w, int n, double* C, double* x, double* wv, bool inverse, bool inverse_only, int32_t* ok) {
   bool done;
-  if (!inverse) {
-    done = w.chol_solve_packed(n, C, x, sgrl::kMinVal);
+  if (inverse_only) {
+    done = w.template chol_inv_packed<FORM>(n, C, sgrl::kMinVal);
+  } else if (!inverse) {
+    done = w.template chol_solve_packed<FORM>(n, C, x, sgrl::kMinVal);
   } else {                     // the explicit-inverse path as lcp_block_pivot ran it: x = T'(T rhs), two lane-per-entry products
-    done = w.chol_inv_packed(n, C, sgrl::kMinVal);
+    done = w.template chol_inv_packed<FORM>(n, C, sgrl::kMinVal);
     if (done) {
       w.lanes(n, [&](int i) {
         double z = 0;
@@ -102,13 +105,16 @@ __global__ __launch_bounds__(64) void k_debug_chol_solve(int flags, const int32_
   sx[t] = rhs[t];
   swv[t] = 0.0;
   __syncthreads();
+  const bool inv = (flags & 2) != 0, inv_only = (flags & 8) != 0;
   if (flags & 1) {
     sgrl::HalfWaveT<15, sgrl::HipHalfPrim<sgrl::DimsAny>> w;
     const int h = w.half;
-    debug_chol_solve(w, n[h], sC + h * LD, sx + h * 32, swv + h * 32, (flags & 2) != 0, ok + h);
+    if (flags & 4) debug_chol_solve<0>(w, n[h], sC + h * LD, sx + h * 32, swv + h * 32, inv, inv_only, ok + h);
+    else debug_chol_solve<1>(w, n[h], sC + h * LD, sx + h * 32, swv + h * 32, inv, inv_only, ok + h);
   } else {
     sgrl::HipWave w;
-    debug_chol_solve(w, n[0], sC, sx, swv, (flags & 2) != 0, ok);
+    if (flags & 4) debug_chol_solve<0>(w, n[0], sC, sx, swv, inv, inv_only, ok);
+    else debug_chol_solve<1>(w, n[0], sC, sx, swv, inv, inv_only, ok);
   }
   __syncthreads();
   for (int i = t; i < 2 * LD; i += 64) C_out[i] = sC[i];
@@ -480,23 +486,25 @@ int sgrl_phase_prof(unsigned long long* host, int n_env, int reset) {
 }
 #endif
 
-int sgrl_debug_chol_solve(int flags, const int32_t* n, const double* C, const double* rhs, double* C_out, double* x_out, int32_t* ok) {
+// kflags: bit 0 half-wave policy, bit 1 explicit-inverse path, bit 2 lane-read form, bit 3 chol_inv_packed alone
+static int debug_chol_run(const char* who, int kflags, const int32_t* n, const double* C, const double* rhs, double* C_out, double* x_out, int32_t* ok) {
   constexpr int LD = SGRL_DEBUG_CHOL_LD;
-  if (!n || !C || !rhs || !C_out || !x_out || !ok) return fail(SGRL_ERR_ARG, "sgrl_debug_chol_solve: null pointer");
-  for (int p = 0; p < ((flags & 1) ? 2 : 1); p++)
-    if (n[p] < 0 || n[p] * (n[p] + 1) / 2 > LD) return fail(SGRL_ERR_ARG, "sgrl_debug_chol_solve: n out of range");
+  const std::string name(who);
+  if (!n || !C || !rhs || !C_out || !x_out || !ok) return fail(SGRL_ERR_ARG, name + ": null pointer");
+  for (int p = 0; p < ((kflags & 1) ? 2 : 1); p++)
+    if (n[p] < 0 || n[p] * (n[p] + 1) / 2 > LD) return fail(SGRL_ERR_ARG, name + ": n out of range");
   const size_t bytes = sizeof(double) * (4 * LD + 128) + sizeof(int32_t) * 4;
   char* d = nullptr;
   HIP_TRY(hipMalloc((void**)&d, bytes));
   double* dC = (double*)d; double* dCo = dC + 2 * LD; double* dr = dCo + 2 * LD; double* dx = dr + 64;
   int32_t* dn = (int32_t*)(dx + 64); int32_t* dok = dn + 2;
-  const int32_t n2[2] = {n[0], (flags & 1) ? n[1] : 0};
+  const int32_t n2[2] = {n[0], (kflags & 1) ? n[1] : 0};
   hipError_t e = hipMemset(d, 0, bytes);
   if (e == hipSuccess) e = hipMemcpy(dC, C, sizeof(double) * 2 * LD, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(dr, rhs, sizeof(double) * 64, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(dn, n2, sizeof(n2), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
-    k_debug_chol_solve<<<1, 64>>>(flags, dn, dC, dr, dCo, dx, dok);
+    k_debug_chol_solve<<<1, 64>>>(kflags, dn, dC, dr, dCo, dx, dok);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -504,8 +512,22 @@ int sgrl_debug_chol_solve(int flags, const int32_t* n, const double* C, const do
   if (e == hipSuccess) e = hipMemcpy(x_out, dx, sizeof(double) * 64, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(ok, dok, sizeof(int32_t) * 2, hipMemcpyDeviceToHost);
   (void)hipFree(d);
-  if (e != hipSuccess) return fail(SGRL_ERR_HIP, std::string("sgrl_debug_chol_solve: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(SGRL_ERR_HIP, name + ": " + hipGetErrorString(e));
   return SGRL_OK;
+}
+
+int sgrl_debug_chol_solve(int flags, const int32_t* n, const double* C, const double* rhs, double* C_out, double* x_out, int32_t* ok) {
+  return debug_chol_run("sgrl_debug_chol_solve", flags & 3, n, C, rhs, C_out, x_out, ok);
+}
+int sgrl_debug_chol_solve_form(int form, int flags, const int32_t* n, const double* C, const double* rhs, double* C_out, double* x_out, int32_t* ok) {
+  if (form != 0 && form != 1) return fail(SGRL_ERR_ARG, "sgrl_debug_chol_solve_form: form must be 0 or 1");
+  return debug_chol_run("sgrl_debug_chol_solve_form", (flags & 3) | (form ? 0 : 4), n, C, rhs, C_out, x_out, ok);
+}
+int sgrl_debug_chol_inv(int form, int policy, const int32_t* n, const double* C, double* C_out, int32_t* ok) {
+  if (form != 0 && form != 1) return fail(SGRL_ERR_ARG, "sgrl_debug_chol_inv: form must be 0 or 1");
+  const double rhs[64] = {0};
+  double x_out[64];
+  return debug_chol_run("sgrl_debug_chol_inv", (policy & 1) | 8 | (form ? 0 : 4), n, C, rhs, C_out, x_out, ok);
 }
 
 void sgrl_engine_destroy(sgrl_engine* e) {

@@ -18,12 +18,21 @@
 //   double half_sum(double) / half_max(double)   reduction over the 32 lanes of the half, result in every lane
 //   uint32_t half_ballot(bool)     bit l = predicate of logical lane l of the half
 //   fence_lane / fenced / kFixedDims / hdr_const   as in HipWaveT
+// Optional, taken where the set has them (HasFnmaBcast; wave_hip.h fnma_bcast16_run / _self: the broadcast inside the FMA instruction):
+//   void fnma_run<N, J0>(double* p, double src, double mul)   p[i] -= mul * (src of logical lane J0 + i), i < N, valid in lanes 0..15
+//   void fnma_self<N, J>(double* p, double mul)                p[i] -= mul * (p[i] of logical lane J), mul = 0 in lane J itself
+//   double bcast16c<J>(double x)                               bcast16 with a compile-time lane
 #pragma once
 #include <stdint.h>
 
 #include "step_body.h"
 
 namespace sgrl {
+
+template <class P, class = void>
+struct HasFnmaBcast { static constexpr int value = 0; };
+template <class P>
+struct HasFnmaBcast<P, decltype((void)P::template fnma_run<1, 0>(ref_of<double*>(), 0.0, 0.0))> { static constexpr int value = 1; };
 
 template <int NVCAP, class P>
 struct HalfWaveT : P {
@@ -58,7 +67,27 @@ struct HalfWaveT : P {
 
   // ---- Cholesky + explicit inverse of the factor on registers (HipWaveT::chol_inv_reg, same arithmetic in the same order): lane i of
   // the half owns row i; pivots and finished inverse rows are broadcast inside the half's first 16-lane row
-  template <int NMAX>
+  // FORM 1: the primitive set's one-instruction broadcast FMAs, same operations in the same order; FORM 0: bcast16, statement for
+  // statement what the CPU fibers run (and what sgrl_debug_chol_inv holds FORM 1 against on the device)
+  template <int NMAX, int J>
+  SGRL_DEV void chol_inv_pivots_fnma(int n, double* a, double& mydj, double minval) {
+    if constexpr (J < NMAX) {
+      if (J < n) {
+        const double c = a[J + 1];
+        double pj = P::template bcast16c<J>(c);
+        pj = pj < minval ? minval : pj;
+        const double dj = inv_sqrt(pj);
+        const double l = c * dj;
+        mydj = lane == J ? dj : mydj;
+        const double lm = lane > J ? l * dj : 0.0;
+        a[J] = lane == J ? 1.0 : 0.0;
+        P::template fnma_self<J + 1, J>(a, lm);
+        P::template fnma_run<NMAX - 1 - J, J + 1>(a + J + 2, l, l);
+      }
+      chol_inv_pivots_fnma<NMAX, J + 1>(n, a, mydj, minval);
+    }
+  }
+  template <int NMAX, int FORM = HasFnmaBcast<P>::value>
   SGRL_DEV void chol_inv_reg(int n, double* Pm, double minval) {
     const bool act = lane < n;
     const int li = act ? lane : 0;
@@ -67,6 +96,8 @@ struct HalfWaveT : P {
 #pragma unroll
     for (int k = 0; k < NMAX; k++) a[k + 1] = rowp[k < li ? k : li];
     double mydj = 0.0;
+    if constexpr (FORM == 1) chol_inv_pivots_fnma<NMAX, 0>(n, a, mydj, minval);
+    else
 #pragma unroll
     for (int j = 0; j < NMAX; j++) {
       if (j < n) {
@@ -92,10 +123,11 @@ struct HalfWaveT : P {
   }
   // The instance is picked PER HALF (two free sets of different size classes run one after the other): the result of one
   // environment never depends on what its wave mate is doing.
+  template <int FORM = HasFnmaBcast<P>::value>
   SGRL_DEV bool chol_inv_packed(int n, double* Pm, double minval) {
-    if (NVCAP >= 9 && n <= 9) chol_inv_reg<9>(n, Pm, minval);
-    else if (NVCAP >= 12 && n <= 12) chol_inv_reg<12>(n, Pm, minval);
-    else if (NVCAP >= 15 && n <= 15) chol_inv_reg<15>(n, Pm, minval);
+    if (NVCAP >= 9 && n <= 9) chol_inv_reg<9, FORM>(n, Pm, minval);
+    else if (NVCAP >= 12 && n <= 12) chol_inv_reg<12, FORM>(n, Pm, minval);
+    else if (NVCAP >= 15 && n <= 15) chol_inv_reg<15, FORM>(n, Pm, minval);
     else return false;
     return true;
   }
@@ -103,7 +135,32 @@ struct HalfWaveT : P {
   // ---- Cholesky and one right-hand side, x <- M^-1 x (HipWaveT::chol_solve_reg, same arithmetic in the same order): the pivot loop
   // above without the inverse rows, the right-hand side as one more column, then the back substitution on the columns of L reloaded
   // from Pm (column k scaled by d_k, zero diagonal slots).  Lanes 16..31 compute on their own row's values, never stored.
-  template <int NMAX>
+  template <int NMAX, int J>
+  SGRL_DEV void chol_solve_pivots_fnma(int n, double* a, double& r, double minval) {
+    if constexpr (J < NMAX) {
+      if (J < n) {
+        const double c = a[J];
+        double pj = P::template bcast16c<J>(c);
+        pj = pj < minval ? minval : pj;
+        const double dj = inv_sqrt(pj);
+        const double l = c * dj;
+        const double lb = lane > J ? l : 0.0;
+        const double zj = P::template bcast16c<J>(r) * dj;
+        r = lane == J ? zj * dj : r - lb * zj;
+        a[J] = lb * dj;
+        P::template fnma_run<NMAX - 1 - J, J + 1>(a + J + 1, l, l);
+      }
+      chol_solve_pivots_fnma<NMAX, J + 1>(n, a, r, minval);
+    }
+  }
+  template <int J>
+  SGRL_DEV void chol_solve_back_fnma(int n, double* a, double& r) {
+    if constexpr (J >= 1) {
+      if (J < n) P::template fnma_self<1, J>(&r, a[J]);    // lane j itself: a[j] is the zero of its diagonal slot
+      chol_solve_back_fnma<J - 1>(n, a, r);
+    }
+  }
+  template <int NMAX, int FORM = HasFnmaBcast<P>::value>
   SGRL_DEV void chol_solve_reg(int n, double* Pm, double* x, double minval) {
     const bool act = lane < n;
     const int li = act ? lane : 0;
@@ -112,6 +169,8 @@ struct HalfWaveT : P {
 #pragma unroll
     for (int k = 0; k < NMAX; k++) a[k] = rowp[k < li ? k : li];
     double r = x[li];
+    if constexpr (FORM == 1) chol_solve_pivots_fnma<NMAX, 0>(n, a, r, minval);
+    else
 #pragma unroll
     for (int j = 0; j < NMAX; j++) {
       if (j < n) {
@@ -139,6 +198,8 @@ struct HalfWaveT : P {
       const int jj = j < nl ? j : nl;
       a[j] = Pm[jj * (jj + 1) / 2 + (lane < jj ? lane : jj)];
     }
+    if constexpr (FORM == 1) chol_solve_back_fnma<NMAX - 1>(n, a, r);
+    else
 #pragma unroll
     for (int j = NMAX - 1; j >= 1; j--) {
       if (j < n) r -= a[j] * P::bcast16(r, j);
@@ -147,12 +208,13 @@ struct HalfWaveT : P {
     P::sync();
   }
   // per half, like chol_inv_packed; false leaves Pm and x untouched
+  template <int FORM = HasFnmaBcast<P>::value>
   SGRL_DEV bool chol_solve_packed(int n, double* Pm, double* x, double minval) {
-    if (n <= 3) chol_solve_reg<3>(n, Pm, x, minval);                    // HipWaveT::chol_solve_packed: the free sets are small
-    else if (n <= 6) chol_solve_reg<6>(n, Pm, x, minval);
-    else if (NVCAP >= 9 && n <= 9) chol_solve_reg<9>(n, Pm, x, minval);
-    else if (NVCAP >= 12 && n <= 12) chol_solve_reg<12>(n, Pm, x, minval);
-    else if (NVCAP >= 15 && n <= 15) chol_solve_reg<15>(n, Pm, x, minval);
+    if (n <= 3) chol_solve_reg<3, FORM>(n, Pm, x, minval);                    // HipWaveT::chol_solve_packed: the free sets are small
+    else if (n <= 6) chol_solve_reg<6, FORM>(n, Pm, x, minval);
+    else if (NVCAP >= 9 && n <= 9) chol_solve_reg<9, FORM>(n, Pm, x, minval);
+    else if (NVCAP >= 12 && n <= 12) chol_solve_reg<12, FORM>(n, Pm, x, minval);
+    else if (NVCAP >= 15 && n <= 15) chol_solve_reg<15, FORM>(n, Pm, x, minval);
     else return false;
     return true;
   }

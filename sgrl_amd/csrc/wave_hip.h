@@ -19,6 +19,84 @@ __device__ __forceinline__ double read_lane(double x, int l) {
   const int hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
   return __hiloint2double(hi, lo);
 }
+// ---- row broadcast and FMA in ONE instruction (gfx950 DP DPP) ------------------------------------------------------------------
+// v_fmac_f64_dpp vdst, vsrc0, -vsrc1 row_newbcast:J   computes   vdst -= (lane J of this lane's 16-lane row of vsrc0) * vsrc1
+// with one rounding: the same operation as fma(-m, bcast(x), acc), without the two instructions that only move the double
+// (2 x v_readlane_b32 or 2 x v_mov_b32_dpp; tools/micro/dpp_f64_lab.hip, profiles/dpp_bcast_ab.txt).  row_newbcast is the only DPP
+// control the 64-bit operations take, and hipcc does not fold a 64-bit DPP move into the FMA, so the instruction is written as
+// inline asm -- ONE statement per group of accumulators that share their source, because the compiler pads no hazard of an asm
+// statement: a VALU write of a VGPR needs 2 wait states before a DPP read of it, a write of EXEC 5; every statement opens with
+// `s_nop 4` (5 states), inside a group no instruction DPP-reads what another one of the group wrote, and every statement closes with
+// `s_nop 1`: the compiler's own DPP moves (bcast16_b64 of the next pivot) may read an accumulator right behind the statement, and
+// its hazard pass does not see the writes inside.  Source lanes must be active.
+#define SGRL_REP1(M, S) M(0)
+#define SGRL_REP2(M, S) SGRL_REP1(M, S) S() M(1)
+#define SGRL_REP3(M, S) SGRL_REP2(M, S) S() M(2)
+#define SGRL_REP4(M, S) SGRL_REP3(M, S) S() M(3)
+#define SGRL_REP5(M, S) SGRL_REP4(M, S) S() M(4)
+#define SGRL_REP6(M, S) SGRL_REP5(M, S) S() M(5)
+#define SGRL_REP7(M, S) SGRL_REP6(M, S) S() M(6)
+#define SGRL_REP8(M, S) SGRL_REP7(M, S) S() M(7)
+#define SGRL_REP9(M, S) SGRL_REP8(M, S) S() M(8)
+#define SGRL_REP10(M, S) SGRL_REP9(M, S) S() M(9)
+#define SGRL_REP11(M, S) SGRL_REP10(M, S) S() M(10)
+#define SGRL_REP12(M, S) SGRL_REP11(M, S) S() M(11)
+#define SGRL_REP13(M, S) SGRL_REP12(M, S) S() M(12)
+#define SGRL_REP14(M, S) SGRL_REP13(M, S) S() M(13)
+#define SGRL_REP15(M, S) SGRL_REP14(M, S) S() M(14)
+#define SGRL_REP16(M, S) SGRL_REP15(M, S) S() M(15)
+#define SGRL_REP17(M, S) SGRL_REP16(M, S) S() M(16)
+#define SGRL_REP18(M, S) SGRL_REP17(M, S) S() M(17)
+#define SGRL_REP19(M, S) SGRL_REP18(M, S) S() M(18)
+#define SGRL_REP20(M, S) SGRL_REP19(M, S) S() M(19)
+#define SGRL_REP21(M, S) SGRL_REP20(M, S) S() M(20)
+#define SGRL_REP22(M, S) SGRL_REP21(M, S) S() M(21)
+#define SGRL_REP23(M, S) SGRL_REP22(M, S) S() M(22)
+#define SGRL_REP24(M, S) SGRL_REP23(M, S) S() M(23)
+#define SGRL_SEP_NONE()
+#define SGRL_SEP_COMMA() ,
+#define SGRL_DPP_ACC(i) "+v"(p[i])
+// accumulator i takes lane j + i of the shared source; the assembler adds the two constants
+#define SGRL_DPP_RUN(i) "v_fmac_f64_dpp %" #i ", %[s], -%[m] row_newbcast:%c[j]+" #i " row_mask:0xf bank_mask:0xf\n\t"
+// accumulator i is its own source, lane j of it
+#define SGRL_DPP_SELF(i) "v_fmac_f64_dpp %" #i ", %" #i ", -%[m] row_newbcast:%c[j] row_mask:0xf bank_mask:0xf\n\t"
+#define SGRL_DPP_CASE_RUN(n) \
+  else if constexpr (N == n) asm volatile("s_nop 4\n\t" SGRL_REP##n(SGRL_DPP_RUN, SGRL_SEP_NONE) "s_nop 1" : SGRL_REP##n(SGRL_DPP_ACC, SGRL_SEP_COMMA) : [s] "v"(src), [m] "v"(mul), [j] "i"(J0));
+#define SGRL_DPP_CASE_SELF(n) \
+  else if constexpr (N == n) asm volatile("s_nop 4\n\t" SGRL_REP##n(SGRL_DPP_SELF, SGRL_SEP_NONE) "s_nop 1" : SGRL_REP##n(SGRL_DPP_ACC, SGRL_SEP_COMMA) : [m] "v"(mul), [j] "i"(J));
+#define SGRL_DPP_CASES(C) C(1) C(2) C(3) C(4) C(5) C(6) C(7) C(8) C(9) C(10) C(11) C(12) C(13) C(14) C(15) C(16) C(17) C(18) C(19) C(20) C(21) C(22) C(23) C(24)
+// p[i] -= mul * (lane J0 + i of the row of src), i < N
+template <int N, int J0>
+__device__ __forceinline__ void fnma_bcast16_run(double* p, double src, double mul) {
+  static_assert(N <= 24 && J0 >= 0 && J0 + N <= 16, "one asm statement: at most 24 accumulators, lanes of one 16-lane row");
+  if constexpr (N <= 0) {}
+  SGRL_DPP_CASES(SGRL_DPP_CASE_RUN)
+}
+// p[i] -= mul * (lane J of the row of p[i]), i < N.  The source lane itself must see mul = 0 (it is read while it is written).
+template <int N, int J>
+__device__ __forceinline__ void fnma_bcast16_self(double* p, double mul) {
+  static_assert(N <= 24 && J >= 0 && J < 16, "one asm statement: at most 24 accumulators, a lane of the 16-lane row");
+  if constexpr (N <= 0) {}
+  SGRL_DPP_CASES(SGRL_DPP_CASE_SELF)
+}
+// acc -= mul * (lane J of the row of src)
+template <int J>
+__device__ __forceinline__ void fnma_bcast16(double& acc, double src, double mul) { fnma_bcast16_run<1, J>(&acc, src, mul); }
+// lane J of every 16-lane row to the whole row, one v_mov_b64_dpp (the compiler pads its hazards)
+template <int J>
+__device__ __forceinline__ double bcast16_b64(double x) {
+  static_assert(J >= 0 && J < 16, "a lane of the 16-lane row");
+  return __builtin_amdgcn_update_dpp(0.0, x, 0x150 + J, 0xF, 0xF, false);
+}
+// v_permlane16_swap (gfx950): odd rows of the first operand <-> even rows of the second; with both = x the pair comes back as
+// (row0 row0 row2 row2), (row1 row1 row3 row3): every lane holds both row values of its half
+__device__ __forceinline__ void rows_of_half(double x, double* even, double* odd) {
+  const unsigned lo = (unsigned)__double2loint(x), hi = (unsigned)__double2hiint(x);
+  const auto l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+  const auto h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+  *even = __hiloint2double((int)h[0], (int)l[0]);
+  *odd = __hiloint2double((int)h[1], (int)l[1]);
+}
 // 64-lane sum with a wave-uniform result: xor butterflies inside each 16-lane row on the DPP network
 // (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror), then four v_readlane row totals.
 __device__ __forceinline__ double wave_sum(double x) {
@@ -209,7 +287,55 @@ struct HipWaveT {
   // lane folds it in with the same multiplier l_ij it uses for the trailing update -- the inverse costs no extra
   // dependent steps, only issue slots.  On return P holds L^-1 (packed lower triangle INCLUDING its diagonal): the
   // triangular solves of the caller become plain dot products with no recurrence.
-  template <int NMAX>
+  //
+  // FORM 1 (what the step kernels run): the broadcast rides in the FMA, v_fmac_f64_dpp row_newbcast (fnma_bcast16_run / _self above),
+  // one instruction where the lane-read form below takes three.  Lane i holds row i and data only flows from lower to higher
+  // lanes, so up to 16 dofs everything stays inside the first 16-lane row.  Beyond 16: rows 16.. of the matrix sit in the second
+  // DPP row and need the multiplier column of the first one -- mirrored once per pivot with v_permlane16_swap -- for the columns
+  // k < 16, their own row's for k >= 16 (lanes < 16 compute filler there: columns beyond their diagonal); the inverse update runs
+  // on DPP for the pivots j >= 16 (lanes < 16 have the multiplier 0 and read a finished entry of their own row: a finite value
+  // times zero) and keeps the lane reads for j < 16, where a cross-row copy of j + 1 values would cost the same.  Same operations
+  // in the same order, bit for bit.  FORM 0: the lane-read form, kept for sgrl_debug_chol_inv to hold FORM 1 against.
+  template <int NMAX, int J>
+  __device__ __forceinline__ void chol_inv_pivots_dpp(int n, double* a, double& mydj, double minval) {
+    if constexpr (J < NMAX) {
+      if (J < n) {
+        const double c = a[J + 1];
+        double pj;
+        if constexpr (NMAX <= 16) pj = bcast16_b64<J>(c); else pj = read_lane(c, J);
+        pj = pj < minval ? minval : pj;
+        const double dj = rsqrt(pj);
+        const double l = c * dj;
+        mydj = lane == J ? dj : mydj;
+        const double lm = lane > J ? l * dj : 0.0;       // multiplier for the (unscaled) row j of the inverse
+        a[J] = lane == J ? 1.0 : 0.0;                    // column j of the identity enters now
+        if constexpr (NMAX <= 16) fnma_bcast16_self<J + 1, J>(a, lm);
+        else if constexpr (J >= 16) fnma_bcast16_self<J + 1, J - 16>(a, lm);
+        else {
+#pragma unroll
+          for (int c2 = 0; c2 <= J; c2++) a[c2] -= lm * read_lane(a[c2], J);
+        }
+        trailing_dpp<NMAX, J>(a + 1, l);
+      }
+      chol_inv_pivots_dpp<NMAX, J + 1>(n, a, mydj, minval);
+    }
+  }
+  // a[k] -= l * (l of lane k) for the columns k = J + 1 .. NMAX - 1 of the trailing matrix
+  template <int NMAX, int J>
+  __device__ __forceinline__ void trailing_dpp(double* a, double l) {
+    if constexpr (NMAX <= 16) {
+      fnma_bcast16_run<NMAX - 1 - J, J + 1>(a + J + 1, l, l);
+    } else {
+      constexpr int KB = J + 1 > 16 ? J + 1 : 16;        // first column served by the lane's own DPP row
+      if constexpr (J + 1 < 16) {
+        double le, lo;
+        rows_of_half(l, &le, &lo);             // le: the first row's l in both rows
+        fnma_bcast16_run<15 - J, J + 1>(a + J + 1, le, l);
+      }
+      fnma_bcast16_run<NMAX - KB, KB - 16>(a + KB, l, l);
+    }
+  }
+  template <int NMAX, int FORM = 1>
   __device__ __forceinline__ void chol_inv_reg(int n, double* P, double minval) {
     const bool act = lane < n;
     const int li = act ? lane : 0;
@@ -220,6 +346,8 @@ struct HipWaveT {
 #pragma unroll
     for (int k = 0; k < NMAX; k++) a[k + 1] = rowp[k < li ? k : li];      // k > i re-reads the diagonal: unused filler
     double mydj = 0.0;
+    if constexpr (FORM == 1) chol_inv_pivots_dpp<NMAX, 0>(n, a, mydj, minval);
+    else
 #pragma unroll
     for (int j = 0; j < NMAX; j++) {
       if (j < n) {
@@ -244,14 +372,15 @@ struct HipWaveT {
     __syncthreads();
   }
   // true when a register version covers n (the caller falls back to its LDS factorisation otherwise)
+  template <int FORM = 1>
   __device__ __forceinline__ bool chol_inv_packed(int n_in, double* P, double minval) {
     const int n = __builtin_amdgcn_readfirstlane(n_in);
-    if (NVCAP >= 9 && n <= 9) chol_inv_reg<9>(n, P, minval);            // one instance per dof count of the shipped nv <= 24 morphologies
-    else if (NVCAP >= 12 && n <= 12) chol_inv_reg<12>(n, P, minval);
-    else if (NVCAP >= 15 && n <= 15) chol_inv_reg<15>(n, P, minval);
-    else if (NVCAP >= 18 && n <= 18) chol_inv_reg<18>(n, P, minval);
-    else if (NVCAP >= 21 && n <= 21) chol_inv_reg<21>(n, P, minval);
-    else if (NVCAP >= 24 && n <= 24) chol_inv_reg<24>(n, P, minval);
+    if (NVCAP >= 9 && n <= 9) chol_inv_reg<9, FORM>(n, P, minval);            // one instance per dof count of the shipped nv <= 24 morphologies
+    else if (NVCAP >= 12 && n <= 12) chol_inv_reg<12, FORM>(n, P, minval);
+    else if (NVCAP >= 15 && n <= 15) chol_inv_reg<15, FORM>(n, P, minval);
+    else if (NVCAP >= 18 && n <= 18) chol_inv_reg<18, FORM>(n, P, minval);
+    else if (NVCAP >= 21 && n <= 21) chol_inv_reg<21, FORM>(n, P, minval);
+    else if (NVCAP >= 24 && n <= 24) chol_inv_reg<24, FORM>(n, P, minval);
     else return false;
     return true;
   }
@@ -263,7 +392,35 @@ struct HipWaveT {
   // the diagonal read that zero and need no mask -- and every step is one broadcast of x_j and one FMA:
   //   x_k = z_k d_k - sum_{j > k} (l_jk d_k) x_j.
   // On return P holds that scaled strict lower triangle of L (diagonal slots zero), x the solution.
-  template <int NMAX>
+  // FORM as in chol_inv_reg; the back substitution rides on DPP up to 16 dofs (the solution entry x_j sits in the row of every
+  // lane below it) and keeps the lane reads beyond.
+  template <int NMAX, int J>
+  __device__ __forceinline__ void chol_solve_pivots_dpp(int n, double* a, double& r, double minval) {
+    if constexpr (J < NMAX) {
+      if (J < n) {
+        const double c = a[J];
+        double pj, rj;
+        if constexpr (NMAX <= 16) { pj = bcast16_b64<J>(c); rj = bcast16_b64<J>(r); } else { pj = read_lane(c, J); rj = read_lane(r, J); }
+        pj = pj < minval ? minval : pj;
+        const double dj = rsqrt(pj);
+        const double l = c * dj;
+        const double lb = lane > J ? l : 0.0;              // column j of L strictly below the diagonal
+        const double zj = rj * dj;
+        r = lane == J ? zj * dj : r - lb * zj;
+        a[J] = lb * dj;
+        trailing_dpp<NMAX, J>(a, l);
+      }
+      chol_solve_pivots_dpp<NMAX, J + 1>(n, a, r, minval);
+    }
+  }
+  template <int J>
+  __device__ __forceinline__ void chol_solve_back_dpp(int n, double* a, double& r) {
+    if constexpr (J >= 1) {
+      if (J < n) fnma_bcast16_self<1, J>(&r, a[J]);        // lane j itself: a[j] is the zero of its diagonal slot
+      chol_solve_back_dpp<J - 1>(n, a, r);
+    }
+  }
+  template <int NMAX, int FORM = 1>
   __device__ __forceinline__ void chol_solve_reg(int n, double* P, double* x, double minval) {
     const bool act = lane < n;
     const int li = act ? lane : 0;
@@ -272,6 +429,8 @@ struct HipWaveT {
 #pragma unroll
     for (int k = 0; k < NMAX; k++) a[k] = rowp[k < li ? k : li];          // k > i re-reads the diagonal: unused filler
     double r = x[li];
+    if constexpr (FORM == 1) chol_solve_pivots_dpp<NMAX, 0>(n, a, r, minval);
+    else
 #pragma unroll
     for (int j = 0; j < NMAX; j++) {
       if (j < n) {
@@ -299,6 +458,8 @@ struct HipWaveT {
       const int jj = j < nl ? j : nl;
       a[j] = P[jj * (jj + 1) / 2 + (lane < jj ? lane : jj)];
     }
+    if constexpr (FORM == 1 && NMAX <= 16) chol_solve_back_dpp<NMAX - 1>(n, a, r);
+    else
 #pragma unroll
     for (int j = NMAX - 1; j >= 1; j--) {
       if (j < n) r -= a[j] * read_lane(r, j);
@@ -307,18 +468,19 @@ struct HipWaveT {
     __syncthreads();
   }
   // true when a register version covers n; false leaves P and x untouched
+  template <int FORM = 1>
   __device__ __forceinline__ bool chol_solve_packed(int n_in, double* P, double* x, double minval) {
     const int n = __builtin_amdgcn_readfirstlane(n_in);
     // the size classes of chol_inv_packed, and two below them: the free sets of lcp_block_pivot, this primitive's one caller, are
     // small (walker mix: 55 % of the pivoting rounds have at most 3 rows, 85 % at most 6; profiles/lcp_solve_ab.txt)
-    if (n <= 3) chol_solve_reg<3>(n, P, x, minval);
-    else if (n <= 6) chol_solve_reg<6>(n, P, x, minval);
-    else if (NVCAP >= 9 && n <= 9) chol_solve_reg<9>(n, P, x, minval);
-    else if (NVCAP >= 12 && n <= 12) chol_solve_reg<12>(n, P, x, minval);
-    else if (NVCAP >= 15 && n <= 15) chol_solve_reg<15>(n, P, x, minval);
-    else if (NVCAP >= 18 && n <= 18) chol_solve_reg<18>(n, P, x, minval);
-    else if (NVCAP >= 21 && n <= 21) chol_solve_reg<21>(n, P, x, minval);
-    else if (NVCAP >= 24 && n <= 24) chol_solve_reg<24>(n, P, x, minval);
+    if (n <= 3) chol_solve_reg<3, FORM>(n, P, x, minval);
+    else if (n <= 6) chol_solve_reg<6, FORM>(n, P, x, minval);
+    else if (NVCAP >= 9 && n <= 9) chol_solve_reg<9, FORM>(n, P, x, minval);
+    else if (NVCAP >= 12 && n <= 12) chol_solve_reg<12, FORM>(n, P, x, minval);
+    else if (NVCAP >= 15 && n <= 15) chol_solve_reg<15, FORM>(n, P, x, minval);
+    else if (NVCAP >= 18 && n <= 18) chol_solve_reg<18, FORM>(n, P, x, minval);
+    else if (NVCAP >= 21 && n <= 21) chol_solve_reg<21, FORM>(n, P, x, minval);
+    else if (NVCAP >= 24 && n <= 24) chol_solve_reg<24, FORM>(n, P, x, minval);
     else return false;
     return true;
   }
@@ -588,15 +750,11 @@ struct HipHalfPrim {
     }
   }
   __device__ static __forceinline__ double xor1(double x) { return dpp_move<0xB1>(x); }      // quad_perm [1,0,3,2]
-  // v_permlane16_swap (gfx950): odd rows of the first operand <-> even rows of the second; with both = x the pair comes back as
-  // (row0 row0 row2 row2), (row1 row1 row3 row3): every lane holds both row values of its half
-  __device__ static __forceinline__ void rows_of_half(double x, double* even, double* odd) {
-    const unsigned lo = (unsigned)__double2loint(x), hi = (unsigned)__double2hiint(x);
-    const auto l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    const auto h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    *even = __hiloint2double((int)h[0], (int)l[0]);
-    *odd = __hiloint2double((int)h[1], (int)l[1]);
-  }
+  __device__ static __forceinline__ void rows_of_half(double x, double* even, double* odd) { sgrl::rows_of_half(x, even, odd); }
+  // the one-instruction broadcast FMAs (top of this file); wave_half.h takes them where the primitive set has them
+  template <int N, int J0> __device__ static __forceinline__ void fnma_run(double* p, double src, double mul) { fnma_bcast16_run<N, J0>(p, src, mul); }
+  template <int N, int J> __device__ static __forceinline__ void fnma_self(double* p, double mul) { fnma_bcast16_self<N, J>(p, mul); }
+  template <int J> __device__ static __forceinline__ double bcast16c(double x) { return bcast16_b64<J>(x); }
   __device__ static __forceinline__ double half_sum(double x) {
     x += dpp_move<0xB1>(x);
     x += dpp_move<0x4E>(x);
